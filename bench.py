@@ -20,6 +20,9 @@ Extra objects on the same line:
                  volume_wall_first_call_s = the cold first call (plans, 0.53 GB weight pack, graph capture).
   config.captured_vs_eager_rel_l2 — the timed hipGraph step replayed once more against the same step launched eagerly from
                  the same state (must be 0); eps_checksum_per_rank: one checksum of that noise prediction per rank.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs), so that two builds can
+be compared output for output: inputs and weights are seeded, identical from run to run for the same arguments.
 """
 import argparse
 import importlib
@@ -79,7 +82,42 @@ def parse():
                          "shard: ONE volume depth-sharded over the GPUs with RCCL halo exchange (strong scaling, config 4); "
                          "train: forward+backward micro-steps of config 3 (frozen-VAE encode + U-Net fwd/bwd), "
                          "gradients all-reduced over RCCL when N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (e.g. bench_outputs; float32, at most "
+                         "64 MB in all; larger outputs are a fixed seeded sample): dp/shard -> z (the sampler state after the "
+                         "step) and eps (its noise prediction); train -> loss and unet_grads")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 60 * 10**6     # array data of one --dump-outputs, below 64 MB with room for the .npy headers
+
+
+def dump_outputs(out_dir, arrays, suffix=""):
+    """Write `arrays` (name -> tensor, or list of tensors concatenated flat) as out_dir/<name><suffix>.npy in float32.
+    When everything fits in DUMP_MAX_BYTES each array is written whole in its own shape; otherwise every array is cut to
+    its share of the budget (in proportion to its size) by a fixed seeded sample of flat indices, taken in sorted order
+    and written 1-D, so that two runs with the same arguments write the same elements."""
+    import numpy as np
+    arrays = {k: (v if isinstance(v, (list, tuple)) else [v]) for k, v in arrays.items()}
+    sizes = {k: sum(t.numel() for t in ts) for k, ts in arrays.items()}
+    cap = DUMP_MAX_BYTES // 4
+    total = sum(sizes.values())
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, ts in arrays.items():
+        if total <= cap:
+            parts = [t.detach().float().cpu() for t in ts]
+            out = parts[0] if len(parts) == 1 else torch.cat([p.flatten() for p in parts])
+        else:
+            share = cap * sizes[name] // total
+            parts = []
+            for t in ts:
+                flat = t.detach().flatten()
+                k = min(flat.numel(), max(1, share * flat.numel() // sizes[name]))
+                idx = torch.randint(0, flat.numel(), (k,), generator=gen).sort().values
+                parts.append(flat[idx.to(flat.device)].float().cpu())
+            out = torch.cat(parts)
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), out.numpy())
 
 
 def _cgroup_cpu_quota():
@@ -306,7 +344,12 @@ def bench_shard(args, pkg, S, E, model, ctx, dev, rank, world, dist):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     with ctx.scope():
-        finite = bool(torch.isfinite(prog.z_ncdhw()).all().item())
+        z_out = prog.z_ncdhw()
+        if args.dump_outputs:
+            eps_out = prog.eps_ncdhw()
+            torch.cuda.synchronize()
+            dump_outputs(args.dump_outputs, {"z": z_out, "eps": eps_out}, f"_rank{rank}" if world > 1 else "")
+        finite = bool(torch.isfinite(z_out).all().item())
     ncomm = sum(1 for m in prog.op_meta if m[2] == "comm")
     if rank == 0:
         print(json.dumps({
@@ -362,6 +405,9 @@ def bench_train(args, pkg, E, model, ctx, dev, rank, world, dist):
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(1), "unet_grads": [p.grad for p in params if p.grad is not None]},
+                     f"_rank{rank}" if world > 1 else "")
     finite = bool(torch.isfinite(loss).item()) and all(bool(torch.isfinite(p.grad).all().item()) for p in params[:8])
     prog = [pr for k, pr in model.unet.__dict__["_ctsi_programs"].items() if k[0] == "unet-train"][0]
     # The timed micro-steps do not step the optimizer (gradient accumulation, as in the reference's loop), so the weights
@@ -626,7 +672,12 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     with ctx.scope():
-        finite = bool(torch.isfinite(prog.z_ncdhw()).all().item())
+        z_out = prog.z_ncdhw()
+        if args.dump_outputs:
+            eps_out = prog.eps_ncdhw()
+            torch.cuda.synchronize()
+            dump_outputs(args.dump_outputs, {"z": z_out, "eps": eps_out}, f"_rank{rank}" if world > 1 else "")
+        finite = bool(torch.isfinite(z_out).all().item())
         # What the timed graph computes, checked beyond "finite": one more replay of the captured step against the same
         # step launched eagerly from the same state (z, conditioning, step counter): identical kernels in identical order, so
         # the noise predictions must agree to the last bit.

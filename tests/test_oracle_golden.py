@@ -13,20 +13,38 @@ from tests.helpers import (MID_UNET, TINY_UNET, formula_input, formula_noise, fo
 TOL = 2e-5
 
 
+# Buffers that pass through torch.sqrt / torch.log: the host CPU's vector math rounds these differently from one CPU
+# family to the next (1 ulp; the goldens' own values are not the IEEE-rounded ones either), and the posterior
+# coefficients carry that ulp through a product and a quotient.  They are held to these ulp counts of the golden;
+# every other buffer is plain IEEE arithmetic and is bit-exact on any host.
+SCHED_MAX_ULP = {"sqrt_alphas_cumprod": 1, "sqrt_one_minus_alphas_cumprod": 1, "posterior_log_variance_clipped": 1,
+                 "posterior_mean_coef1": 4, "posterior_mean_coef2": 4}
+
+
+def _assert_sched_buffer(v, ref, sched, name):
+    if name in SCHED_MAX_ULP:
+        np.testing.assert_array_max_ulp(v, ref, maxulp=SCHED_MAX_ULP[name], dtype=np.float32)
+    else:
+        assert np.array_equal(v, ref), (sched, name)
+
+
 def test_schedule_buffers_bit_exact(golden):
     for sched in ("cosine", "linear"):
         bufs = R.diffusion_buffers(sched, 1000)
         assert len(bufs) == 10
         for name, v in bufs.items():
-            ref = golden[f"sched.{sched}.{name}"]
-            assert np.array_equal(v.numpy(), ref), (sched, name)
+            assert v.dtype == torch.float32, (sched, name)
+            _assert_sched_buffer(v.numpy(), golden[f"sched.{sched}.{name}"], sched, name)
 
 
 def test_module_buffers_bit_exact(golden, pkg):
     for sched in ("cosine", "linear"):
         g = pkg.GaussianDiffusion(noise_schedule=sched, timesteps=1000)
+        oracle = R.diffusion_buffers(sched, 1000)
         for name, buf in g.named_buffers():
-            assert np.array_equal(buf.numpy(), golden[f"sched.{sched}.{name}"]), (sched, name)
+            # the package and the oracle run the same ops on the same host: bit-exact, whatever the host's math library
+            assert np.array_equal(buf.numpy(), oracle[name].numpy()), (sched, name, "vs oracle")
+            _assert_sched_buffer(buf.numpy(), golden[f"sched.{sched}.{name}"], sched, name)
     with pytest.raises(ValueError, match="Unknown noise schedule"):
         pkg.GaussianDiffusion(noise_schedule="sigmoid")
 
@@ -272,9 +290,16 @@ def test_training_forward_backward_vs_reference_autograd(golden, pkg):
         if tag == "nomask":
             stored = [k for k in golden.files if k.startswith("train.nomask.grad.")]
             assert len(stored) > 40
+            # A gradient that is zero in exact arithmetic (a conv bias straight into GroupNorm with one channel per group)
+            # is rounding noise on both sides, at a level set by the host's accumulation order: it is held to the same
+            # noise floor as the norms above, every other stored gradient to its golden.
+            floor = 1e-6 * ref.max()
             for k in stored:
                 g = grads[k[len("train.nomask.grad."):]]
-                assert rel_l2(g, torch.tensor(golden[k])) <= 2e-3 or float(g.abs().max()) < 1e-9, k
+                if np.linalg.norm(golden[k]) <= floor:
+                    assert float(g.double().norm()) <= floor, k
+                else:
+                    assert rel_l2(g, torch.tensor(golden[k])) <= 2e-3, k
 
 
 def test_metrics_vs_reference(golden):
