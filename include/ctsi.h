@@ -312,6 +312,24 @@ int ctsi_channel_sum(const void* x, long long rows, int c, int c_stride, float* 
 int ctsi_add_bf16(void* a, const void* b, long long count, void* stream);        /* a += b */
 int ctsi_f32_to_bf16(const float* src, void* dst, long long count, void* stream);
 
+/* ---- VAE training (SliceInterpolationVAE.forward's backward) ---- */
+/* Output gradient of the decoder's tanh head / encoder-output gradient at the latent seam.  g (and y): fp32 NCDHW
+ * (n, c, d, h, w); dst: bf16 NDHWC with c_stride channels per voxel (c_stride >= c, a multiple of 8, 16-byte aligned).
+ * mode 0: dst = bf16(scale * g * (1 - y^2)), channels c .. c_stride-1 zero.  mode 1: dst += scale * g (y unused, padding
+ * channels untouched). */
+int ctsi_vae_head_grad(const float* g, const float* y, int n, int c, int d, int h, int w, float scale, int mode, void* dst,
+                       int c_stride, void* stream);
+/* Weight gradient of a 3x3x3 stride-1 padding-1 Conv3d with ONE input channel (head = 0: wide = output gradient (c channels),
+ * thin = layer input) or ONE output channel (head = 1: wide = layer input, thin = output gradient).  bf16 NDHWC tensors of
+ * shape (n, d, h, w); the thin tensor's channel 0 is read at stride thin_stride.  dw[c * 27 + t] = scale * (the weight
+ * gradient), WRITTEN; deterministic (per-block partials in `workspace`, summed in a fixed order).  Supported when
+ * ctsi_thin_wgrad_supported(c, w, kd, kh, kw); the call fails without launching otherwise. */
+size_t ctsi_thin_wgrad_workspace_bytes(int n, int c, int d, int h, int w);
+int ctsi_thin_wgrad_supported(int c, int w, int kd, int kh, int kw);
+int ctsi_thin_wgrad(const void* wide, int c, int c_stride, const void* thin, int thin_stride, int head, int n, int d, int h,
+                    int w, int kd, int kh, int kw, void* workspace, size_t workspace_bytes, float* dw, float scale,
+                    void* stream);
+
 /* q_sample (models/diffusion.py:81-106): z_t = sqrt_alphas_cumprod[t_b]*z0 + sqrt_one_minus_alphas_cumprod[t_b]*noise,
  * fp32 NCDHW in, bf16 NDHWC channel slice out (the U-Net input tensor [z_t | cond]). */
 int ctsi_q_sample(const float* z0, const float* noise, const float* sqrt_ac, const float* sqrt_1mac, const int* t,

@@ -123,6 +123,10 @@ SIGNATURES = {
     "ctsi_channel_sum": (_i, [_vp, _ll, _i, _i, _vp, _vp, _f, _vp], True),
     "ctsi_add_bf16": (_i, [_vp, _vp, _ll, _vp], True),
     "ctsi_f32_to_bf16": (_i, [_vp, _vp, _ll, _vp], True),
+    "ctsi_vae_head_grad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp], True),
+    "ctsi_thin_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i], False),
+    "ctsi_thin_wgrad_supported": (_i, [_i, _i, _i, _i, _i], False),
+    "ctsi_thin_wgrad": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _f, _vp], True),
     "ctsi_q_sample": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp], True),
     "ctsi_mse_loss_workspace_doubles": (_sz, [_i], False),
     "ctsi_mse_loss_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp], True),

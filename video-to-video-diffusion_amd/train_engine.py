@@ -30,7 +30,242 @@ from .engine import Act, Ctx, Program, _ptr
 from .lib import CtsiError, WgradDesc
 
 
-class UNetTrainProgram(Program):
+class TrainProgram(Program):
+    """Shared machinery of the training programs (U-Net here, VAE in vae_train_engine.py): the gradient arena, the conv and
+    GroupNorm forward wrappers that record their backward on a tape, and the backward launches themselves."""
+    tbias = None       # time-bias rows of the U-Net (programs without a time embedding leave these unset)
+    total_out = 0
+
+    def _ws_ptr(self, key):
+        return C.c_void_p(self._ws[key].data_ptr())
+
+    # ---- helpers ---------------------------------------------------------------------------------------------
+    def grad_alloc(self, shape) -> torch.Tensor:
+        """A zeroed fp32 gradient buffer: a 256-byte-aligned piece of the arena (a separate allocation once the arena is full)."""
+        numel = 1
+        for v in shape:
+            numel *= int(v)
+        if self._garena_used + numel > self._garena.numel():
+            return self.persistent(tuple(shape), torch.float32, zero=True)
+        g = self._garena[self._garena_used:self._garena_used + numel].view(tuple(shape))
+        self._garena_used += (numel + 63) // 64 * 64
+        return g
+
+    def grad_buf(self, p: torch.Tensor, rows_pad: Optional[int] = None) -> torch.Tensor:
+        g = self.grads.get(id(p))
+        if g is None:
+            shape = list(p.shape)
+            if rows_pad is not None and rows_pad > shape[0]:
+                shape[0] = rows_pad
+            g = self.grad_alloc(shape)
+            self.grads[id(p)] = g
+        return g
+
+    def act_like(self, a: Act) -> Act:
+        return self.act(a.n, a.c, a.d, a.h, a.w, halo=0)
+
+    def into_grad(self, a: Act, produce: Callable[[Act], None]):
+        """Run `produce(dst)` so that it writes a gradient contribution of `a`; the first contribution lands in
+        a.grad directly, later ones go through a temporary and ctsi_add_bf16."""
+        if a.grad is None:
+            a.grad = self.act_like(a)
+            produce(a.grad)
+            return
+        tmp = self.act_like(a)
+        produce(tmp)
+        lib, sptr = self.lib, self.ctx.sptr
+        gp, tp, cnt = a.grad.ip, tmp.ip, a.n * a.vox * a.c
+
+        def run():
+            lib.add_bf16(gp, tp, cnt, sptr)
+
+        self._emit(run, "grad.add")
+        self.release(tmp)
+
+    # ---- conv ----------------------------------------------------------------------------------------------------
+    def t_conv(self, name, m, x1: Act, x2: Optional[Act], *, transposed=False, k=(3, 3, 3), s=(1, 1), want_stats=False,
+               need_dx=True, f32_out=None, f32_strides=None, gy: Optional[Act] = None, ret_stats=False,
+               bias_from_gn=False):
+        p = (1, 1, 1) if k != (1, 1, 1) else (0, 0, 0)
+        cout = m.out_channels
+        out, st = self.conv(name, lambda: m.weight, lambda: m.bias, x1, x2, transposed=transposed, k=k, s=s, p=p,
+                            cout=cout, want_stats=want_stats, f32_out=f32_out, f32_strides=f32_strides)
+
+        def bwd():
+            g = gy if gy is not None else out.grad
+            if g is None:
+                raise CtsiError(f"internal: no gradient reached the output of {name}")
+            self._conv_bwd(name, m.weight, None if bias_from_gn else m.bias, x1, x2, g, transposed, k, s, p, cout,
+                           need_dx)
+            if gy is None:
+                self.release(out.grad)
+                out.grad = None
+
+        self.tape.append(bwd)
+        return (out, st) if ret_stats else out
+
+    def _conv_bwd(self, name, wparam, bparam, x1, x2, g: Act, transposed, k, s, p, cout, need_dx,
+                  w_rows=None, b_scale=1.0, gw: Optional[torch.Tensor] = None, gb: Optional[torch.Tensor] = None,
+                  gw_off=0, gb_off=0, w_src: Optional[Callable[[], torch.Tensor]] = None, defer_wb: bool = False,
+                  w_scale: float = 1.0, gw_cin: Optional[int] = None, emit_wgrad: bool = True):
+        """Emit bias / weight / data gradient launches of one conv whose output gradient is `g`.
+        gw/gb (+ element offsets) override the destination (used for the V slice of attention's qkv);
+        w_src overrides the weight the data gradient uses (same slice).  w_scale multiplies the weight gradient (a factor
+        the forward folded into the weight image); gw_cin: input channels per row of a Conv3d weight-gradient buffer padded
+        beyond the weight's own (a thin input whose padded channels the wgrad kernel also writes); emit_wgrad False: the
+        caller emits the weight gradient itself."""
+        lib, sptr, prog = self.lib, self.ctx.sptr, self
+        T = k[0] * k[1] * k[2]
+        cin = x1.c + (0 if x2 is None else x2.c)
+        cw_out = wparam.shape[1] if transposed else wparam.shape[0]
+        if gw is None:
+            pad = g.c if (not transposed and g.c > wparam.shape[0]) else None
+            gw = self.grad_buf(wparam, rows_pad=pad)
+        if gb is None and bparam is not None:
+            gb = self.grad_buf(bparam, rows_pad=g.c if g.c > bparam.shape[0] else None)
+        rows = g.n * g.vox
+        if defer_wb:
+            # a small 1x1x1 layer (rows of a depth-summed tensor): weight and bias gradient join the batched launch at the end of
+            # the backward pass (ctsi_linear_wgrad_multi); x1 and g must stay alive until then
+            if transposed or T != 1 or x2 is not None:
+                raise CtsiError("internal: only plain pointwise layers can defer their weight gradient")
+            self._deferred_lin.append((x1, g, gw, gw_off, gb, gb_off, float(b_scale), rows, x1.c, g.c, wparam.shape[1]))
+        # bias: channel sums of the output gradient
+        if gb is not None and not defer_wb:
+            self._need["chsum"] = max(self._need["chsum"], 4 * lib.channel_sum_workspace_floats(rows, g.c))
+            gp, gbp, gc = g.ip, C.c_void_p(gb.data_ptr() + 4 * gb_off), g.c
+
+            def run_b():
+                lib.channel_sum(gp, rows, gc, gc, prog._ws_ptr("chsum"), gbp, b_scale, sptr)
+
+            self._emit(run_b, name + ".bgrad")
+        # weight
+        srcs = [(x1, 0)] + ([(x2, x1.c)] if x2 is not None else [])
+        for xa, coff in ([] if (defer_wb or not emit_wgrad) else srcs):
+            if transposed:   # weight (cin, cout, T): R = layer input, G = output gradient
+                r_act, g_act = xa, g
+                sr, sg = cw_out * T, T
+                off = gw_off + coff * cw_out * T
+            else:            # weight (cout, cin, T): R = output gradient, G = layer input
+                r_act, g_act = g, xa
+                sr, sg = (gw_cin or wparam.shape[1]) * T, T
+                off = gw_off + coff * T
+            desc = WgradDesc(k[0], k[1], k[2], s[0], s[1], p[0], p[1], p[2], r_act.n, r_act.d, r_act.h, r_act.w,
+                             g_act.d, g_act.h, g_act.w, r_act.c, r_act.c, g_act.c, g_act.c)
+            self.keep.append(desc)
+            self._need["wgrad"] = max(self._need["wgrad"], lib.wgrad_workspace_bytes(C.byref(desc)))
+            fl = lib.wgrad_flops(C.byref(desc))
+            self.flops += fl
+            rp, gp2, dwp = r_act.ip, g_act.ip, C.c_void_p(gw.data_ptr() + 4 * off)
+
+            def run_w(desc=desc, rp=rp, gp2=gp2, dwp=dwp, sr=sr, sg=sg):
+                lib.wgrad(C.byref(desc), rp, gp2, prog._ws_ptr("wgrad"), prog._ws["wgrad"].numel(), dwp, sr, sg, 1, w_scale, sptr)
+
+            self._emit(run_w, name + ".wgrad", fl, "conv_wgrad")
+        # data
+        if not need_dx:
+            return
+        if transposed:      # ConvTranspose3d layer: dx = strided Conv3d of g with the same weight tensor
+            self.into_grad(x1, lambda dst: self.conv(name + ".dgrad", lambda: wparam, None, g, None, k=k, s=s, p=p,
+                                                     cout=x1.c, out=dst))
+        elif s != (1, 1):   # strided Conv3d layer: dx = ConvTranspose3d of g with the same weight tensor
+            self.into_grad(x1, lambda dst: self.conv(name + ".dgrad", lambda: wparam, None, g, None, transposed=True,
+                                                     k=k, s=s, p=p, cout=x1.c, out=dst))
+        else:               # stride-1 'same' conv: flipped, transposed weights, one launch per concatenated source
+            co_w, ci_w = wparam.shape[0], wparam.shape[1]
+            if w_src is not None:
+                co_w = cout
+            for xa, coff in srcs:
+                def wfn(coff=coff, cnt=xa.c):
+                    src = (w_src() if w_src is not None else wparam).detach().contiguous()
+                    outw = torch.empty((cnt, co_w) + tuple(wparam.shape[2:]), dtype=torch.float32,
+                                       device=self.ctx.device)
+                    lib.weight_dgrad_layout(_ptr(src), _ptr(outw), co_w, ci_w, T, coff, cnt, sptr)
+                    src.record_stream(self.ctx.stream)
+                    return outw
+
+                # (fast_repack: the same re-layout from a pointer table, into a buffer the program keeps)
+                wfn.fast_layout = ((w_src if w_src is not None else (lambda: wparam)), co_w, ci_w, T, coff, xa.c)
+
+                self.into_grad(xa, lambda dst, wfn=wfn, cnt=xa.c: self.conv(
+                    name + ".dgrad", wfn, None, g, None, k=k, s=(1, 1), p=p, cout=cnt, out=dst,
+                    cin_w=(co_w if co_w != g.c else None)))
+
+    # ---- GroupNorm chain ---------------------------------------------------------------------------------------------
+    def t_gn(self, x: Act, slot: int, gn: nn.GroupNorm, *, silu_pre: bool, tb_off: Optional[int] = None,
+             residual: Optional[Act] = None, silu_post: bool = False, conv_bias: Optional[torch.Tensor] = None) -> Act:
+        """`conv_bias`: bias parameter of the convolution that produced x; its gradient (sum of dx) then comes out of
+        the GroupNorm backward's statistics and that conv's backward skips its own channel-sum pass."""
+        out = self.gn_apply(x, slot, gn, silu_pre=silu_pre, tbias=self.tbias if tb_off is not None else None,
+                            tbias_off=tb_off or 0, tbias_stride=self.total_out, residual=residual, silu_post=silu_post)
+        lib, sptr, prog = self.lib, self.ctx.sptr, self
+        gamma = self.dev_f32(lambda: gn.weight)
+        beta = self.dev_f32(lambda: gn.bias)
+
+        def bwd():
+            gy = out.grad
+            if gy is None:
+                raise CtsiError("internal: no gradient reached a GroupNorm output")
+            self._gn_bwd(x, gy, False, slot, gn, gamma, beta, silu_pre, tb_off, residual, silu_post, None,
+                         dxsum=None if conv_bias is None else self.grad_buf(conv_bias))
+            self.release(gy)
+            out.grad = None
+
+        self.tape.append(bwd)
+        return out
+
+    def _gn_bwd(self, x: Act, gy: Act, bcast: bool, slot: int, gn, gamma, beta, silu_pre, tb_off, residual, silu_post,
+                add: Optional[Act], dxsum: Optional[torch.Tensor] = None):
+        lib, sptr, prog = self.lib, self.ctx.sptr, self
+        n, c, d, h, w = x.n, x.c, x.d, x.h, x.w
+        groups, eps = gn.num_groups, float(gn.eps)
+        self._need["gn"] = max(self._need["gn"], 4 * lib.gn_bwd_workspace_floats(n, c, d, h, w, groups))
+        if x.grad is not None:
+            raise CtsiError("internal: a normalised tensor has a second consumer")
+        x.grad = self.act_like(x)
+        # g_buf (gradient of the GroupNorm output) is the residual's gradient when no SiLU sits in between
+        tmp = None
+        if residual is not None and not silu_pre and residual.grad is None:
+            residual.grad = self.act_like(residual)
+            gbuf = residual.grad
+            add_to_res = False
+        elif residual is None and not silu_post:
+            gbuf = None         # nobody but pass 3 needs the GroupNorm output's gradient: it re-derives it from dy (no buffer, no write)
+            add_to_res = False
+        else:
+            tmp = self.act_like(x)
+            gbuf = tmp
+            add_to_res = residual is not None
+        if residual is not None and silu_pre:
+            raise CtsiError("internal: residual after a pre-SiLU is not a combination the U-Net uses")
+        dgam, dbet = self.grad_buf(gn.weight), self.grad_buf(gn.bias)
+        xp, gyp, gp, bp = x.ip, gy.ip, _ptr(gamma), _ptr(beta)
+        rp = C.c_void_p(0) if residual is None else residual.ip
+        ap = C.c_void_p(0) if add is None else add.ip
+        gbp, dxp, dgp, dbp = (C.c_void_p(0) if gbuf is None else gbuf.ip), x.grad.ip, _ptr(dgam), _ptr(dbet)
+        dtp = C.c_void_p(0 if tb_off is None else self.d_tbias.data_ptr() + 4 * tb_off)
+        tstride = self.total_out
+        dxsp = _ptr(dxsum)
+
+        def run():
+            lib.gn_bwd(xp, gyp, int(bcast), C.c_void_p(prog._gn_sums.data_ptr() + slot * 8), gp, bp, n, c, d, h, w,
+                       groups, eps, int(silu_pre), rp, int(silu_post), ap, gbp, dxp, prog._ws_ptr("gn"), dgp, dbp, dtp,
+                       tstride, dxsp, sptr)
+
+        self._emit(run, "gn.bwd")
+        if add_to_res:
+            rgp, cnt = residual.grad.ip, n * x.vox * c
+
+            def run_add():
+                lib.add_bf16(rgp, gbp, cnt, sptr)
+
+            self._emit(run_add, "grad.add")
+        if tmp is not None:
+            self.release(tmp)
+
+
+
+class UNetTrainProgram(TrainProgram):
     def __init__(self, ctx: Ctx, unet, n: int, d: int, h: int, w: int):
         super().__init__(ctx)
         self.weight_cache = False    # weights change every optimizer step: private images, repacked in place
@@ -195,52 +430,6 @@ class UNetTrainProgram(Program):
         for (xa, ga, *_rest) in self._deferred_lin:
             self.release(ga)
 
-    # ---- helpers ---------------------------------------------------------------------------------------------
-    def _ws_ptr(self, key):
-        return C.c_void_p(self._ws[key].data_ptr())
-
-    def grad_alloc(self, shape) -> torch.Tensor:
-        """A zeroed fp32 gradient buffer: a 256-byte-aligned piece of the arena (a separate allocation once the arena is full)."""
-        numel = 1
-        for v in shape:
-            numel *= int(v)
-        if self._garena_used + numel > self._garena.numel():
-            return self.persistent(tuple(shape), torch.float32, zero=True)
-        g = self._garena[self._garena_used:self._garena_used + numel].view(tuple(shape))
-        self._garena_used += (numel + 63) // 64 * 64
-        return g
-
-    def grad_buf(self, p: torch.Tensor, rows_pad: Optional[int] = None) -> torch.Tensor:
-        g = self.grads.get(id(p))
-        if g is None:
-            shape = list(p.shape)
-            if rows_pad is not None and rows_pad > shape[0]:
-                shape[0] = rows_pad
-            g = self.grad_alloc(shape)
-            self.grads[id(p)] = g
-        return g
-
-    def act_like(self, a: Act) -> Act:
-        return self.act(a.n, a.c, a.d, a.h, a.w, halo=0)
-
-    def into_grad(self, a: Act, produce: Callable[[Act], None]):
-        """Run `produce(dst)` so that it writes a gradient contribution of `a`; the first contribution lands in
-        a.grad directly, later ones go through a temporary and ctsi_add_bf16."""
-        if a.grad is None:
-            a.grad = self.act_like(a)
-            produce(a.grad)
-            return
-        tmp = self.act_like(a)
-        produce(tmp)
-        lib, sptr = self.lib, self.ctx.sptr
-        gp, tp, cnt = a.grad.ip, tmp.ip, a.n * a.vox * a.c
-
-        def run():
-            lib.add_bf16(gp, tp, cnt, sptr)
-
-        self._emit(run, "grad.add")
-        self.release(tmp)
-
     def _layer(self, layer, x: Act, skip: Optional[Act]) -> Act:
         kind = type(layer).__name__
         if kind == "ResBlock3D":
@@ -250,183 +439,6 @@ class UNetTrainProgram(Program):
         else:
             raise CtsiError(f"unsupported U-Net layer {kind}")
         return y
-
-    # ---- conv ----------------------------------------------------------------------------------------------------
-    def t_conv(self, name, m, x1: Act, x2: Optional[Act], *, transposed=False, k=(3, 3, 3), s=(1, 1), want_stats=False,
-               need_dx=True, f32_out=None, f32_strides=None, gy: Optional[Act] = None, ret_stats=False,
-               bias_from_gn=False):
-        p = (1, 1, 1) if k != (1, 1, 1) else (0, 0, 0)
-        cout = m.out_channels
-        out, st = self.conv(name, lambda: m.weight, lambda: m.bias, x1, x2, transposed=transposed, k=k, s=s, p=p,
-                            cout=cout, want_stats=want_stats, f32_out=f32_out, f32_strides=f32_strides)
-
-        def bwd():
-            g = gy if gy is not None else out.grad
-            if g is None:
-                raise CtsiError(f"internal: no gradient reached the output of {name}")
-            self._conv_bwd(name, m.weight, None if bias_from_gn else m.bias, x1, x2, g, transposed, k, s, p, cout,
-                           need_dx)
-            if gy is None:
-                self.release(out.grad)
-                out.grad = None
-
-        self.tape.append(bwd)
-        return (out, st) if ret_stats else out
-
-    def _conv_bwd(self, name, wparam, bparam, x1, x2, g: Act, transposed, k, s, p, cout, need_dx,
-                  w_rows=None, b_scale=1.0, gw: Optional[torch.Tensor] = None, gb: Optional[torch.Tensor] = None,
-                  gw_off=0, gb_off=0, w_src: Optional[Callable[[], torch.Tensor]] = None, defer_wb: bool = False):
-        """Emit bias / weight / data gradient launches of one conv whose output gradient is `g`.
-        gw/gb (+ element offsets) override the destination (used for the V slice of attention's qkv);
-        w_src overrides the weight the data gradient uses (same slice)."""
-        lib, sptr, prog = self.lib, self.ctx.sptr, self
-        T = k[0] * k[1] * k[2]
-        cin = x1.c + (0 if x2 is None else x2.c)
-        cw_out = wparam.shape[1] if transposed else wparam.shape[0]
-        if gw is None:
-            pad = g.c if (not transposed and g.c > wparam.shape[0]) else None
-            gw = self.grad_buf(wparam, rows_pad=pad)
-        if gb is None and bparam is not None:
-            gb = self.grad_buf(bparam, rows_pad=g.c if g.c > bparam.shape[0] else None)
-        rows = g.n * g.vox
-        if defer_wb:
-            # a small 1x1x1 layer (rows of a depth-summed tensor): weight and bias gradient join the batched launch at the end of
-            # the backward pass (ctsi_linear_wgrad_multi); x1 and g must stay alive until then
-            if transposed or T != 1 or x2 is not None:
-                raise CtsiError("internal: only plain pointwise layers can defer their weight gradient")
-            self._deferred_lin.append((x1, g, gw, gw_off, gb, gb_off, float(b_scale), rows, x1.c, g.c, wparam.shape[1]))
-        # bias: channel sums of the output gradient
-        if gb is not None and not defer_wb:
-            self._need["chsum"] = max(self._need["chsum"], 4 * lib.channel_sum_workspace_floats(rows, g.c))
-            gp, gbp, gc = g.ip, C.c_void_p(gb.data_ptr() + 4 * gb_off), g.c
-
-            def run_b():
-                lib.channel_sum(gp, rows, gc, gc, prog._ws_ptr("chsum"), gbp, b_scale, sptr)
-
-            self._emit(run_b, name + ".bgrad")
-        # weight
-        srcs = [(x1, 0)] + ([(x2, x1.c)] if x2 is not None else [])
-        for xa, coff in ([] if defer_wb else srcs):
-            if transposed:   # weight (cin, cout, T): R = layer input, G = output gradient
-                r_act, g_act = xa, g
-                sr, sg = cw_out * T, T
-                off = gw_off + coff * cw_out * T
-            else:            # weight (cout, cin, T): R = output gradient, G = layer input
-                r_act, g_act = g, xa
-                sr, sg = wparam.shape[1] * T, T
-                off = gw_off + coff * T
-            desc = WgradDesc(k[0], k[1], k[2], s[0], s[1], p[0], p[1], p[2], r_act.n, r_act.d, r_act.h, r_act.w,
-                             g_act.d, g_act.h, g_act.w, r_act.c, r_act.c, g_act.c, g_act.c)
-            self.keep.append(desc)
-            self._need["wgrad"] = max(self._need["wgrad"], lib.wgrad_workspace_bytes(C.byref(desc)))
-            fl = lib.wgrad_flops(C.byref(desc))
-            self.flops += fl
-            rp, gp2, dwp = r_act.ip, g_act.ip, C.c_void_p(gw.data_ptr() + 4 * off)
-
-            def run_w(desc=desc, rp=rp, gp2=gp2, dwp=dwp, sr=sr, sg=sg):
-                lib.wgrad(C.byref(desc), rp, gp2, prog._ws_ptr("wgrad"), prog._ws["wgrad"].numel(), dwp, sr, sg, 1, 1.0, sptr)
-
-            self._emit(run_w, name + ".wgrad", fl, "conv_wgrad")
-        # data
-        if not need_dx:
-            return
-        if transposed:      # ConvTranspose3d layer: dx = strided Conv3d of g with the same weight tensor
-            self.into_grad(x1, lambda dst: self.conv(name + ".dgrad", lambda: wparam, None, g, None, k=k, s=s, p=p,
-                                                     cout=x1.c, out=dst))
-        elif s != (1, 1):   # strided Conv3d layer: dx = ConvTranspose3d of g with the same weight tensor
-            self.into_grad(x1, lambda dst: self.conv(name + ".dgrad", lambda: wparam, None, g, None, transposed=True,
-                                                     k=k, s=s, p=p, cout=x1.c, out=dst))
-        else:               # stride-1 'same' conv: flipped, transposed weights, one launch per concatenated source
-            co_w, ci_w = wparam.shape[0], wparam.shape[1]
-            if w_src is not None:
-                co_w = cout
-            for xa, coff in srcs:
-                def wfn(coff=coff, cnt=xa.c):
-                    src = (w_src() if w_src is not None else wparam).detach().contiguous()
-                    outw = torch.empty((cnt, co_w) + tuple(wparam.shape[2:]), dtype=torch.float32,
-                                       device=self.ctx.device)
-                    lib.weight_dgrad_layout(_ptr(src), _ptr(outw), co_w, ci_w, T, coff, cnt, sptr)
-                    src.record_stream(self.ctx.stream)
-                    return outw
-
-                # (fast_repack: the same re-layout from a pointer table, into a buffer the program keeps)
-                wfn.fast_layout = ((w_src if w_src is not None else (lambda: wparam)), co_w, ci_w, T, coff, xa.c)
-
-                self.into_grad(xa, lambda dst, wfn=wfn, cnt=xa.c: self.conv(
-                    name + ".dgrad", wfn, None, g, None, k=k, s=(1, 1), p=p, cout=cnt, out=dst,
-                    cin_w=(co_w if co_w != g.c else None)))
-
-    # ---- GroupNorm chain ---------------------------------------------------------------------------------------------
-    def t_gn(self, x: Act, slot: int, gn: nn.GroupNorm, *, silu_pre: bool, tb_off: Optional[int] = None,
-             residual: Optional[Act] = None, silu_post: bool = False, conv_bias: Optional[torch.Tensor] = None) -> Act:
-        """`conv_bias`: bias parameter of the convolution that produced x; its gradient (sum of dx) then comes out of
-        the GroupNorm backward's statistics and that conv's backward skips its own channel-sum pass."""
-        out = self.gn_apply(x, slot, gn, silu_pre=silu_pre, tbias=self.tbias if tb_off is not None else None,
-                            tbias_off=tb_off or 0, tbias_stride=self.total_out, residual=residual, silu_post=silu_post)
-        lib, sptr, prog = self.lib, self.ctx.sptr, self
-        gamma = self.dev_f32(lambda: gn.weight)
-        beta = self.dev_f32(lambda: gn.bias)
-
-        def bwd():
-            gy = out.grad
-            if gy is None:
-                raise CtsiError("internal: no gradient reached a GroupNorm output")
-            self._gn_bwd(x, gy, False, slot, gn, gamma, beta, silu_pre, tb_off, residual, silu_post, None,
-                         dxsum=None if conv_bias is None else self.grad_buf(conv_bias))
-            self.release(gy)
-            out.grad = None
-
-        self.tape.append(bwd)
-        return out
-
-    def _gn_bwd(self, x: Act, gy: Act, bcast: bool, slot: int, gn, gamma, beta, silu_pre, tb_off, residual, silu_post,
-                add: Optional[Act], dxsum: Optional[torch.Tensor] = None):
-        lib, sptr, prog = self.lib, self.ctx.sptr, self
-        n, c, d, h, w = x.n, x.c, x.d, x.h, x.w
-        groups, eps = gn.num_groups, float(gn.eps)
-        self._need["gn"] = max(self._need["gn"], 4 * lib.gn_bwd_workspace_floats(n, c, d, h, w, groups))
-        if x.grad is not None:
-            raise CtsiError("internal: a normalised tensor has a second consumer")
-        x.grad = self.act_like(x)
-        # g_buf (gradient of the GroupNorm output) is the residual's gradient when no SiLU sits in between
-        tmp = None
-        if residual is not None and not silu_pre and residual.grad is None:
-            residual.grad = self.act_like(residual)
-            gbuf = residual.grad
-            add_to_res = False
-        elif residual is None and not silu_post:
-            gbuf = None         # nobody but pass 3 needs the GroupNorm output's gradient: it re-derives it from dy (no buffer, no write)
-            add_to_res = False
-        else:
-            tmp = self.act_like(x)
-            gbuf = tmp
-            add_to_res = residual is not None
-        if residual is not None and silu_pre:
-            raise CtsiError("internal: residual after a pre-SiLU is not a combination the U-Net uses")
-        dgam, dbet = self.grad_buf(gn.weight), self.grad_buf(gn.bias)
-        xp, gyp, gp, bp = x.ip, gy.ip, _ptr(gamma), _ptr(beta)
-        rp = C.c_void_p(0) if residual is None else residual.ip
-        ap = C.c_void_p(0) if add is None else add.ip
-        gbp, dxp, dgp, dbp = (C.c_void_p(0) if gbuf is None else gbuf.ip), x.grad.ip, _ptr(dgam), _ptr(dbet)
-        dtp = C.c_void_p(0 if tb_off is None else self.d_tbias.data_ptr() + 4 * tb_off)
-        tstride = self.total_out
-        dxsp = _ptr(dxsum)
-
-        def run():
-            lib.gn_bwd(xp, gyp, int(bcast), C.c_void_p(prog._gn_sums.data_ptr() + slot * 8), gp, bp, n, c, d, h, w,
-                       groups, eps, int(silu_pre), rp, int(silu_post), ap, gbp, dxp, prog._ws_ptr("gn"), dgp, dbp, dtp,
-                       tstride, dxsp, sptr)
-
-        self._emit(run, "gn.bwd")
-        if add_to_res:
-            rgp, cnt = residual.grad.ip, n * x.vox * c
-
-            def run_add():
-                lib.add_bf16(rgp, gbp, cnt, sptr)
-
-            self._emit(run_add, "grad.add")
-        if tmp is not None:
-            self.release(tmp)
 
     # ---- ResBlock3D (models/unet3d.py:116-133) ------------------------------------------------------------------------
     def t_resblock(self, m, x: Act, skip: Optional[Act]) -> Act:

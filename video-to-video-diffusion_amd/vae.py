@@ -150,8 +150,24 @@ class SliceInterpolationVAE(nn.Module):
         return torch.chunk(z, 2, dim=1)
 
     def forward(self, x):
+        """(recon, z) = (decode(encode(x)), encode(x)).  In grad mode with at least one trainable parameter both outputs carry
+        an autograd node whose backward (on the HIP engine: vae_train_engine.VAETrainProgram) fills .grad of every VAE
+        parameter; the values are bit for bit those of encode / decode.  `x` itself gets no gradient.  Training needs H and W
+        that are multiples of 4 and a latent_dim that is a multiple of 8 (CtsiError otherwise)."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return self._train_forward(x)
         z = self.encode(x)
         return self.decode(z), z
+
+    def _train_forward(self, x):
+        from .vae_train_engine import VAETrainProgram, check_trainable_geometry, vae_train_step
+        check_trainable_geometry(self, x)
+        n, _, d, h, w = x.shape
+        ctx = Ctx.get(x.device)
+        with ctx.scope():
+            key = ("train", ctx.device.index, n, d, h, w, float(self.scaling_factor))
+            prog = cached_program(self, key, lambda: VAETrainProgram(ctx, self, n, d, h, w))
+        return vae_train_step(prog, x)
 
     def get_latent_shape(self, volume_shape):
         b, _, t, h, w = volume_shape
