@@ -394,6 +394,55 @@ int ctsi_copy_scale_multi(const void* segs, const void* pieces, int npieces, voi
  * SYNCHRONOUS 8-byte device-to-host read: the samplers call it once per sample(), where they read the non-finite table. */
 int ctsi_device_error_status(unsigned int* count, unsigned int* detail, int reset);
 
+/* fp32 inference mode (csrc/conv_f32.hip, csrc/f32_ops.hip) ---------------------------------------------------------------- *
+ * The reference's generate() runs the VAE and the sampler in fp32 (models/model.py:254-259).  In this mode activations are
+ * fp32 NDHWC and every convolution multiplies fp32 operands on the exact f32-input MFMA (v_mfma_f32_32x32x2_f32: a k-ordered
+ * fmaf chain) with fp32 accumulation.  GroupNorm statistics still go through ctsi_gn_finalize (fp64); the time embedding,
+ * the trilinear depth upsample and the fp32 layout converters above are shared with the bf16 path.  Depth sharding
+ * (halo_d = 1) is not supported.
+ *
+ * Convolution: the ctsi_conv_desc of the bf16 path, any channel counts (c1 + c2 >= 1, cout >= 1), geometries 3x3x3 p1,
+ * 1x1x1 p0, Conv3d (3,4,4) s(1,2,2) p1 and ConvTranspose3d (3,4,4) s(1,2,2) p1 (evaluated as 4 output parity classes of
+ * 3x2x2 taps).  No plan object: the descriptor is the plan.
+ *   _supported   1 when the fp32 kernel covers the descriptor, 0 otherwise (the reason in ctsi_last_error)
+ *   _weight_bytes  bytes of the packed fp32 image (0 when unsupported)
+ *   _geometry    output dims, row tiles per (sample, class), classes (4 for the transposed form), padded cout: a colsum
+ *                slab is [2][nclass * n * tiles_per_sample][cout_pad] floats, as ctsi_gn_finalize reads it (nclass > 1:
+ *                tiles of class k of sample i start at (k * n + i) * tiles_per_sample)
+ *   _pack_weights  reference weights (fp32, PyTorch layout) -> the kernel's fp32 image [class][tap * cpad + ci][cout_pad]
+ *   _fwd         y = act(conv(cat(x1, x2)) + bias + residual); `out` as for ctsi_conv_fwd with mode 0 = fp32 NDHWC (channel
+ *                stride cout_stride, offset c_off) and mode 1 = fp32 with element strides; act 0 / 1 (tanh); colsum
+ *                optional; gn_x must be NULL and workspace is ignored.  `residual` (may be NULL) is fp32 and addressed exactly
+ *                like y.  Fixed summation order, no atomics: a relaunch is bit-identical.                                   */
+int ctsi_conv_f32_supported(const ctsi_conv_desc* desc);
+size_t ctsi_conv_f32_weight_bytes(const ctsi_conv_desc* desc);
+double ctsi_conv_f32_flops(const ctsi_conv_desc* desc);
+int ctsi_conv_f32_geometry(const ctsi_conv_desc* desc, int* d_out, int* h_out, int* w_out, int* tiles_per_sample,
+                           int* nclass, int* cout_pad);
+int ctsi_conv_f32_pack_weights(const ctsi_conv_desc* desc, const float* w_f32, void* packed, void* stream);
+int ctsi_conv_f32_fwd(const ctsi_conv_desc* desc, const float* x1, const float* x2, const void* packed_w, const float* bias,
+                      const float* residual, const ctsi_conv_out* out, void* stream);
+/* GroupNorm on fp32 NDHWC: column sums in 512-voxel tiles (ctsi_gn_colsum_f32_tiles per sample) and the apply pass with every
+ * option of ctsi_gn_apply (SiLU before, time bias row (step_ptr ? *step_ptr : 0) * n + i, fp32 residual, SiLU after). */
+int ctsi_gn_colsum_f32_tiles(int d, int h, int w);
+int ctsi_gn_colsum_f32(const float* x, float* colsum, int n, int c, int d, int h, int w, int* tiles_per_sample, void* stream);
+int ctsi_gn_apply_f32(const float* x, float* y, const double* sums, const float* gamma, const float* beta, int n, int c,
+                      int d, int h, int w, int d_stat, int groups, float eps, int silu_pre, const float* tbias,
+                      int tbias_stride, const int* step_ptr, const float* residual, int silu_post, void* stream);
+/* TemporalAttention fast mode on fp32: depth sums + GroupNorm column sums (tiles of 64 positions per sample), the normalised
+ * depth sum (fp32 [n][h*w][c]; the folded (proj_out . W_v) product is then one fp32 1x1x1 conv), and y = x + p broadcast
+ * over depth.  Exact mode has no fp32 form (it is the same mathematics). */
+int ctsi_attn_depthsum_f32_tiles(int h, int w);
+int ctsi_attn_depthsum_f32(const float* x, float* depthsum, float* colsum, int n, int c, int d, int h, int w, void* stream);
+int ctsi_attn_normsum_f32(const float* depthsum, const double* sums, const float* gamma, const float* beta, float* out,
+                          int n, int c, int d, int h, int w, int groups, float eps, void* stream);
+int ctsi_attn_broadcast_add_f32(const float* x, const float* p, float* y, int n, int c, int d, int h, int w, void* stream);
+/* ctsi_ddim_step / ctsi_ddpm_step with the U-Net input slice `zin` written in fp32 (NDHWC, c_total channels, offset c_off). */
+int ctsi_ddim_step_f32(float* z, const float* eps, const float* noise, float* zin, int c_total, int c_off, const float* coef,
+                       const int* step_ptr, int n, int c, int d, int h, int w, int* nonfinite, void* stream);
+int ctsi_ddpm_step_f32(float* z, const float* eps, const float* noise, float* zin, int c_total, int c_off, const float* coef,
+                       const int* step_ptr, int n, int c, int d, int h, int w, void* stream);
+
 /* hipGraph helpers (one captured graph per denoising step) -------------------------------- */
 typedef struct ctsi_graph ctsi_graph;
 int ctsi_graph_begin_capture(void* stream);

@@ -263,10 +263,14 @@ __device__ __forceinline__ void count_nonfinite(float v, int& n_nan, int& n_inf)
     n_inf += (v == __builtin_inff() || v == -__builtin_inff()) ? 1 : 0;
 }
 
-template <bool DDPM>
+// the U-Net input slice `zin` is bf16 (bf16 engine) or fp32 (fp32 inference mode, ctsi_ddim_step_f32 / ctsi_ddpm_step_f32)
+__device__ __forceinline__ void store_zin(bf16_t* p, float v) { *p = f32_to_bf16(v); }
+__device__ __forceinline__ void store_zin(float* p, float v) { *p = v; }
+
+template <bool DDPM, typename ZT>
 __global__ void __launch_bounds__(256)
 sampler_step_kernel(float* __restrict__ z, const float* __restrict__ eps, const float* __restrict__ noise,
-                    bf16_t* __restrict__ zin, int c_total, int c_off, const float* __restrict__ coef,
+                    ZT* __restrict__ zin, int c_total, int c_off, const float* __restrict__ coef,
                     const int* __restrict__ step_ptr, int c, long long vox, long long total, int* __restrict__ nonfinite) {
     const int step = step_ptr ? *step_ptr : 0;
     const float* cf = coef + (long long)step * 8;
@@ -302,7 +306,7 @@ sampler_step_kernel(float* __restrict__ z, const float* __restrict__ eps, const 
             zn = nan_to_num_f(zn);
         }
         z[e] = zn;
-        if (zin) zin[nv * c_total + c_off + ch] = f32_to_bf16(zn);
+        if (zin) store_zin(zin + nv * c_total + c_off + ch, zn);
     }
     if (!DDPM && nonfinite != nullptr) {
         const int any = cnt[0] | cnt[1] | cnt[2] | cnt[3] | cnt[4] | cnt[5];
@@ -314,8 +318,8 @@ sampler_step_kernel(float* __restrict__ z, const float* __restrict__ eps, const 
     }
 }
 
-template <bool DDPM>
-static int sampler_step(float* z, const float* eps, const float* noise, void* zin, int c_total, int c_off,
+template <bool DDPM, typename ZT>
+static int sampler_step(float* z, const float* eps, const float* noise, ZT* zin, int c_total, int c_off,
                         const float* coef, const int* step_ptr, int n, int c, int d, int h, int w, int* nonfinite,
                         void* stream) {
     CTSI_CHECK_ARG(z && eps && coef, "sampler step: null argument");
@@ -323,8 +327,8 @@ static int sampler_step(float* z, const float* eps, const float* noise, void* zi
     const long long vox = (long long)d * h * w, total = vox * n * c;
     long long blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((sampler_step_kernel<DDPM>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, z,
-                       eps, noise, (bf16_t*)zin, c_total, c_off, coef, step_ptr, c, vox, total, nonfinite);
+    hipLaunchKernelGGL((sampler_step_kernel<DDPM, ZT>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, z,
+                       eps, noise, zin, c_total, c_off, coef, step_ptr, c, vox, total, nonfinite);
     CTSI_LAUNCH_CHECK();
     return CTSI_OK;
 }
@@ -332,11 +336,21 @@ static int sampler_step(float* z, const float* eps, const float* noise, void* zi
 extern "C" int ctsi_ddim_step(float* z, const float* eps, const float* noise, void* zin, int c_total, int c_off,
                               const float* coef, const int* step_ptr, int n, int c, int d, int h, int w,
                               int* nonfinite, void* stream) {
-    return sampler_step<false>(z, eps, noise, zin, c_total, c_off, coef, step_ptr, n, c, d, h, w, nonfinite, stream);
+    return sampler_step<false>(z, eps, noise, (bf16_t*)zin, c_total, c_off, coef, step_ptr, n, c, d, h, w, nonfinite,
+                               stream);
 }
 extern "C" int ctsi_ddpm_step(float* z, const float* eps, const float* noise, void* zin, int c_total, int c_off,
                               const float* coef, const int* step_ptr, int n, int c, int d, int h, int w,
                               void* stream) {
+    return sampler_step<true>(z, eps, noise, (bf16_t*)zin, c_total, c_off, coef, step_ptr, n, c, d, h, w, nullptr, stream);
+}
+extern "C" int ctsi_ddim_step_f32(float* z, const float* eps, const float* noise, float* zin, int c_total, int c_off,
+                                  const float* coef, const int* step_ptr, int n, int c, int d, int h, int w, int* nonfinite,
+                                  void* stream) {
+    return sampler_step<false>(z, eps, noise, zin, c_total, c_off, coef, step_ptr, n, c, d, h, w, nonfinite, stream);
+}
+extern "C" int ctsi_ddpm_step_f32(float* z, const float* eps, const float* noise, float* zin, int c_total, int c_off,
+                                  const float* coef, const int* step_ptr, int n, int c, int d, int h, int w, void* stream) {
     return sampler_step<true>(z, eps, noise, zin, c_total, c_off, coef, step_ptr, n, c, d, h, w, nullptr, stream);
 }
 

@@ -220,7 +220,9 @@ class GaussianDiffusion(nn.Module):
                     with ctx.scope():
                         ctx.lib.ndhwc_f32_to_ncdhw_f32(C.c_void_p(prog.eps.data_ptr()), C.c_void_p(eps.data_ptr()), B, L, d, h,
                                                        w, ctx.sptr)
-                    v_pred = vae.decode(self._predict_z_0_from_noise(z_t, t, eps))
+                    z0_pred = self._predict_z_0_from_noise(z_t, t, eps)
+                    # training keeps the bf16 programs whatever `vae.inference_precision` says
+                    v_pred = vae._decode(z0_pred, "bf16") if hasattr(vae, "_decode") else vae.decode(z0_pred)
                     terms = []
                     for i in range(v_gt.shape[2]):
                         terms.append(1.0 - ms_ssim((v_pred[:, :, i] + 1.0) / 2.0, (v_gt[:, :, i].float() + 1.0) / 2.0,

@@ -1054,8 +1054,7 @@ class UNetProgram(Program):
         self.attention_mode = attention_mode
         self.max_rows = max_rows
         halo = 0 if shard is None else 1
-        self.xin = Act(self.persistent((n * (d + 2 * halo) * h * w * 2 * L,), torch.bfloat16, zero=True), n, 2 * L, d,
-                       h, w, halo)
+        self.xin, self.xin2 = self._input_acts(n, d, h, w, halo)
         self.eps = self.persistent((n, d, h, w, L), torch.float32)
         self.z = self.persistent((n, d, h, w, L), torch.float32, zero=True)
         self.step_ptr = self.persistent((1,), torch.int32, zero=True)
@@ -1086,7 +1085,7 @@ class UNetProgram(Program):
 
         # ---- network ------------------------------------------------------------------------------------
         self.zero_gn_op()
-        x, _ = self.conv("conv_in", lambda: unet.conv_in.weight, lambda: unet.conv_in.bias, self.xin, None,
+        x, _ = self.conv("conv_in", lambda: unet.conv_in.weight, lambda: unet.conv_in.bias, self.xin, self.xin2,
                          cout=unet.conv_in.out_channels)
         skips: List[Act] = []
 
@@ -1132,6 +1131,12 @@ class UNetProgram(Program):
         self.release(y)
         self.unet_op_count = len(self.ops)
         self.finalize_layout()
+
+    def _input_acts(self, n, d, h, w, halo) -> Tuple[Act, Optional[Act]]:
+        """The network input: ONE bf16 tensor [z | cond] (2 L channels; the sampler writes the z half in place)."""
+        L = self.L
+        return Act(self.persistent((n * (d + 2 * halo) * h * w * 2 * L,), torch.bfloat16, zero=True), n, 2 * L, d, h, w,
+                   halo), None
 
     def _layer(self, layer, x: Act, skip: Optional[Act]) -> Act:
         kind = type(layer).__name__
@@ -1237,10 +1242,9 @@ class VAEEncodeProgram(Program):
         cin = vae.in_channels
         self.cin, self.cin_pad = cin, _pad8(cin)
         self.track_module(enc)
-        self.xin = Act(self.persistent((n * d * h * w * self.cin_pad,), torch.bfloat16, zero=True), n,
-                       self.cin_pad, d, h, w)
+        self.xin, cin_w = self._input_act(n, cin, d, h, w, 0)
         self.zero_gn_op()
-        x = self._conv_gn_act(enc.conv_in, self.xin, cin_w=cin, free=False)
+        x = self._conv_gn_act(enc.conv_in, self.xin, cin_w=cin_w, free=False)
         for stage in (enc.down1, enc.down2):
             for m in stage:
                 x = self._block(m, x)
@@ -1261,6 +1265,15 @@ class VAEEncodeProgram(Program):
                   f32_strides=(L * vox, vox, hl * wl, wl, 1))
         self.release(y)
         self.finalize_layout()
+
+    def _input_act(self, n, c, d, h, w, halo) -> Tuple[Act, Optional[int]]:
+        """The network input and the `cin_w` of its first conv: bf16 NDHWC padded to 8 channels (the weights carry c)."""
+        return Act(self.persistent((n * (d + 2 * halo) * h * w * _pad8(c),), torch.bfloat16, zero=True), n, _pad8(c), d, h,
+                   w, halo), c
+
+    def _upload(self, src: torch.Tensor, a: Act, c: int):
+        """fp32 NCDHW `src` (c channels) -> the own slices of the input tensor `a`."""
+        self.lib.ncdhw_f32_to_ndhwc_bf16(_ptr(src), a.ip, a.n, c, a.d, a.h, a.w, a.c, 0, self.ctx.sptr)
 
     def _conv_gn_act(self, m, x: Act, *, cin_w=None, free=True, k=(3, 3, 3), s=(1, 1), transposed=False) -> Act:
         c, st = self.conv("conv+gn", lambda: m.conv.weight, lambda: m.conv.bias, x, None, k=k, s=s,
@@ -1293,11 +1306,9 @@ class VAEEncodeProgram(Program):
         raise CtsiError(f"unsupported VAE block {kind}")
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
-        lib, sptr = self.lib, self.ctx.sptr
         self.ensure_fresh()
         xx = x.detach().to(device=self.ctx.device, dtype=torch.float32).contiguous()
-        lib.ncdhw_f32_to_ndhwc_bf16(_ptr(xx), _ptr(self.xin.t), self.n, self.cin, self.d, self.h, self.w,
-                                    self.cin_pad, 0, sptr)
+        self._upload(xx, self.xin, self.cin)
         xx.record_stream(self.ctx.stream)
         self.launch()
         out = self.out.clone()
@@ -1319,13 +1330,12 @@ class VAEDecodeProgram(VAEEncodeProgram):
         self.L, self.L_pad = L, _pad8(L)
         self.track_module(dec)
         halo = 0 if shard is None else 1
-        self.zin = Act(self.persistent((n * (d + 2 * halo) * h * w * self.L_pad,), torch.bfloat16, zero=True), n,
-                       self.L_pad, d, h, w, halo)
+        self.zin, cin_w = self._input_act(n, L, d, h, w, halo)
         self.zero_gn_op()
         inv = lambda: 1.0 / float(vae.scaling_factor)
         x, _ = self.conv("dec.post_quant", lambda: dec.post_quant_conv.weight * inv(),
                          lambda: dec.post_quant_conv.bias, self.zin, None, k=(1, 1, 1), p=(0, 0, 0),
-                         cout=dec.post_quant_conv.out_channels, cin_w=L)
+                         cout=dec.post_quant_conv.out_channels, cin_w=cin_w)
         x = self._conv_gn_act(dec.conv_in, x)
         for m in dec.mid:
             x = self._block(m, x)
@@ -1346,11 +1356,10 @@ class VAEDecodeProgram(VAEEncodeProgram):
         self.finalize_layout()
 
     def load(self, z: torch.Tensor):
-        lib, sptr = self.lib, self.ctx.sptr
         self.ensure_fresh()
         lo = 0 if self.shard is None else self.shard.depth_start
         zz = z.detach()[:, :, lo:lo + self.d].to(device=self.ctx.device, dtype=torch.float32).contiguous()
-        lib.ncdhw_f32_to_ndhwc_bf16(_ptr(zz), self.zin.ip, self.n, self.L, self.d, self.h, self.w, self.L_pad, 0, sptr)
+        self._upload(zz, self.zin, self.L)
         zz.record_stream(self.ctx.stream)
 
     def __call__(self, z: torch.Tensor) -> torch.Tensor:

@@ -1,0 +1,333 @@
+"""fp32 inference mode of the engine: the U-Net and VAE programs with fp32 activations and fp32 MFMA convolutions.
+
+The reference's `generate()` runs the VAE and the whole sampler in fp32 (models/model.py:254-259).  These programs are
+built by the SAME module walks as engine.UNetProgram / VAEEncodeProgram / VAEDecodeProgram and use the same emit,
+capture and launch machinery (one captured hipGraph per sampler step); only the primitives differ:
+
+  activations   fp32 NDHWC (exact channel counts: no layout padding)
+  convolutions  ctsi_conv_f32_fwd: implicit GEMM on v_mfma_f32_32x32x2_f32, fp32 operands, fp32 accumulation
+  weights       fp32 image [class][tap * cpad + ci][cout_pad], cached under a key that carries the precision
+  GroupNorm     ctsi_gn_colsum_f32 / conv column sums -> ctsi_gn_finalize (fp64) -> ctsi_gn_apply_f32
+  attention     fast mode only: ctsi_attn_depthsum_f32 / _normsum_f32, the folded (proj_out . W_v) matrix (fp64 product,
+                rounded once) as one fp32 1x1x1 conv, ctsi_attn_broadcast_add_f32
+  sampler       ctsi_ddim_step_f32 / ctsi_ddpm_step_f32 (the U-Net's z input written in fp32)
+
+Not supported here (CtsiError): depth sharding, attention_mode='exact', training.  There is no torch conv, MIOpen or BLAS
+call on this path: torch allocates and copies.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import weakref
+from typing import List, Optional, Tuple
+
+import torch
+import torch.nn as nn
+
+from .engine import (_PACKED, Act, Ctx, UNetProgram, VAEDecodeProgram, VAEEncodeProgram, _content_key,
+                     _ptr)
+from .lib import ConvDesc, ConvOut, CtsiError
+
+PRECISIONS = ("bf16", "fp32")
+
+
+def check_precision(p) -> str:
+    """Validate an inference precision value ('bf16' | 'fp32'); raises ValueError otherwise."""
+    if not isinstance(p, str) or p not in PRECISIONS:
+        raise ValueError(f"unknown inference precision {p!r}: expected one of {PRECISIONS}")
+    return p
+
+
+class _F32Ops:
+    """The primitive emitters of engine.Program on fp32 tensors (mixed in before the bf16 program class)."""
+
+    precision = "fp32"
+
+    def act(self, n, c, d, h, w, halo: Optional[int] = None) -> Act:
+        if halo:
+            raise CtsiError("the fp32 inference mode does not support depth sharding")
+        return Act(self.pool.get(n * c * d * h * w, torch.float32), n, c, d, h, w, 0)
+
+    def conv(self, name: str, weight_fn, bias_fn, x1: Act, x2: Optional[Act], *, transposed=False, k=(3, 3, 3), s=(1, 1),
+             p=(1, 1, 1), cout: int, cin_w: Optional[int] = None, out: Optional[Act] = None, want_stats=False,
+             f32_out: Optional[torch.Tensor] = None, f32_strides=None, act: int = 0, fuse_gn=None, ext_out: bool = False,
+             norm_in=None, residual: Optional[Act] = None):
+        """engine.Program.conv on ctsi_conv_f32_fwd.  `norm_in` is applied as its own in-place pass first; `residual`
+        (fp32 Act of the output's shape) is added in the epilogue.  The fused GroupNorm tail has no fp32 form."""
+        lib, prog = self.lib, self
+        if fuse_gn is not None or ext_out:
+            raise CtsiError("internal: the fused GroupNorm tail / halo-extended outputs are bf16-path features")
+        c2 = 0 if x2 is None else x2.c
+        if cin_w is not None and cin_w != x1.c + c2:
+            raise CtsiError(f"internal: fp32 activations carry no padding channels (cin_w={cin_w}, c={x1.c + c2})")
+        if x2 is not None and (x2.n, x2.d, x2.h, x2.w) != (x1.n, x1.d, x1.h, x1.w):
+            raise CtsiError("internal: concatenated sources of different shapes")
+        if norm_in is not None:
+            nslot, ngn, nsilu, ntb = norm_in
+            kw_tb = {} if ntb is None else dict(tbias=ntb[0], tbias_off=ntb[1], tbias_stride=ntb[2], step_ptr=ntb[3])
+            self.gn_apply(x1, nslot, ngn, silu_pre=nsilu, out=x1, **kw_tb)
+        desc = ConvDesc(int(transposed), k[0], k[1], k[2], s[0], s[1], p[0], p[1], p[2], x1.n, x1.c, c2, cout, x1.d, x1.h,
+                        x1.w, 0)
+        if not lib.conv_f32_supported(C.byref(desc)):
+            raise CtsiError(f"{name}: {lib.last_error().decode()}")
+        self.keep.append(desc)
+        do, ho, wo, tps, ncls, cpad = (C.c_int() for _ in range(6))
+        lib.conv_f32_geometry(C.byref(desc), C.byref(do), C.byref(ho), C.byref(wo), C.byref(tps), C.byref(ncls),
+                              C.byref(cpad))
+        do, ho, wo, tps, ncls, cpad = do.value, ho.value, wo.value, tps.value, ncls.value, cpad.value
+        wbytes = lib.conv_f32_weight_bytes(C.byref(desc))
+        bias = (self.dev_f32(bias_fn, parts=getattr(bias_fn, "parts", None), scale=getattr(bias_fn, "scale", 1.0))
+                if bias_fn is not None else None)
+        sptr = self.ctx.sptr
+        # the fp32 image is its own cache family: the precision leads the key, so a bf16 program never finds it
+        sig = ("fp32", int(transposed), tuple(k), tuple(s), x1.c, c2, cout, cpad, wbytes)
+        holder: List[Optional[torch.Tensor]] = [None]
+
+        def pack():
+            wt = weight_fn().detach().to(device=prog.ctx.device, dtype=torch.float32).contiguous()
+            cache = _PACKED.setdefault(prog.ctx.device.index, weakref.WeakValueDictionary())
+            key = (sig, _content_key(wt))
+            t = cache.get(key)
+            if t is None:
+                t = torch.empty(wbytes, dtype=torch.uint8, device=prog.ctx.device)
+                lib.conv_f32_pack_weights(C.byref(desc), _ptr(wt), _ptr(t), sptr)
+                cache[key] = t
+                prog.pack_stats["packed"] += 1
+            else:
+                prog.pack_stats["shared"] += 1
+            wt.record_stream(prog.ctx.stream)
+            if holder[0] is not t:
+                prog._weights_moved = prog._weights_moved or holder[0] is not None
+                holder[0] = t
+
+        self.pack_fns.append(pack)
+        fl = lib.conv_f32_flops(C.byref(desc))
+        self.flops += fl
+        self.conv_flops.append((name, fl))
+        stats = None
+        if want_stats:
+            self._colsum_need = max(self._colsum_need, 2 * ncls * x1.n * tps * cpad)
+            stats = dict(tps=tps, cpad=cpad, nclass=ncls)
+        co = ConvOut()
+        if f32_out is not None:
+            co.y = f32_out.data_ptr()
+            co.mode = 1
+            co.sn, co.sc, co.sd, co.sh, co.sw = [int(v) for v in f32_strides]
+            out_act = None
+        else:
+            if out is None:
+                out = self.act(x1.n, cout, do, ho, wo)
+            if (out.n, out.c, out.d, out.h, out.w) != (x1.n, cout, do, ho, wo):
+                raise CtsiError("internal: conv output buffer of the wrong shape")
+            co.y = out.t.data_ptr()
+            co.mode = 0
+            co.cout_stride = out.c
+            co.c_off = 0
+            out_act = out
+        if residual is not None and (f32_out is not None or residual.t.numel() != out.t.numel()):
+            raise CtsiError("internal: the residual must have the NDHWC output's shape")
+        co.act = act
+        self.keep.append(co)
+        x1p, x2p = _ptr(x1.t), _ptr(None if x2 is None else x2.t)
+        bp, rp = _ptr(bias), _ptr(None if residual is None else residual.t)
+
+        def run():
+            co.colsum = prog._colsum.data_ptr() if want_stats else 0
+            lib.conv_f32_fwd(C.byref(desc), x1p, x2p, _ptr(holder[0]), bp, rp, C.byref(co), sptr)
+
+        bn = 32 if cout <= 32 else (64 if cout <= 64 else 128)
+        kernel = "conv_f32_mfma_128x%d%s" % (bn, "t" if transposed else ("d" if tuple(s) == (2, 2) else ""))
+        alg = (4.0 * x1.n * x1.d * x1.h * x1.w * (x1.c + c2) + float(wbytes) + 4.0 * x1.n * do * ho * wo * cout
+               * (2 if residual is not None else 1))
+        self._emit(run, name, fl, kernel, alg_bytes=alg)
+        return out_act, stats
+
+    def gn_colsum(self, x: Act) -> dict:
+        lib, sptr, prog = self.lib, self.ctx.sptr, self
+        tps = lib.gn_colsum_f32_tiles(x.d, x.h, x.w)
+        self._colsum_need = max(self._colsum_need, 2 * x.n * tps * x.c)
+        xp = _ptr(x.t)
+        n, c, d, h, w = x.n, x.c, x.d, x.h, x.w
+
+        def run():
+            lib.gn_colsum_f32(xp, _ptr(prog._colsum), n, c, d, h, w, None, sptr)
+
+        self._emit(run, "gn.colsum", nbytes=4.0 * n * c * d * h * w)
+        return dict(tps=tps, cpad=x.c, nclass=1)
+
+    def gn_apply(self, x: Act, slot: int, gn: nn.GroupNorm, *, silu_pre: bool, tbias=None, tbias_off: int = 0,
+                 tbias_stride: int = 0, step_ptr: Optional[torch.Tensor] = None, residual: Optional[Act] = None,
+                 silu_post: bool = False, out: Optional[Act] = None, synced: bool = False) -> Act:
+        lib, sptr, prog = self.lib, self.ctx.sptr, self
+        gamma = self.dev_f32(lambda: gn.weight)
+        beta = self.dev_f32(lambda: gn.bias)
+        self.track(gn.weight, gn.bias)
+        if out is None:
+            out = self.act(x.n, x.c, x.d, x.h, x.w)
+        xp, yp, gp, bp = _ptr(x.t), _ptr(out.t), _ptr(gamma), _ptr(beta)
+        tbp = C.c_void_p(0 if tbias is None else tbias.data_ptr() + tbias_off * 4)
+        stp = _ptr(step_ptr)
+        rp = _ptr(None if residual is None else residual.t)
+        n, c, d, h, w, groups, eps = x.n, x.c, x.d, x.h, x.w, gn.num_groups, float(gn.eps)
+
+        def run():
+            lib.gn_apply_f32(xp, yp, C.c_void_p(prog._gn_sums.data_ptr() + slot * 8), gp, bp, n, c, d, h, w, d, groups, eps,
+                             int(silu_pre), tbp, tbias_stride, stp, rp, int(silu_post), sptr)
+
+        self._emit(run, "gn.apply", nbytes=(2 + (residual is not None)) * 4.0 * n * c * d * h * w)
+        return out
+
+    def unet_resblock(self, m, x: Act, skip: Optional[Act], tbias: torch.Tensor, tbias_off: int, tbias_stride: int,
+                      step_ptr: Optional[torch.Tensor]) -> Act:
+        """ResBlock3D (models/unet3d.py:116-133): conv1 (+column sums) -> GN + SiLU + time bias in place -> conv2 ->
+        silu(gn(c2) + residual), the residual being x itself or the 1x1x1 conv of [x | skip]."""
+        cout = m.conv1.conv.out_channels
+        has_res_conv = not isinstance(m.residual_conv, nn.Identity)
+        if not has_res_conv and skip is not None:
+            raise CtsiError("identity residual with a concatenated input")
+        c1, st = self.conv("rb.conv1", lambda: m.conv1.conv.weight, lambda: m.conv1.conv.bias, x, skip, cout=cout,
+                           want_stats=True)
+        slot = self.gn_finalize(c1, m.conv1.norm.num_groups, st)
+        c2, st = self.conv("rb.conv2", lambda: m.conv2[0].weight, lambda: m.conv2[0].bias, c1, None, cout=cout,
+                           want_stats=True, norm_in=(slot, m.conv1.norm, True, (tbias, tbias_off, tbias_stride, step_ptr)))
+        self.release(c1)
+        slot = self.gn_finalize(c2, m.conv2[1].num_groups, st)
+        if not has_res_conv:
+            return self.gn_apply(c2, slot, m.conv2[1], silu_pre=False, residual=x, silu_post=True, out=c2)
+        r, _ = self.conv("res1x1", lambda: m.residual_conv.weight, lambda: m.residual_conv.bias, x, skip, k=(1, 1, 1),
+                         p=(0, 0, 0), cout=cout)
+        out = self.gn_apply(c2, slot, m.conv2[1], silu_pre=False, residual=r, silu_post=True, out=c2)
+        self.release(r)
+        return out
+
+    def attention(self, m, x: Act, mode: str = "fast") -> Act:
+        """TemporalAttention, fast mode (csrc/attention.hip has the identity it rests on)."""
+        if mode != "fast":
+            raise CtsiError("the fp32 inference mode supports attention_mode='fast' only (the exact mode evaluates the "
+                            "same mathematics, DESIGN section 3.2)")
+        lib, sptr, prog = self.lib, self.ctx.sptr, self
+        n, c, d, h, w = x.n, x.c, x.d, x.h, x.w
+        tps = lib.attn_depthsum_f32_tiles(h, w)
+        self._colsum_need = max(self._colsum_need, 2 * n * tps * c)
+        depthsum = self.pool.get(n * h * w * c, torch.float32)
+        xp, dsp = _ptr(x.t), _ptr(depthsum)
+
+        def run_ds():
+            lib.attn_depthsum_f32(xp, dsp, _ptr(prog._colsum), n, c, d, h, w, sptr)
+
+        self._emit(run_ds, "attn.depthsum", nbytes=4.0 * n * c * d * h * w)
+        slot = self.gn_finalize(x, m.norm.num_groups, dict(tps=tps, cpad=c, nclass=1))
+        gamma = self.dev_f32(lambda: m.norm.weight)
+        beta = self.dev_f32(lambda: m.norm.bias)
+        groups, eps = m.norm.num_groups, float(m.norm.eps)
+        gp, bp = _ptr(gamma), _ptr(beta)
+        xs = self.act(n, c, 1, h, w)
+        xsp = _ptr(xs.t)
+
+        def run_ns():
+            lib.attn_normsum_f32(dsp, C.c_void_p(prog._gn_sums.data_ptr() + slot * 8), gp, bp, xsp, n, c, d, h, w, groups,
+                                 eps, sptr)
+
+        self._emit(run_ns, "attn.normsum")
+
+        # fold proj_out . V-projection in fp64, round once:  P = (Wp Wv) xs + (D Wp bv + bp)
+        def wpv():
+            wp = m.proj_out.weight[:, :, 0, 0, 0].double()
+            return (wp @ m.qkv.weight[2 * c:3 * c, :, 0, 0, 0].double()).float().reshape(c, c, 1, 1, 1)
+
+        def bpv():
+            wp = m.proj_out.weight[:, :, 0, 0, 0].double()
+            return (float(d) * (wp @ m.qkv.bias[2 * c:3 * c].double()) + m.proj_out.bias.double()).float()
+
+        pterm, _ = self.conv("attn.pv", wpv, bpv, xs, None, k=(1, 1, 1), p=(0, 0, 0), cout=c)
+        self.pool.put(depthsum)
+        self.release(xs)
+        out = self.act(n, c, d, h, w)
+        pp, op_ = _ptr(pterm.t), _ptr(out.t)
+
+        def run_ba():
+            lib.attn_broadcast_add_f32(xp, pp, op_, n, c, d, h, w, sptr)
+
+        self._emit(run_ba, "attn.broadcast_add", nbytes=12.0 * n * c * d * h * w)
+        self.release(pterm)
+        return out
+
+
+# ==========================================================================================================
+# U-Net
+# ==========================================================================================================
+class UNetProgramF32(_F32Ops, UNetProgram):
+    """engine.UNetProgram in fp32.  The network input is two fp32 NDHWC tensors, z and the conditioning, fed to conv_in as
+    a concatenated pair (never materialised)."""
+
+    def __init__(self, ctx: Ctx, unet, n: int, d: int, h: int, w: int, max_rows: int, attention_mode="fast", shard=None):
+        if shard is not None:
+            raise CtsiError("the fp32 inference mode does not support depth sharding")
+        if attention_mode != "fast":
+            raise CtsiError("the fp32 inference mode supports attention_mode='fast' only (the exact mode evaluates the "
+                            "same mathematics, DESIGN section 3.2)")
+        super().__init__(ctx, unet, n, d, h, w, max_rows, attention_mode, shard=None)
+
+    def _input_acts(self, n, d, h, w, halo) -> Tuple[Act, Optional[Act]]:
+        L = self.L
+        zin = Act(self.persistent((n * d * h * w * L,), torch.float32, zero=True), n, L, d, h, w, 0)
+        cin = Act(self.persistent((n * d * h * w * L,), torch.float32, zero=True), n, L, d, h, w, 0)
+        return zin, cin
+
+    def load_latents(self, z_ncdhw: Optional[torch.Tensor], cond_ncdhw: Optional[torch.Tensor]):
+        lib, sptr = self.lib, self.ctx.sptr
+        n, L, d, h, w = self.n, self.L, self.d, self.h, self.w
+        if z_ncdhw is not None:
+            z = z_ncdhw.detach().to(device=self.ctx.device, dtype=torch.float32).contiguous()
+            lib.ncdhw_f32_to_ndhwc_f32(_ptr(z), _ptr(self.z), n, L, d, h, w, sptr)
+            lib.ncdhw_f32_to_ndhwc_f32(_ptr(z), _ptr(self.xin.t), n, L, d, h, w, sptr)
+            z.record_stream(self.ctx.stream)
+        if cond_ncdhw is not None:
+            cnd = cond_ncdhw.detach().to(device=self.ctx.device, dtype=torch.float32).contiguous()
+            lib.ncdhw_f32_to_ndhwc_f32(_ptr(cnd), _ptr(self.xin2.t), n, L, d, h, w, sptr)
+            cnd.record_stream(self.ctx.stream)
+
+    def add_sampler_step(self, kind: str, with_noise: bool):
+        lib, sptr = self.lib, self.ctx.sptr
+        n, L, d, h, w = self.n, self.L, self.d, self.h, self.w
+        if with_noise and self.noise is None:
+            self.noise = self.persistent((n, L, d, h, w), torch.float32, zero=True)
+        zp, ep, xp, cp, sp = _ptr(self.z), _ptr(self.eps), _ptr(self.xin.t), _ptr(self.coef), _ptr(self.step_ptr)
+        npz = _ptr(self.noise if with_noise else None)
+        self.nonfinite = self.persistent((self.max_rows + 2, 6), torch.int32, zero=True)
+        nfp = _ptr(self.nonfinite)
+
+        def run_step():
+            if kind == "ddim":
+                lib.ddim_step_f32(zp, ep, npz, xp, L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
+            else:
+                lib.ddpm_step_f32(zp, ep, npz, xp, L, 0, cp, sp, n, L, d, h, w, sptr)
+
+        def run_adv():
+            lib.step_advance(sp, sptr)
+
+        self._emit(run_step, "sampler.step", nbytes=(4 + 4 + 4 + 4 + (4 if with_noise else 0)) * float(n * L * d * h * w))
+        self._emit(run_adv, "sampler.advance")
+        self.sampler_kind = (kind, with_noise)
+
+
+# ==========================================================================================================
+# VAE
+# ==========================================================================================================
+class VAEEncodeProgramF32(_F32Ops, VAEEncodeProgram):
+    """engine.VAEEncodeProgram in fp32: the same walk; the input volume keeps its own channel count."""
+
+    def _input_act(self, n, c, d, h, w, halo) -> Tuple[Act, Optional[int]]:
+        return Act(self.persistent((n * d * h * w * c,), torch.float32, zero=True), n, c, d, h, w), None
+
+    def _upload(self, src: torch.Tensor, a: Act, c: int):
+        self.lib.ncdhw_f32_to_ndhwc_f32(_ptr(src), _ptr(a.t), a.n, c, a.d, a.h, a.w, self.ctx.sptr)
+
+
+class VAEDecodeProgramF32(VAEEncodeProgramF32, VAEDecodeProgram):
+    """engine.VAEDecodeProgram in fp32 (one device; the tanh head stores fp32 NCDHW)."""
+
+    def __init__(self, ctx: Ctx, vae, n, d, h, w, shard=None):
+        if shard is not None:
+            raise CtsiError("the fp32 inference mode does not support depth sharding")
+        VAEDecodeProgram.__init__(self, ctx, vae, n, d, h, w)

@@ -151,6 +151,22 @@ SIGNATURES = {
     "ctsi_adamw_multi": (_i, [_vp, _vp, _vp, _i, _vp], True),
     "ctsi_copy_scale_multi": (_i, [_vp, _vp, _i, _vp], True),
     "ctsi_device_error_status": (_i, [C.POINTER(C.c_uint), C.POINTER(C.c_uint), _i], True),
+    "ctsi_conv_f32_supported": (_i, [C.POINTER(ConvDesc)], False),
+    "ctsi_conv_f32_weight_bytes": (_sz, [C.POINTER(ConvDesc)], False),
+    "ctsi_conv_f32_flops": (C.c_double, [C.POINTER(ConvDesc)], False),
+    "ctsi_conv_f32_geometry": (_i, [C.POINTER(ConvDesc), _ip, _ip, _ip, _ip, _ip, _ip], True),
+    "ctsi_conv_f32_pack_weights": (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp], True),
+    "ctsi_conv_f32_fwd": (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvOut), _vp], True),
+    "ctsi_gn_colsum_f32_tiles": (_i, [_i, _i, _i], False),
+    "ctsi_gn_colsum_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ip, _vp], True),
+    "ctsi_gn_apply_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp, _vp,
+                               _i, _vp], True),
+    "ctsi_attn_depthsum_f32_tiles": (_i, [_i, _i], False),
+    "ctsi_attn_depthsum_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_attn_normsum_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp], True),
+    "ctsi_attn_broadcast_add_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_ddim_step_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp], True),
+    "ctsi_ddpm_step_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp], True),
     "ctsi_graph_begin_capture": (_i, [_vp], True),
     "ctsi_graph_end_capture": (_i, [_vp, C.POINTER(_vp)], True),
     "ctsi_graph_launch": (_i, [_vp, _vp], True),

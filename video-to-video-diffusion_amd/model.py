@@ -10,6 +10,7 @@ import torch.nn.functional as F
 
 from .diffusion import GaussianDiffusion
 from .engine import Ctx, nan_to_num_, trilinear_depth
+from .engine_f32 import check_precision
 from .lib import CtsiError
 from .unet3d import UNet3D
 from .vae import VideoVAE
@@ -63,6 +64,16 @@ class VideoToVideoDiffusion(nn.Module):
                                            beta_end=config.get('beta_end', 0.02))
         self.config = config
         self.use_pretrained = use_pretrained
+        # additive key: the arithmetic of generate() / the samplers / encode / decode ('bf16' default, or 'fp32')
+        self.set_inference_precision(config.get('hardware', {}).get('inference_precision', 'bf16'))
+
+    def set_inference_precision(self, precision):
+        """'bf16' (default) or 'fp32': sets `unet.inference_precision` and `vae.inference_precision`, i.e. the arithmetic
+        of generate(), the samplers and VAE encode / decode (engine_f32.py: fp32 activations, fp32 MFMA operands, the
+        reference's fp32 inference of models/model.py:254-259).  Training (`forward`) keeps its bf16 programs."""
+        check_precision(precision)
+        self.unet.inference_precision = precision
+        self.vae.inference_precision = precision
 
     def invalidate_engine_cache(self):
         """Drop the engine's cached programs (packed bf16 weights, captured graphs) -- needed only after weight
@@ -88,8 +99,9 @@ class VideoToVideoDiffusion(nn.Module):
             raise CtsiError("the training forward runs on the HIP engine: move the inputs to a ROCm device")
         ctx = Ctx.get(v_in.device)
         with torch.no_grad():
-            z_in = self.vae.encode(v_in)
-            z_gt = self.vae.encode(v_gt)
+            # training keeps the bf16 programs whatever `inference_precision` says
+            z_in = self.vae._encode(v_in, "bf16")
+            z_gt = self.vae._encode(v_gt, "bf16")
             if z_in.shape[2] != z_gt.shape[2]:
                 with ctx.scope():
                     z_cond = trilinear_depth(ctx, z_in, int(z_gt.shape[2]))
@@ -105,12 +117,22 @@ class VideoToVideoDiffusion(nn.Module):
 
     @torch.no_grad()
     def generate(self, v_in, sampler, num_inference_steps=20, guidance_scale=1.0, target_depth=None,
-                 noise_fn=None):
+                 noise_fn=None, precision=None):
         """thick slices (B, C, T_in, H, W) -> thin slices (B, C, T_out, H, W), fp32.
 
         encode -> trilinear depth upsample of the conditioning -> DDIM/DDPM -> decode, with the
         reference's nan_to_num guards applied unconditionally on device (model.py:230-343).
-        `guidance_scale` is accepted and ignored, as in the reference."""
+        `guidance_scale` is accepted and ignored, as in the reference.
+        `precision` (additive, default None = the models' `inference_precision` attributes): 'bf16' or 'fp32' for this
+        call only; the attributes are restored afterwards."""
+        if precision is not None:
+            check_precision(precision)
+            saved = (self.unet.inference_precision, self.vae.inference_precision)
+            self.unet.inference_precision = self.vae.inference_precision = precision
+            try:
+                return self.generate(v_in, sampler, num_inference_steps, guidance_scale, target_depth, noise_fn)
+            finally:
+                self.unet.inference_precision, self.vae.inference_precision = saved
         if sampler not in ('ddpm', 'ddim'):
             raise ValueError(f"Unknown sampler: {sampler}")
         if not v_in.is_cuda:

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from .engine import Ctx, UNetProgram, _ptr, check_device_errors, nan_to_num_, trilinear_depth
+from .engine_f32 import UNetProgramF32, check_precision
 from .lib import CtsiError
 
 logger = logging.getLogger(__name__)
@@ -205,16 +206,21 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
     if not _is_engine_unet(model):
         return _run_sampler_generic(diffusion, model, shape, conditioning, ctx, z0, kind=kind, t_desc=t_desc, eta=eta,
                                     noise_fn=noise_fn, progress=progress, trajectory=trajectory)
+    precision = check_precision(getattr(unet, "inference_precision", "bf16"))
     comm = getattr(unet, "depth_shard_comm", None)
     if comm is not None and comm.world > 1:
+        if precision != "bf16":
+            raise CtsiError("the fp32 inference mode does not support depth sharding (unet.depth_shard_comm); "
+                            "set inference_precision='bf16' or drop the communicator")
         return run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, kind=kind, t_desc=t_desc, eta=eta,
                                    noise_fn=noise_fn, comm=comm, trajectory=trajectory)
     with ctx.scope():
-        key = ("sampler", ctx.device.index, n, d, h, w, max_rows, kind, with_noise, unet.attention_mode)
+        key = ("sampler", ctx.device.index, n, d, h, w, max_rows, kind, with_noise, unet.attention_mode, precision)
         from .engine import cached_program
 
         def build():
-            prog = UNetProgram(ctx, unet, n, d, h, w, max_rows, unet.attention_mode)
+            cls = UNetProgramF32 if precision == "fp32" else UNetProgram
+            prog = cls(ctx, unet, n, d, h, w, max_rows, unet.attention_mode)
             prog.add_sampler_step(kind, with_noise)
             return prog
 
@@ -418,6 +424,8 @@ def _stitched(sampler, v_thick_full, vae, patch_size, target_patch_size, stride,
             except Exception:
                 total = 64 << 30
             per_window = 2500.0 * b * td * th * tw
+            if getattr(vae, "inference_precision", "bf16") == "fp32":
+                per_window *= 2.0         # fp32 activations: twice the bytes per voxel
             group = max(1, min(len(mine), int(0.2 * total / per_window)))
     ngroups = max(1, -(-len(mine) // group))            # balanced groups: 25 windows, window_batch 8 -> 7 + 6 + 6 + 6
     bounds = [round(i * len(mine) / ngroups) for i in range(ngroups + 1)]

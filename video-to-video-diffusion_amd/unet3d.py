@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from .engine import Ctx, UNetProgram, cached_program
+from .engine_f32 import UNetProgramF32, check_precision
 from .lib import CtsiError
 
 _GROUP_CANDIDATES = (32, 16, 8, 4, 2, 1)
@@ -105,6 +106,12 @@ class UNet3D(nn.Module):
 
     Extra attribute `attention_mode` ('fast' | 'exact') selects how TemporalAttention's
     rowsum(softmax) factor is obtained; both reproduce the reference einsum (see attention.hip).
+
+    Extra attribute `inference_precision` ('bf16' | 'fp32', default 'bf16') selects the arithmetic of `forward` (under
+    no_grad) and of the samplers: bf16 activations and bf16 MFMA operands, or fp32 activations and fp32 MFMA operands
+    (engine_f32.py: the reference's fp32 inference, models/model.py:254-259).  'fp32' supports attention_mode='fast' and
+    one device only (CtsiError with 'exact' or with depth sharding).  Training (`diffusion.training_loss`) always runs
+    the bf16 programs, whatever this attribute says.
     """
 
     def __init__(self, latent_dim=4, model_channels=128, num_res_blocks=2, attention_levels=[1, 2],
@@ -118,6 +125,7 @@ class UNet3D(nn.Module):
         self.num_levels = len(channel_mult)
         self.use_checkpoint = use_checkpoint
         self.attention_mode = "fast"
+        self.inference_precision = "bf16"
 
         self.time_embed = TimeEmbedding(model_channels, time_embed_dim)
         self.conv_in = nn.Conv3d(latent_dim * 2, model_channels, kernel_size=3, padding=1)
@@ -173,12 +181,17 @@ class UNet3D(nn.Module):
         invalidate_engine_cache(self)
 
     def program(self, ctx: Ctx, n: int, d: int, h: int, w: int, max_rows: int) -> UNetProgram:
-        key = ("unet", ctx.device.index, n, d, h, w, max_rows, self.attention_mode)
+        precision = check_precision(self.inference_precision)
+        key = ("unet", ctx.device.index, n, d, h, w, max_rows, self.attention_mode, precision)
+        if precision == "fp32":
+            return cached_program(self, key, lambda: UNetProgramF32(ctx, self, n, d, h, w, max_rows,
+                                                                    self.attention_mode))
         return cached_program(self, key, lambda: UNetProgram(ctx, self, n, d, h, w, max_rows,
                                                              self.attention_mode))
 
     @torch.no_grad()
     def forward(self, x, t, c):
+        check_precision(self.inference_precision)
         if not (x.is_cuda and c.is_cuda):
             raise CtsiError("UNet3D.forward runs on the HIP engine: move the tensors to a ROCm device "
                             "(there is no CPU path; the oracle under oracle/ is test infrastructure only)")

@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 
 from .engine import Ctx, VAEDecodeProgram, VAEEncodeProgram, cached_program
+from .engine_f32 import VAEDecodeProgramF32, VAEEncodeProgramF32, check_precision
 from .lib import CtsiError
 from .unet3d import _EngineOnly
 
@@ -84,7 +85,11 @@ class VideoDecoder(_EngineOnly):
 
 
 class SliceInterpolationVAE(nn.Module):
-    """encode(x) = encoder(x) * scaling_factor; decode(z) = decoder(z / scaling_factor)."""
+    """encode(x) = encoder(x) * scaling_factor; decode(z) = decoder(z / scaling_factor).
+
+    Extra attribute `inference_precision` ('bf16' | 'fp32', default 'bf16') selects the arithmetic of `encode` / `decode`:
+    bf16 activations and MFMA operands, or fp32 ones (engine_f32.py).  'fp32' runs on one device (CtsiError with depth
+    sharding).  The grad-mode `forward` (training) always runs the bf16 programs, whatever this attribute says."""
 
     def __init__(self, in_channels=3, latent_dim=4, base_channels=64, scaling_factor=0.18215,
                  gradient_checkpointing=False):
@@ -95,6 +100,7 @@ class SliceInterpolationVAE(nn.Module):
         self.encoder = VideoEncoder(in_channels, latent_dim, base_channels)
         self.decoder = VideoDecoder(latent_dim, in_channels, base_channels)
         self.scaling_factor = scaling_factor
+        self.inference_precision = "bf16"
 
     def invalidate_engine_cache(self):
         """Drop the engine's cached programs (packed bf16 weights, captured graphs) -- needed only after weight
@@ -112,18 +118,28 @@ class SliceInterpolationVAE(nn.Module):
 
     @torch.no_grad()
     def encode(self, x):
+        return self._encode(x, self.inference_precision)
+
+    @torch.no_grad()
+    def decode(self, z):
+        return self._decode(z, self.inference_precision)
+
+    def _encode(self, x, precision):
+        """encode() in an explicit precision: the training paths pin 'bf16' whatever `inference_precision` says."""
+        precision = check_precision(precision)
         self._check(x, "encode")
         n, c, d, h, w = x.shape
         if c != self.in_channels:
             raise ValueError(f"encode expects {self.in_channels} input channels, got {c}")
         ctx = Ctx.get(x.device)
         with ctx.scope():
-            key = ("enc", ctx.device.index, n, d, h, w, float(self.scaling_factor))
-            prog = cached_program(self, key, lambda: VAEEncodeProgram(ctx, self, n, d, h, w))
+            key = ("enc", ctx.device.index, n, d, h, w, float(self.scaling_factor), precision)
+            cls = VAEEncodeProgramF32 if precision == "fp32" else VAEEncodeProgram
+            prog = cached_program(self, key, lambda: cls(ctx, self, n, d, h, w))
             return prog(x)
 
-    @torch.no_grad()
-    def decode(self, z):
+    def _decode(self, z, precision):
+        precision = check_precision(precision)
         self._check(z, "decode")
         n, c, d, h, w = z.shape
         if c != self.latent_dim:
@@ -132,6 +148,8 @@ class SliceInterpolationVAE(nn.Module):
         comm = getattr(self, "depth_shard_comm", None)
         with ctx.scope():
             if comm is not None and comm.world > 1:
+                if precision != "bf16":
+                    raise CtsiError("the fp32 inference mode does not support depth sharding (vae.depth_shard_comm)")
                 from .parallel import ShardSpec
                 spec = ShardSpec(comm.rank, comm.world, comm, d)
                 key = ("dec-shard", ctx.device.index, 1, d, h, w, comm.rank, comm.world, float(self.scaling_factor))
@@ -140,8 +158,9 @@ class SliceInterpolationVAE(nn.Module):
                 # a depth-sharded program holds one volume: a batch is decoded volume by volume
                 return torch.cat([prog(z[i:i + 1]) for i in range(n)], dim=0)
             else:
-                key = ("dec", ctx.device.index, n, d, h, w, float(self.scaling_factor))
-                prog = cached_program(self, key, lambda: VAEDecodeProgram(ctx, self, n, d, h, w))
+                key = ("dec", ctx.device.index, n, d, h, w, float(self.scaling_factor), precision)
+                cls = VAEDecodeProgramF32 if precision == "fp32" else VAEDecodeProgram
+                prog = cached_program(self, key, lambda: cls(ctx, self, n, d, h, w))
             return prog(z)
 
     def encode_with_posterior(self, x):
