@@ -443,6 +443,18 @@ int ctsi_ddim_step_f32(float* z, const float* eps, const float* noise, float* zi
 int ctsi_ddpm_step_f32(float* z, const float* eps, const float* noise, float* zin, int c_total, int c_off, const float* coef,
                        const int* step_ptr, int n, int c, int d, int h, int w, void* stream);
 
+/* DPM-Solver++(2M) update (multistep, data prediction; csrc/multistep.hip).  The arguments of ctsi_ddim_step /
+ * ctsi_ddim_step_f32 without `noise` (the solver is deterministic), plus x0_prev: a persistent fp32 NDHWC buffer of z's
+ * shape, allocated zeroed, that holds the previous step's data prediction; it is read and then overwritten with this
+ * step's.  Row coef[*step_ptr] = {1/alpha_i, sigma_i/alpha_i, a_i, b_i, c_i, 0, 0, 0}:
+ *   x0_i = clamp(nan_to_num(z_i/alpha_i - (sigma_i/alpha_i) eps_i), -10, 10),  z_{i+1} = a_i z_i + b_i x0_i + c_i x0_prev.
+ * Writes z, x0_prev and the U-Net input slice (bf16 / fp32, channels [c_off, c_off+c) of c_total).  nonfinite as for
+ * ctsi_ddim_step.  Capture-safe: no allocation, no synchronisation.                                                    */
+int ctsi_dpm_step(float* z, const float* eps, float* x0_prev, void* zin_bf16, int c_total, int c_off, const float* coef,
+                  const int* step_ptr, int n, int c, int d, int h, int w, int* nonfinite, void* stream);
+int ctsi_dpm_step_f32(float* z, const float* eps, float* x0_prev, float* zin, int c_total, int c_off, const float* coef,
+                      const int* step_ptr, int n, int c, int d, int h, int w, int* nonfinite, void* stream);
+
 /* hipGraph helpers (one captured graph per denoising step) -------------------------------- */
 typedef struct ctsi_graph ctsi_graph;
 int ctsi_graph_begin_capture(void* stream);

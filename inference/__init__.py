@@ -4,5 +4,6 @@ import importlib as _il
 _pkg = _il.import_module("video-to-video-diffusion_amd")
 DDIMSampler = _pkg.DDIMSampler
 DDPMSampler = _pkg.DDPMSampler
+DPMSolverSampler = _pkg.DPMSolverSampler   # additive: DPM-Solver++(2M), not in the reference
 
-__all__ = ['DDIMSampler', 'DDPMSampler']
+__all__ = ['DDIMSampler', 'DDPMSampler', 'DPMSolverSampler']

@@ -1196,7 +1196,7 @@ class UNetProgram(Program):
         return out
 
     def add_sampler_step(self, kind: str, with_noise: bool):
-        """Append the DDIM/DDPM update and the step-counter increment (done once, before capture)."""
+        """Append the DDIM/DDPM/DPM-Solver++ update and the step-counter increment (done once, before capture)."""
         lib, sptr = self.lib, self.ctx.sptr
         n, L, d, h, w = self.n, self.L, self.d, self.h, self.w
         if with_noise and self.noise is None:
@@ -1207,11 +1207,17 @@ class UNetProgram(Program):
         # x {NaN, Inf}; the two extra rows = initial noise and conditioning (sampler.py:268-275).  Read once per sample().
         self.nonfinite = self.persistent((self.max_rows + 2, 6), torch.int32, zero=True)
         nfp = _ptr(self.nonfinite)
+        if kind == "dpmpp":
+            # the multistep history x0_{i-1} (fp32 NDHWC, zeroed: ctsi_dpm_step only ever stores finite values in it)
+            self.x0_prev = self.persistent((n, d, h, w, L), torch.float32, zero=True)
+            x0p = _ptr(self.x0_prev)
 
         xin = self.xin
 
         def run_step():
-            if kind == "ddim":
+            if kind == "dpmpp":
+                lib.dpm_step(zp, ep, x0p, xp, 2 * L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
+            elif kind == "ddim":
                 lib.ddim_step(zp, ep, npz, xp, 2 * L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
             else:
                 lib.ddpm_step(zp, ep, npz, xp, 2 * L, 0, cp, sp, n, L, d, h, w, sptr)
@@ -1220,7 +1226,8 @@ class UNetProgram(Program):
         def run_adv():
             lib.step_advance(sp, sptr)
 
-        self._emit(run_step, "sampler.step", nbytes=(4 + 4 + 4 + 2 + (4 if with_noise else 0)) * float(n * L * d * h * w))
+        step_bytes = (4 + 4 + 4 + 2 + (4 if with_noise else 0) + (8 if kind == "dpmpp" else 0)) * float(n * L * d * h * w)
+        self._emit(run_step, "sampler.step", nbytes=step_bytes)
         self._emit(run_adv, "sampler.advance")
         self.sampler_kind = (kind, with_noise)
 

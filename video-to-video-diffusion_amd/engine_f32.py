@@ -10,7 +10,7 @@ capture and launch machinery (one captured hipGraph per sampler step); only the 
   GroupNorm     ctsi_gn_colsum_f32 / conv column sums -> ctsi_gn_finalize (fp64) -> ctsi_gn_apply_f32
   attention     fast mode only: ctsi_attn_depthsum_f32 / _normsum_f32, the folded (proj_out . W_v) matrix (fp64 product,
                 rounded once) as one fp32 1x1x1 conv, ctsi_attn_broadcast_add_f32
-  sampler       ctsi_ddim_step_f32 / ctsi_ddpm_step_f32 (the U-Net's z input written in fp32)
+  sampler       ctsi_ddim_step_f32 / ctsi_ddpm_step_f32 / ctsi_dpm_step_f32 (the U-Net's z input written in fp32)
 
 Not supported here (CtsiError): depth sharding, attention_mode='exact', training.  There is no torch conv, MIOpen or BLAS
 call on this path: torch allocates and copies.
@@ -296,9 +296,14 @@ class UNetProgramF32(_F32Ops, UNetProgram):
         npz = _ptr(self.noise if with_noise else None)
         self.nonfinite = self.persistent((self.max_rows + 2, 6), torch.int32, zero=True)
         nfp = _ptr(self.nonfinite)
+        if kind == "dpmpp":
+            self.x0_prev = self.persistent((n, d, h, w, L), torch.float32, zero=True)
+            x0p = _ptr(self.x0_prev)
 
         def run_step():
-            if kind == "ddim":
+            if kind == "dpmpp":
+                lib.dpm_step_f32(zp, ep, x0p, xp, L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
+            elif kind == "ddim":
                 lib.ddim_step_f32(zp, ep, npz, xp, L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
             else:
                 lib.ddpm_step_f32(zp, ep, npz, xp, L, 0, cp, sp, n, L, d, h, w, sptr)
@@ -306,7 +311,8 @@ class UNetProgramF32(_F32Ops, UNetProgram):
         def run_adv():
             lib.step_advance(sp, sptr)
 
-        self._emit(run_step, "sampler.step", nbytes=(4 + 4 + 4 + 4 + (4 if with_noise else 0)) * float(n * L * d * h * w))
+        step_bytes = (4 + 4 + 4 + 4 + (4 if with_noise else 0) + (8 if kind == "dpmpp" else 0)) * float(n * L * d * h * w)
+        self._emit(run_step, "sampler.step", nbytes=step_bytes)
         self._emit(run_adv, "sampler.advance")
         self.sampler_kind = (kind, with_noise)
 

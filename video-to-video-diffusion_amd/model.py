@@ -123,6 +123,8 @@ class VideoToVideoDiffusion(nn.Module):
         encode -> trilinear depth upsample of the conditioning -> DDIM/DDPM -> decode, with the
         reference's nan_to_num guards applied unconditionally on device (model.py:230-343).
         `guidance_scale` is accepted and ignored, as in the reference.
+        `sampler` also accepts 'dpmpp_2m' (additive): DPM-Solver++(2M) with `num_inference_steps` steps
+        (sampler.DPMSolverSampler), e.g. 20 steps in place of DDIM-50.
         `precision` (additive, default None = the models' `inference_precision` attributes): 'bf16' or 'fp32' for this
         call only; the attributes are restored afterwards."""
         if precision is not None:
@@ -133,7 +135,7 @@ class VideoToVideoDiffusion(nn.Module):
                 return self.generate(v_in, sampler, num_inference_steps, guidance_scale, target_depth, noise_fn)
             finally:
                 self.unet.inference_precision, self.vae.inference_precision = saved
-        if sampler not in ('ddpm', 'ddim'):
+        if sampler not in ('ddpm', 'ddim', 'dpmpp_2m'):
             raise ValueError(f"Unknown sampler: {sampler}")
         if not v_in.is_cuda:
             raise CtsiError("generate runs on the HIP engine: move the input to a ROCm device")
@@ -154,6 +156,10 @@ class VideoToVideoDiffusion(nn.Module):
         if sampler == 'ddpm':
             z_0 = self.diffusion.p_sample_loop(self.unet, latent_shape, z_cond, device, progress=True,
                                                noise_fn=noise_fn)
+        elif sampler == 'dpmpp_2m':
+            from .sampler import DPMSolverSampler
+            z_0 = DPMSolverSampler(self.diffusion, self.unet, order=2).sample(latent_shape, z_cond, num_inference_steps,
+                                                                              device, noise_fn=noise_fn)
         else:
             from .sampler import DDIMSampler
             z_0 = DDIMSampler(self.diffusion, self.unet).sample(latent_shape, z_cond, num_inference_steps,

@@ -1,7 +1,8 @@
-"""DDPM / DDIM samplers (mirror of reference inference/sampler.py) on the HIP engine.
+"""DDPM / DDIM samplers (mirror of reference inference/sampler.py) on the HIP engine, plus DPM-Solver++(2M)
+(DPMSolverSampler, additive: not in the reference).
 
 One denoising step = one replay of a captured hipGraph holding every kernel of a U-Net evaluation,
-the elementwise x_{t-1} update (ctsi_ddim_step / ctsi_ddpm_step) and the increment of the device-side
+the elementwise x_{t-1} update (ctsi_ddim_step / ctsi_ddpm_step / ctsi_dpm_step) and the increment of the device-side
 step counter.  Per-step scalars (timestep embedding rows, update coefficients) come from device
 tables indexed by that counter, so the same graph serves all steps and the host never synchronises
 inside the loop.  The reference's five isnan/isinf host checks per step are folded into the update
@@ -34,7 +35,7 @@ def _is_engine_unet(model) -> bool:
 def _log_nonfinite(kind: str, table: torch.Tensor, steps: int, max_rows: int):
     """What the reference's five NaN/Inf checkpoints log (inference/sampler.py:268-275, 288-292, 307-311, 331-334), from
     the device-side counters the update kernel keeps: one host read after the loop instead of five syncs per step."""
-    if kind != "ddim":
+    if kind not in ("ddim", "dpmpp"):
         return            # the reference's DDPM loop (models/diffusion.py:340-367) has no such checkpoints
     t = table.cpu()
     if not bool(t.any()):
@@ -55,10 +56,10 @@ def _log_nonfinite(kind: str, table: torch.Tensor, steps: int, max_rows: int):
 
 
 def _run_sampler_generic(diffusion, model, shape, conditioning, ctx, z0, *, kind, t_desc, eta, noise_fn, progress,
-                         trajectory):
+                         trajectory, order=2, eps_trajectory=None):
     """Reverse loop over an ARBITRARY `model(z, t, c) -> eps` callable (the reference's samplers accept any,
     inference/sampler.py:211-219): the network evaluation is the caller's (any torch code on the ROCm device), the
-    x_{t-1} update with its guards is the engine's ctsi_ddim_step / ctsi_ddpm_step.  Not captured: the callable is
+    x_{t-1} update with its guards is the engine's ctsi_ddim_step / ctsi_ddpm_step / ctsi_dpm_step.  Not captured: the callable is
     opaque.  The engine's own UNet3D takes the hipGraph path in run_sampler instead."""
     import ctypes as C
     lib, sptr = ctx.lib, ctx.sptr
@@ -66,10 +67,10 @@ def _run_sampler_generic(diffusion, model, shape, conditioning, ctx, z0, *, kind
     steps = len(t_desc)
     with_noise = (kind == "ddpm") or eta > 0
     dev = ctx.device
-    coef = (ddim_coef_rows(diffusion.alphas_cumprod, t_desc, eta) if kind == "ddim"
-            else diffusion.ddpm_coef_rows(t_desc)).to(dev, torch.float32).contiguous()
+    coef = _coef_rows(diffusion, kind, t_desc, eta, order).to(dev, torch.float32).contiguous()
     z_nd = torch.empty((n, d, h, w, L), dtype=torch.float32, device=dev)
     eps_nd = torch.empty_like(z_nd)
+    x0_prev = torch.zeros_like(z_nd) if kind == "dpmpp" else None
     step_ptr = torch.zeros(1, dtype=torch.int32, device=dev)
     nonfinite = torch.zeros((steps + 2, 6), dtype=torch.int32, device=dev)
     cond = conditioning.to(dev)
@@ -88,6 +89,8 @@ def _run_sampler_generic(diffusion, model, shape, conditioning, ctx, z0, *, kind
             raise CtsiError("the model callable must return a ROCm tensor of the latent's shape "
                             f"{tuple(shape)}, got {type(eps).__name__} {tuple(getattr(eps, 'shape', ()))}")
         eps = eps.detach().to(torch.float32).contiguous()
+        if eps_trajectory is not None:
+            eps_trajectory.append(eps.clone())
         noise = None
         if with_noise:
             noise = (noise_fn(i, tuple(shape)) if noise_fn is not None else torch.randn(tuple(shape), device=dev))
@@ -95,7 +98,10 @@ def _run_sampler_generic(diffusion, model, shape, conditioning, ctx, z0, *, kind
         with ctx.scope():
             lib.ncdhw_f32_to_ndhwc_f32(_ptr(z), _ptr(z_nd), n, L, d, h, w, sptr)
             lib.ncdhw_f32_to_ndhwc_f32(_ptr(eps), _ptr(eps_nd), n, L, d, h, w, sptr)
-            if kind == "ddim":
+            if kind == "dpmpp":
+                lib.dpm_step(_ptr(z_nd), _ptr(eps_nd), _ptr(x0_prev), None, 0, 0, _ptr(coef), _ptr(step_ptr), n, L, d, h,
+                             w, _ptr(nonfinite), sptr)
+            elif kind == "ddim":
                 lib.ddim_step(_ptr(z_nd), _ptr(eps_nd), _ptr(noise), None, 0, 0, _ptr(coef), _ptr(step_ptr), n, L, d, h, w,
                               _ptr(nonfinite), sptr)
             else:
@@ -128,14 +134,63 @@ def ddim_coef_rows(alphas_cumprod: torch.Tensor, timesteps: Sequence[int], eta: 
     return rows
 
 
+def dpm_coef_rows(alphas_cumprod: torch.Tensor, t_desc: Sequence[int], order: int = 2) -> torch.Tensor:
+    """Coefficient rows for ctsi_dpm_step: multistep DPM-Solver++ in data prediction (Lu et al. 2022, "DPM-Solver++",
+    Algorithm 2) on the timestep list `t_desc`, the last target being abar = 1 as in the reference DDIM.
+
+    With alpha = sqrt(abar), sigma = sqrt(1 - abar), lambda = log alpha - log sigma and h_i = lambda_{i+1} - lambda_i,
+    step i maps z_i to z_{i+1} = a_i z_i + b_i x0_i + c_i x0_{i-1}, x0_i = clamp(nan_to_num((z_i - sigma_i eps_i) /
+    alpha_i), -10, 10):
+      first order (step 0, order=1):  a = sigma_{i+1}/sigma_i,  b = alpha_{i+1} (1 - e^-h),  c = 0  (= DDIM, eta 0)
+      second order:  r = h_{i-1}/h_i,  b = alpha_{i+1} (1 - e^-h) (1 + 1/2r),  c = -alpha_{i+1} (1 - e^-h) / 2r
+      final step (sigma = 0, lambda = +inf): first order, exactly a = 0, b = 1, c = 0.
+    Rows [1/alpha_i, sigma_i/alpha_i, a_i, b_i, c_i, 0, 0, 0], computed in float64 and rounded once to fp32."""
+    if order not in (1, 2):
+        raise ValueError(f"DPM-Solver++ order must be 1 or 2, got {order}")
+    ac = alphas_cumprod.detach().double().cpu().numpy()
+    n = len(t_desc)
+    abar = np.array([ac[int(t)] for t in t_desc], dtype=np.float64)
+    alpha, sigma = np.sqrt(abar), np.sqrt(1.0 - abar)
+    lam = np.log(alpha) - np.log(sigma)
+    rows = np.zeros((n, 8), dtype=np.float64)
+    rows[:, 0] = 1.0 / alpha
+    rows[:, 1] = sigma / alpha
+    h_prev = None
+    for i in range(n):
+        if i == n - 1:
+            rows[i, 2:5] = (0.0, 1.0, 0.0)
+            break
+        h = lam[i + 1] - lam[i]
+        phi = -np.expm1(-h)                         # 1 - e^{-h}
+        rows[i, 2] = sigma[i + 1] / sigma[i]
+        if order == 1 or h_prev is None:
+            rows[i, 3] = alpha[i + 1] * phi
+        else:
+            r = h_prev / h
+            rows[i, 3] = alpha[i + 1] * phi * (1.0 + 0.5 / r)
+            rows[i, 4] = -alpha[i + 1] * phi * (0.5 / r)
+        h_prev = h
+    return torch.from_numpy(rows).to(torch.float32)
+
+
+def _coef_rows(diffusion, kind: str, t_desc: Sequence[int], eta: float, order: int) -> torch.Tensor:
+    if kind == "dpmpp":
+        return dpm_coef_rows(diffusion.alphas_cumprod, t_desc, order)
+    if kind == "ddim":
+        return ddim_coef_rows(diffusion.alphas_cumprod, t_desc, eta)
+    return diffusion.ddpm_coef_rows(t_desc)
+
+
 def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, t_desc, eta, noise_fn, comm,
-                        trajectory=None):
+                        trajectory=None, order=2):
     """Depth-sharded reverse loop: this process owns depth slab `comm.rank` of the volume (parallel.RcclComm: RCCL
     issued by libctsi on the engine stream; parallel.DistComm under the gloo tests).  Every rank passes the full
     conditioning / initial noise and gets the full result back (all-gather along depth).  A batch runs volume by
     volume through the one-volume sharded program (every rank holds 1/world of ONE volume at a time).
     With a capture-safe transport and CTSI_SHARD_CAPTURE=1 the step -- kernels AND collectives -- is replayed as one
-    hipGraph, like the single-GPU step."""
+    hipGraph, like the single-GPU step.
+    DPM-Solver++ ('dpmpp'): the update is elementwise over the rank's own slab (its history buffer too), and step 0's
+    row (c = 0) overwrites that history, so volume b + 1 starts clean."""
     import os
     from .engine import cached_program
     from .parallel import ShardSpec
@@ -148,6 +203,8 @@ def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, 
     outs, trajs = [], [[] for _ in range(steps)]
     with ctx.scope():
         key = ("sampler-shard", ctx.device.index, 1, d, h, w, comm.rank, comm.world, kind, with_noise)
+        if kind == "dpmpp":
+            key += (order,)
 
         def build():
             prog = UNetProgram(ctx, unet, 1, dl, h, w, diffusion.timesteps + 1, "fast", shard=spec)
@@ -155,8 +212,7 @@ def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, 
             return prog
 
         prog = cached_program(unet, key, build)
-        coef = (ddim_coef_rows(diffusion.alphas_cumprod, t_desc, eta) if kind == "ddim"
-                else diffusion.ddpm_coef_rows(t_desc))
+        coef = _coef_rows(diffusion, kind, t_desc, eta, order)
         lo = spec.depth_start
         noises = {}
         for b in range(n):
@@ -185,8 +241,9 @@ def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, 
 
 def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_desc: Sequence[int],
                 progress: bool, eta: float = 0.0, noise_fn=None, z_init: Optional[torch.Tensor] = None,
-                trajectory: Optional[list] = None):
-    """Shared reverse loop.  kind: 'ddim' | 'ddpm'; t_desc: descending timestep list."""
+                trajectory: Optional[list] = None, order: int = 2, eps_trajectory: Optional[list] = None):
+    """Shared reverse loop.  kind: 'ddim' | 'ddpm' | 'dpmpp' (DPM-Solver++ of `order` 1 or 2); t_desc: descending
+    timestep list.  `eps_trajectory` (unsharded runs only): receives the noise prediction of every step, fp32 NCDHW."""
     if not _is_engine_unet(model) and not callable(model):
         raise CtsiError(f"the samplers need a model(z, t, c) callable; got {type(model).__name__}")
     unet = model
@@ -205,17 +262,22 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
         z0 = torch.randn(tuple(shape), device=ctx.device)
     if not _is_engine_unet(model):
         return _run_sampler_generic(diffusion, model, shape, conditioning, ctx, z0, kind=kind, t_desc=t_desc, eta=eta,
-                                    noise_fn=noise_fn, progress=progress, trajectory=trajectory)
+                                    noise_fn=noise_fn, progress=progress, trajectory=trajectory, order=order,
+                                    eps_trajectory=eps_trajectory)
     precision = check_precision(getattr(unet, "inference_precision", "bf16"))
     comm = getattr(unet, "depth_shard_comm", None)
     if comm is not None and comm.world > 1:
         if precision != "bf16":
             raise CtsiError("the fp32 inference mode does not support depth sharding (unet.depth_shard_comm); "
                             "set inference_precision='bf16' or drop the communicator")
+        if eps_trajectory is not None:
+            raise CtsiError("eps_trajectory is not recorded by the depth-sharded sampler")
         return run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, kind=kind, t_desc=t_desc, eta=eta,
-                                   noise_fn=noise_fn, comm=comm, trajectory=trajectory)
+                                   noise_fn=noise_fn, comm=comm, trajectory=trajectory, order=order)
     with ctx.scope():
         key = ("sampler", ctx.device.index, n, d, h, w, max_rows, kind, with_noise, unet.attention_mode, precision)
+        if kind == "dpmpp":
+            key += (order,)
         from .engine import cached_program
 
         def build():
@@ -235,10 +297,7 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
         cnd = conditioning.detach().to(ctx.device, torch.float32).contiguous()
         ctx.lib.count_nonfinite_f32(_ptr(cnd), cnd.numel(), 0, C.c_void_p(nf_tail + 24), ctx.sptr)
         cnd.record_stream(ctx.stream)
-        if kind == "ddim":
-            coef = ddim_coef_rows(diffusion.alphas_cumprod, t_desc, eta)
-        else:
-            coef = diffusion.ddpm_coef_rows(t_desc)
+        coef = _coef_rows(diffusion, kind, t_desc, eta, order)
         t_rows = [int(t) for t in t_desc for _ in range(n)]
         prog.set_schedule(t_rows, coef.to(ctx.device))
         if prog.graph is None:
@@ -257,6 +316,8 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
             prog.launch()
             if trajectory is not None:
                 trajectory.append(prog.z_ncdhw())
+            if eps_trajectory is not None:
+                eps_trajectory.append(prog.eps_ncdhw())
         out = prog.z_ncdhw()
         _log_nonfinite(kind, prog.nonfinite, steps, prog.max_rows)     # (one host read: the loop itself never synchronises)
         check_device_errors(ctx)
@@ -334,6 +395,51 @@ class DDIMSampler:
         return _stitched(self, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress,
                          lambda shp, cond: self.sample(shp, cond, num_inference_steps, device, eta=eta,
                                                        progress=False),
+                         batched_fn=batched, window_batch=window_batch, dp_group=dp_group)
+
+    def _create_gaussian_weight(self, d, h, w):
+        return gaussian_weight(d, h, w)
+
+
+class DPMSolverSampler:
+    """DPM-Solver++(2M) (Lu et al. 2022): the training-free multistep ODE solver in data prediction, on the DDIM
+    timestep list (N steps = the same N + 1 U-Net evaluations as DDIM-N).  Additive: the reference has no such sampler.
+    order=1 is the DDIM (eta = 0) update written in data-prediction form.  Deterministic: no noise is drawn after the
+    initial latent."""
+
+    def __init__(self, diffusion, model, order=2):
+        if order not in (1, 2):
+            raise ValueError(f"DPM-Solver++ order must be 1 or 2, got {order}")
+        self.diffusion = diffusion
+        self.model = model
+        self.order = int(order)
+        self.timesteps = diffusion.timesteps
+
+    def _get_timesteps(self, num_inference_steps):
+        return DDIMSampler._get_timesteps(self, num_inference_steps)
+
+    @torch.no_grad()
+    def sample(self, shape, conditioning, num_inference_steps, device, progress=True, noise_fn=None, trajectory=None,
+               z_init=None):
+        t_desc = [int(t) for t in self._get_timesteps(num_inference_steps)]
+        return run_sampler(self.diffusion, self.model, shape, conditioning, device, kind="dpmpp", t_desc=t_desc,
+                           progress=progress, noise_fn=noise_fn, trajectory=trajectory, z_init=z_init,
+                           order=self.order)
+
+    @torch.no_grad()
+    def sample_with_stitching(self, v_thick_full, vae, num_inference_steps=20, patch_size=(8, 192, 192),
+                              target_patch_size=(48, 192, 192), stride=(4, 96, 96), device='cuda', progress=True,
+                              window_batch=None, dp_group=None):
+        """DDIMSampler.sample_with_stitching without `eta`: the same windows, blend, `window_batch` and `dp_group`
+        behaviour (the solver is deterministic, so windows are always batchable)."""
+        batched = None
+        if window_batch is None:
+            window_batch = 0
+        if window_batch != 1:
+            batched = lambda shp, cond, z_init: self.sample(shp, cond, num_inference_steps, device, progress=False,
+                                                            z_init=z_init)
+        return _stitched(self, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress,
+                         lambda shp, cond: self.sample(shp, cond, num_inference_steps, device, progress=False),
                          batched_fn=batched, window_batch=window_batch, dp_group=dp_group)
 
     def _create_gaussian_weight(self, d, h, w):
