@@ -212,6 +212,13 @@ int ctsi_time_embed_fwd(const int* t_rows, int rows, int dim, int time_dim, cons
                         const float* b_all, int total_out, float* scratch, float* tbias_out,
                         void* stream);
 
+/* ctsi_time_embed_fwd with fractional timesteps: `t_rows` holds `rows` fp32 values (the EDM sampler's t(sigma),
+ * UNet3D.forward with a non-integer t).  An integer-valued row gives the bit-identical embedding of the int entry. */
+int ctsi_time_embed_fwd_tf(const float* t_rows, int rows, int dim, int time_dim, const float* w1,
+                           const float* b1, const float* w2, const float* b2, const float* w_all,
+                           const float* b_all, int total_out, float* scratch, float* tbias_out,
+                           void* stream);
+
 /* trilinear depth upsample (F.interpolate(..., 'trilinear', align_corners=False) with h, w
  * unchanged: models/model.py:284-289, 191-196).  fp32 NCDHW in -> bf16 NDHWC channel slice
  * [c_off, c_off+c) of a c_total-channel tensor, plus an optional fp32 NCDHW copy.            */
@@ -454,6 +461,21 @@ int ctsi_dpm_step(float* z, const float* eps, float* x0_prev, void* zin_bf16, in
                   const int* step_ptr, int n, int c, int d, int h, int w, int* nonfinite, void* stream);
 int ctsi_dpm_step_f32(float* z, const float* eps, float* x0_prev, float* zin, int c_total, int c_off, const float* coef,
                       const int* step_ptr, int n, int c, int d, int h, int w, int* nonfinite, void* stream);
+
+/* EDM Heun / Euler update (Karras et al. 2022, Algorithm 2; csrc/multistep.hip), one call per U-Net evaluation.  z
+ * holds zhat, the VP latent of the churned state; d1: a persistent fp32 NDHWC buffer of z's shape, allocated zeroed, that
+ * holds the predictor's data prediction; noise: fp32 NCDHW churn noise of the next step, or NULL (read only by rows with
+ * c7 != 0).  Row coef[*step_ptr] = {c0, c1, c2, kind, c4, c5, c6, c7} (sampler.heun_coef_rows):
+ *   D = clamp(nan_to_num(c0 z + c1 d1 - c2 eps), -10, 10)
+ *   kind 0 (predictor): d1 = D, zin = c4 z + c5 D;   kind 1 (closing): z = zin = c4 z + c5 D + c6 d1 + c7 noise.
+ * zin (the U-Net input slice, bf16 / fp32, channels [c_off, c_off+c) of c_total) is required: a predictor row writes
+ * the corrector's input there only.  nonfinite as for ctsi_dpm_step.  Capture-safe: no allocation, no synchronisation. */
+int ctsi_heun_step(float* z, const float* eps, float* d1, const float* noise, void* zin_bf16, int c_total, int c_off,
+                   const float* coef, const int* step_ptr, int n, int c, int d, int h, int w, int* nonfinite,
+                   void* stream);
+int ctsi_heun_step_f32(float* z, const float* eps, float* d1, const float* noise, float* zin, int c_total, int c_off,
+                       const float* coef, const int* step_ptr, int n, int c, int d, int h, int w, int* nonfinite,
+                       void* stream);
 
 /* hipGraph helpers (one captured graph per denoising step) -------------------------------- */
 typedef struct ctsi_graph ctsi_graph;

@@ -10,7 +10,7 @@ from .vae import SliceInterpolationVAE, VideoVAE  # noqa: F401
 from .unet3d import UNet3D  # noqa: F401
 from .diffusion import GaussianDiffusion  # noqa: F401
 from .model import VideoToVideoDiffusion  # noqa: F401
-from .sampler import DDIMSampler, DDPMSampler, DPMSolverSampler, EDMSampler  # noqa: F401
+from .sampler import DDIMSampler, DDPMSampler, DPMSolverSampler, EDMSampler, HeunSampler  # noqa: F401
 from .generate import generate_batch, interpolate_videos  # noqa: F401
 from .optim import FusedAdam, FusedAdamW  # noqa: F401
 from . import parallel  # noqa: F401,E402

@@ -141,8 +141,11 @@ extern "C" int ctsi_trilinear_depth_fwd(const float* src, void* dst_bf16, int n,
 // rows = (steps x batch) timestep values.  Three launches:
 //   (1) sincos + Linear1 + SiLU   (2) Linear2   (3) all per-ResBlock Linear(SiLU(temb)) stacked.
 // One wave per output feature; the wave keeps its weight row in registers and walks the rows.
+// TT = int (integer timesteps) or float (fractional ones, ctsi_time_embed_fwd_tf): an integer-valued float row converts
+// to the same fp32 argument as the int row, so both entries give bit-identical embeddings there.
+template <typename TT>
 __global__ void __launch_bounds__(256)
-time_sincos_kernel(const int* __restrict__ t_rows, int rows, int dim, float* __restrict__ out) {
+time_sincos_kernel(const TT* __restrict__ t_rows, int rows, int dim, float* __restrict__ out) {
     const int half = dim / 2;
     const float step = logf(10000.0f) / (float)(half - 1);
     for (int e = blockIdx.x * 256 + threadIdx.x; e < rows * half; e += gridDim.x * 256) {
@@ -191,10 +194,10 @@ time_linear_kernel(const float* __restrict__ in, int rows, int in_dim, const flo
     }
 }
 
-extern "C" int ctsi_time_embed_fwd(const int* t_rows, int rows, int dim, int time_dim, const float* w1,
-                                   const float* b1, const float* w2, const float* b2, const float* w_all,
-                                   const float* b_all, int total_out, float* scratch, float* tbias_out,
-                                   void* stream) {
+template <typename TT>
+static int time_embed_fwd(const TT* t_rows, int rows, int dim, int time_dim, const float* w1, const float* b1,
+                          const float* w2, const float* b2, const float* w_all, const float* b_all, int total_out,
+                          float* scratch, float* tbias_out, void* stream) {
     CTSI_CHECK_ARG(t_rows && w1 && b1 && w2 && b2 && scratch, "ctsi_time_embed_fwd: null argument");
     CTSI_CHECK_ARG(rows > 0 && dim >= 4 && dim % 2 == 0 && dim <= 2048 && time_dim > 0 && time_dim <= 2048,
                    "ctsi_time_embed_fwd: unsupported sizes dim=%d time_dim=%d", dim, time_dim);
@@ -203,7 +206,7 @@ extern "C" int ctsi_time_embed_fwd(const int* t_rows, int rows, int dim, int tim
     float* hidden = scratch + (long long)rows * dim;   // rows*time_dim
     float* temb = hidden + (long long)rows * time_dim; // rows*time_dim
     int blocks = (rows * (dim / 2) + 255) / 256;
-    hipLaunchKernelGGL(time_sincos_kernel, dim3(blocks), dim3(256), 0, st, t_rows, rows, dim, sincos);
+    hipLaunchKernelGGL(time_sincos_kernel<TT>, dim3(blocks), dim3(256), 0, st, t_rows, rows, dim, sincos);
     CTSI_LAUNCH_CHECK();
     hipLaunchKernelGGL(time_linear_kernel, dim3((time_dim + 3) / 4), dim3(256), 0, st, sincos, rows, dim, w1, b1,
                        time_dim, hidden, 0, 1);
@@ -218,6 +221,23 @@ extern "C" int ctsi_time_embed_fwd(const int* t_rows, int rows, int dim, int tim
         CTSI_LAUNCH_CHECK();
     }
     return CTSI_OK;
+}
+
+extern "C" int ctsi_time_embed_fwd(const int* t_rows, int rows, int dim, int time_dim, const float* w1,
+                                   const float* b1, const float* w2, const float* b2, const float* w_all,
+                                   const float* b_all, int total_out, float* scratch, float* tbias_out,
+                                   void* stream) {
+    return time_embed_fwd(t_rows, rows, dim, time_dim, w1, b1, w2, b2, w_all, b_all, total_out, scratch, tbias_out,
+                          stream);
+}
+
+// fractional timesteps (the EDM sampler's t(sigma), UNet3D.forward with a non-integer t): fp32 rows
+extern "C" int ctsi_time_embed_fwd_tf(const float* t_rows, int rows, int dim, int time_dim, const float* w1,
+                                      const float* b1, const float* w2, const float* b2, const float* w_all,
+                                      const float* b_all, int total_out, float* scratch, float* tbias_out,
+                                      void* stream) {
+    return time_embed_fwd(t_rows, rows, dim, time_dim, w1, b1, w2, b2, w_all, b_all, total_out, scratch, tbias_out,
+                          stream);
 }
 
 // Training variant: scratch keeps the PRE-activation of the first Linear (the backward needs SiLU' of it);
@@ -235,7 +255,7 @@ extern "C" int ctsi_time_embed_train_fwd(const int* t_rows, int rows, int dim, i
     float* lin1 = scratch + (long long)rows * dim;     // rows*time_dim, pre-activation
     float* temb = lin1 + (long long)rows * time_dim;   // rows*time_dim
     int blocks = (rows * (dim / 2) + 255) / 256;
-    hipLaunchKernelGGL(time_sincos_kernel, dim3(blocks), dim3(256), 0, st, t_rows, rows, dim, sincos);
+    hipLaunchKernelGGL(time_sincos_kernel<int>, dim3(blocks), dim3(256), 0, st, t_rows, rows, dim, sincos);
     CTSI_LAUNCH_CHECK();
     hipLaunchKernelGGL(time_linear_kernel, dim3((time_dim + 3) / 4), dim3(256), 0, st, sincos, rows, dim, w1, b1,
                        time_dim, lin1, 0, 0);

@@ -1059,6 +1059,7 @@ class UNetProgram(Program):
         self.z = self.persistent((n, d, h, w, L), torch.float32, zero=True)
         self.step_ptr = self.persistent((1,), torch.int32, zero=True)
         self.t_rows = self.persistent((max_rows,), torch.int32, zero=True)
+        self.t_rows_f = self.persistent((max_rows,), torch.float32, zero=True)   # fractional timesteps (EDM sampler)
         self.coef = self.persistent((max_rows, 8), torch.float32, zero=True)
         self.noise = None  # fp32 NCDHW, allocated on demand
         self.track_module(unet)
@@ -1164,22 +1165,27 @@ class UNetProgram(Program):
             lib.ncdhw_f32_to_ndhwc_bf16(_ptr(cnd), self.xin.ip, n, L, d, h, w, 2 * L, L, sptr)
             cnd.record_stream(self.ctx.stream)
 
-    def set_schedule(self, t_rows: Sequence[int], coef_rows: Optional[torch.Tensor] = None):
+    def set_schedule(self, t_rows: Sequence[float], coef_rows: Optional[torch.Tensor] = None):
         """Upload the timestep of every (step, sample) row, embed all of them in one go and rewind the
-        device-side step counter."""
+        device-side step counter.  Integer-valued rows take the int32 entry (ctsi_time_embed_fwd); a schedule with any
+        fractional timestep is embedded from fp32 rows (ctsi_time_embed_fwd_tf)."""
         rows = len(t_rows)
         if rows > self.max_rows:
             raise CtsiError(f"schedule needs {rows} rows but the program was built for {self.max_rows}")
         lib, sptr = self.lib, self.ctx.sptr
         self.ensure_fresh()
-        tt = torch.tensor(list(t_rows), dtype=torch.int32)
-        self.t_rows[:rows].copy_(tt, non_blocking=False)
+        vals = list(t_rows)
+        fractional = any(float(v) != int(v) for v in vals)
+        if fractional:
+            self.t_rows_f[:rows].copy_(torch.tensor([float(v) for v in vals], dtype=torch.float32), non_blocking=False)
+        else:
+            self.t_rows[:rows].copy_(torch.tensor([int(v) for v in vals], dtype=torch.int32), non_blocking=False)
         if coef_rows is not None:
             self.coef[:coef_rows.shape[0]].copy_(coef_rows.to(torch.float32))
         self.step_ptr.zero_()
-        lib.time_embed_fwd(_ptr(self.t_rows), rows, self.dim, self.time_dim, _ptr(self.w1), _ptr(self.b1),
-                           _ptr(self.w2), _ptr(self.b2), _ptr(self.w_all), _ptr(self.b_all), self.total_out,
-                           _ptr(self.te_scratch), _ptr(self.tbias), sptr)
+        embed, tp = (lib.time_embed_fwd_tf, self.t_rows_f) if fractional else (lib.time_embed_fwd, self.t_rows)
+        embed(_ptr(tp), rows, self.dim, self.time_dim, _ptr(self.w1), _ptr(self.b1), _ptr(self.w2), _ptr(self.b2),
+              _ptr(self.w_all), _ptr(self.b_all), self.total_out, _ptr(self.te_scratch), _ptr(self.tbias), sptr)
 
     def eps_ncdhw(self) -> torch.Tensor:
         out = torch.empty((self.n, self.L, self.d, self.h, self.w), dtype=torch.float32, device=self.ctx.device)
@@ -1196,7 +1202,8 @@ class UNetProgram(Program):
         return out
 
     def add_sampler_step(self, kind: str, with_noise: bool):
-        """Append the DDIM/DDPM/DPM-Solver++ update and the step-counter increment (done once, before capture)."""
+        """Append the DDIM/DDPM/DPM-Solver++/Heun update and the step-counter increment (done once, before capture).
+        'heun': one update per U-Net evaluation (predictor, corrector or final row); `with_noise` = churn on."""
         lib, sptr = self.lib, self.ctx.sptr
         n, L, d, h, w = self.n, self.L, self.d, self.h, self.w
         if with_noise and self.noise is None:
@@ -1211,11 +1218,17 @@ class UNetProgram(Program):
             # the multistep history x0_{i-1} (fp32 NDHWC, zeroed: ctsi_dpm_step only ever stores finite values in it)
             self.x0_prev = self.persistent((n, d, h, w, L), torch.float32, zero=True)
             x0p = _ptr(self.x0_prev)
+        if kind == "heun":
+            # the predictor's data prediction D1 (fp32 NDHWC, zeroed: ctsi_heun_step only ever stores finite values in it)
+            self.d1 = self.persistent((n, d, h, w, L), torch.float32, zero=True)
+            d1p = _ptr(self.d1)
 
         xin = self.xin
 
         def run_step():
-            if kind == "dpmpp":
+            if kind == "heun":
+                lib.heun_step(zp, ep, d1p, npz, xp, 2 * L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
+            elif kind == "dpmpp":
                 lib.dpm_step(zp, ep, x0p, xp, 2 * L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
             elif kind == "ddim":
                 lib.ddim_step(zp, ep, npz, xp, 2 * L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
@@ -1226,7 +1239,8 @@ class UNetProgram(Program):
         def run_adv():
             lib.step_advance(sp, sptr)
 
-        step_bytes = (4 + 4 + 4 + 2 + (4 if with_noise else 0) + (8 if kind == "dpmpp" else 0)) * float(n * L * d * h * w)
+        step_bytes = (4 + 4 + 4 + 2 + (4 if with_noise else 0) + (8 if kind in ("dpmpp", "heun") else 0)) * float(
+            n * L * d * h * w)
         self._emit(run_step, "sampler.step", nbytes=step_bytes)
         self._emit(run_adv, "sampler.advance")
         self.sampler_kind = (kind, with_noise)

@@ -10,7 +10,8 @@ capture and launch machinery (one captured hipGraph per sampler step); only the 
   GroupNorm     ctsi_gn_colsum_f32 / conv column sums -> ctsi_gn_finalize (fp64) -> ctsi_gn_apply_f32
   attention     fast mode only: ctsi_attn_depthsum_f32 / _normsum_f32, the folded (proj_out . W_v) matrix (fp64 product,
                 rounded once) as one fp32 1x1x1 conv, ctsi_attn_broadcast_add_f32
-  sampler       ctsi_ddim_step_f32 / ctsi_ddpm_step_f32 / ctsi_dpm_step_f32 (the U-Net's z input written in fp32)
+  sampler       ctsi_ddim_step_f32 / ctsi_ddpm_step_f32 / ctsi_dpm_step_f32 / ctsi_heun_step_f32 (the U-Net's z input
+                written in fp32)
 
 Not supported here (CtsiError): depth sharding, attention_mode='exact', training.  There is no torch conv, MIOpen or BLAS
 call on this path: torch allocates and copies.
@@ -299,9 +300,14 @@ class UNetProgramF32(_F32Ops, UNetProgram):
         if kind == "dpmpp":
             self.x0_prev = self.persistent((n, d, h, w, L), torch.float32, zero=True)
             x0p = _ptr(self.x0_prev)
+        if kind == "heun":
+            self.d1 = self.persistent((n, d, h, w, L), torch.float32, zero=True)
+            d1p = _ptr(self.d1)
 
         def run_step():
-            if kind == "dpmpp":
+            if kind == "heun":
+                lib.heun_step_f32(zp, ep, d1p, npz, xp, L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
+            elif kind == "dpmpp":
                 lib.dpm_step_f32(zp, ep, x0p, xp, L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
             elif kind == "ddim":
                 lib.ddim_step_f32(zp, ep, npz, xp, L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
@@ -311,7 +317,8 @@ class UNetProgramF32(_F32Ops, UNetProgram):
         def run_adv():
             lib.step_advance(sp, sptr)
 
-        step_bytes = (4 + 4 + 4 + 4 + (4 if with_noise else 0) + (8 if kind == "dpmpp" else 0)) * float(n * L * d * h * w)
+        step_bytes = (4 + 4 + 4 + 4 + (4 if with_noise else 0) + (8 if kind in ("dpmpp", "heun") else 0)) * float(
+            n * L * d * h * w)
         self._emit(run_step, "sampler.step", nbytes=step_bytes)
         self._emit(run_adv, "sampler.advance")
         self.sampler_kind = (kind, with_noise)

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import torch
 
-from .sampler import DDIMSampler, DDPMSampler, DPMSolverSampler
+from .sampler import DDIMSampler, DDPMSampler, DPMSolverSampler, HeunSampler
 
 
 def _sample(model, z_cond, sampler_type, num_inference_steps, device, progress, noise_fn=None):
@@ -17,6 +17,9 @@ def _sample(model, z_cond, sampler_type, num_inference_steps, device, progress, 
     if sampler_type == 'dpmpp_2m':
         return DPMSolverSampler(model.diffusion, model.unet, order=2).sample(z_cond.shape, z_cond, num_inference_steps,
                                                                              device, progress=progress, noise_fn=noise_fn)
+    if sampler_type == 'heun':
+        return HeunSampler(model.diffusion, model.unet).sample(z_cond.shape, z_cond, num_inference_steps, device,
+                                                               progress=progress, noise_fn=noise_fn)
     raise ValueError(f"Unknown sampler type: {sampler_type}")
 
 
@@ -24,8 +27,8 @@ def _sample(model, z_cond, sampler_type, num_inference_steps, device, progress, 
 def generate_batch(model, input_videos, sampler_type='ddim', num_inference_steps=20, device='cuda',
                    noise_fn=None):
     """encode -> sample at the input's latent shape (no depth change) -> decode (generate.py:98-155).
-    sampler_type: 'ddim', 'ddpm' or (additive) 'dpmpp_2m'."""
-    if sampler_type not in ('ddim', 'ddpm', 'dpmpp_2m'):
+    sampler_type: 'ddim', 'ddpm' or (additive) 'dpmpp_2m' or 'heun'."""
+    if sampler_type not in ('ddim', 'ddpm', 'dpmpp_2m', 'heun'):
         raise ValueError(f"Unknown sampler type: {sampler_type}")
     model.eval()
     model.to(device)

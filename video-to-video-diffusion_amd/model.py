@@ -124,7 +124,8 @@ class VideoToVideoDiffusion(nn.Module):
         reference's nan_to_num guards applied unconditionally on device (model.py:230-343).
         `guidance_scale` is accepted and ignored, as in the reference.
         `sampler` also accepts 'dpmpp_2m' (additive): DPM-Solver++(2M) with `num_inference_steps` steps
-        (sampler.DPMSolverSampler), e.g. 20 steps in place of DDIM-50.
+        (sampler.DPMSolverSampler), e.g. 20 steps in place of DDIM-50, and 'heun' (additive): EDM Heun with
+        `num_inference_steps` steps on Karras sigmas, 2 N - 1 U-Net evaluations (sampler.HeunSampler).
         `precision` (additive, default None = the models' `inference_precision` attributes): 'bf16' or 'fp32' for this
         call only; the attributes are restored afterwards."""
         if precision is not None:
@@ -135,7 +136,7 @@ class VideoToVideoDiffusion(nn.Module):
                 return self.generate(v_in, sampler, num_inference_steps, guidance_scale, target_depth, noise_fn)
             finally:
                 self.unet.inference_precision, self.vae.inference_precision = saved
-        if sampler not in ('ddpm', 'ddim', 'dpmpp_2m'):
+        if sampler not in ('ddpm', 'ddim', 'dpmpp_2m', 'heun'):
             raise ValueError(f"Unknown sampler: {sampler}")
         if not v_in.is_cuda:
             raise CtsiError("generate runs on the HIP engine: move the input to a ROCm device")
@@ -156,6 +157,10 @@ class VideoToVideoDiffusion(nn.Module):
         if sampler == 'ddpm':
             z_0 = self.diffusion.p_sample_loop(self.unet, latent_shape, z_cond, device, progress=True,
                                                noise_fn=noise_fn)
+        elif sampler == 'heun':
+            from .sampler import HeunSampler
+            z_0 = HeunSampler(self.diffusion, self.unet).sample(latent_shape, z_cond, num_inference_steps, device,
+                                                                noise_fn=noise_fn)
         elif sampler == 'dpmpp_2m':
             from .sampler import DPMSolverSampler
             z_0 = DPMSolverSampler(self.diffusion, self.unet, order=2).sample(latent_shape, z_cond, num_inference_steps,

@@ -1,8 +1,9 @@
 """DDPM / DDIM samplers (mirror of reference inference/sampler.py) on the HIP engine, plus DPM-Solver++(2M)
-(DPMSolverSampler, additive: not in the reference).
+(DPMSolverSampler) and EDM Heun / Euler on Karras sigmas (HeunSampler), both additive: not in the reference.
 
 One denoising step = one replay of a captured hipGraph holding every kernel of a U-Net evaluation,
-the elementwise x_{t-1} update (ctsi_ddim_step / ctsi_ddpm_step / ctsi_dpm_step) and the increment of the device-side
+the elementwise x_{t-1} update (ctsi_ddim_step / ctsi_ddpm_step / ctsi_dpm_step / ctsi_heun_step) and the increment of
+the device-side
 step counter.  Per-step scalars (timestep embedding rows, update coefficients) come from device
 tables indexed by that counter, so the same graph serves all steps and the host never synchronises
 inside the loop.  The reference's five isnan/isinf host checks per step are folded into the update
@@ -11,7 +12,8 @@ kernel as unconditional nan_to_num (identity on finite values).
 from __future__ import annotations
 
 import logging
-from typing import Optional, Sequence, Tuple
+import math
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -35,7 +37,7 @@ def _is_engine_unet(model) -> bool:
 def _log_nonfinite(kind: str, table: torch.Tensor, steps: int, max_rows: int):
     """What the reference's five NaN/Inf checkpoints log (inference/sampler.py:268-275, 288-292, 307-311, 331-334), from
     the device-side counters the update kernel keeps: one host read after the loop instead of five syncs per step."""
-    if kind not in ("ddim", "dpmpp"):
+    if kind not in ("ddim", "dpmpp", "heun"):
         return            # the reference's DDPM loop (models/diffusion.py:340-367) has no such checkpoints
     t = table.cpu()
     if not bool(t.any()):
@@ -56,11 +58,14 @@ def _log_nonfinite(kind: str, table: torch.Tensor, steps: int, max_rows: int):
 
 
 def _run_sampler_generic(diffusion, model, shape, conditioning, ctx, z0, *, kind, t_desc, eta, noise_fn, progress,
-                         trajectory, order=2, eps_trajectory=None):
+                         trajectory, order=2, eps_trajectory=None, heun=None):
     """Reverse loop over an ARBITRARY `model(z, t, c) -> eps` callable (the reference's samplers accept any,
     inference/sampler.py:211-219): the network evaluation is the caller's (any torch code on the ROCm device), the
     x_{t-1} update with its guards is the engine's ctsi_ddim_step / ctsi_ddpm_step / ctsi_dpm_step.  Not captured: the callable is
     opaque.  The engine's own UNet3D takes the hipGraph path in run_sampler instead."""
+    if kind == "heun":
+        return _run_heun_generic(model, shape, conditioning, ctx, z0, heun, noise_fn=noise_fn, progress=progress,
+                                 trajectory=trajectory, eps_trajectory=eps_trajectory)
     import ctypes as C
     lib, sptr = ctx.lib, ctx.sptr
     n, L, d, h, w = [int(v) for v in shape]
@@ -116,6 +121,66 @@ def _run_sampler_generic(diffusion, model, shape, conditioning, ctx, z0, *, kind
     return z
 
 
+def _check_eps(eps, shape):
+    if not (torch.is_tensor(eps) and tuple(eps.shape) == tuple(shape) and eps.is_cuda):
+        raise CtsiError("the model callable must return a ROCm tensor of the latent's shape "
+                        f"{tuple(shape)}, got {type(eps).__name__} {tuple(getattr(eps, 'shape', ()))}")
+
+
+def _run_heun_generic(model, shape, conditioning, ctx, z0, plan, *, noise_fn, progress, trajectory, eps_trajectory):
+    """The generic-callable loop for 'heun': one ctsi_heun_step_f32 per evaluation.  The model sees the fractional
+    timestep of every evaluation as an fp32 tensor (the reference embeds t as a float); its input after a predictor
+    row is the corrector's z', which the update writes to `zin` (z keeps zhat)."""
+    import ctypes as C
+    lib, sptr = ctx.lib, ctx.sptr
+    n, L, d, h, w = [int(v) for v in shape]
+    evals = len(plan.t)
+    dev = ctx.device
+    coef = plan.rows.to(dev, torch.float32).contiguous()
+    z_nd = torch.empty((n, d, h, w, L), dtype=torch.float32, device=dev)
+    zin_nd = torch.empty_like(z_nd)
+    eps_nd = torch.empty_like(z_nd)
+    d1 = torch.zeros_like(z_nd)
+    step_ptr = torch.zeros(1, dtype=torch.int32, device=dev)
+    nonfinite = torch.zeros((evals + 2, 6), dtype=torch.int32, device=dev)
+    cond = conditioning.to(dev)
+    z = z0.to(dev, torch.float32).contiguous()
+    with ctx.scope():
+        lib.count_nonfinite_f32(_ptr(z), z.numel(), 1, C.c_void_p(nonfinite.data_ptr() + evals * 24), sptr)
+        cf = cond.float().contiguous()
+        lib.count_nonfinite_f32(_ptr(cf), cf.numel(), 0, C.c_void_p(nonfinite.data_ptr() + (evals + 1) * 24), sptr)
+        lib.ncdhw_f32_to_ndhwc_f32(_ptr(z), _ptr(z_nd), n, L, d, h, w, sptr)
+    it = range(evals)
+    if progress and tqdm is not None:
+        it = tqdm(it, desc="HEUN Sampling", total=evals)
+    for e in it:
+        t = torch.full((n,), float(plan.t[e]), device=dev, dtype=torch.float32)
+        eps = model(z, t, cond)
+        _check_eps(eps, shape)
+        eps = eps.detach().to(torch.float32).contiguous()
+        if eps_trajectory is not None:
+            eps_trajectory.append(eps.clone())
+        noise = None
+        if plan.noise_step[e] >= 0:
+            noise = _draw_noise(noise_fn, plan.noise_step[e], shape, dev).contiguous()
+        with ctx.scope():
+            lib.ncdhw_f32_to_ndhwc_f32(_ptr(eps), _ptr(eps_nd), n, L, d, h, w, sptr)
+            lib.heun_step_f32(_ptr(z_nd), _ptr(eps_nd), _ptr(d1), _ptr(noise), _ptr(zin_nd), L, 0, _ptr(coef),
+                              _ptr(step_ptr), n, L, d, h, w, _ptr(nonfinite), sptr)
+            lib.step_advance(_ptr(step_ptr), sptr)
+            z = torch.empty((n, L, d, h, w), dtype=torch.float32, device=dev)
+            lib.ndhwc_f32_to_ncdhw_f32(_ptr(zin_nd), _ptr(z), n, L, d, h, w, sptr)
+        if trajectory is not None and plan.closes[e]:
+            trajectory.append(z.clone())
+    _log_nonfinite("heun", nonfinite, evals, evals)
+    return z
+
+
+def _draw_noise(noise_fn, i, shape, dev) -> torch.Tensor:
+    return (noise_fn(i, tuple(shape)) if noise_fn is not None
+            else torch.randn(tuple(shape), device=dev)).to(dev, torch.float32)
+
+
 def ddim_coef_rows(alphas_cumprod: torch.Tensor, timesteps: Sequence[int], eta: float) -> torch.Tensor:
     """Coefficient rows for ctsi_ddim_step, computed with fp32 torch ops in the reference's order
     (sampler.py:295-325): [sqrt(1-a+1e-8), sqrt(a+1e-8)+1e-8, sqrt(a'+1e-8), sqrt(1-a'+1e-8), sigma]."""
@@ -134,7 +199,8 @@ def ddim_coef_rows(alphas_cumprod: torch.Tensor, timesteps: Sequence[int], eta: 
     return rows
 
 
-def dpm_coef_rows(alphas_cumprod: torch.Tensor, t_desc: Sequence[int], order: int = 2) -> torch.Tensor:
+def dpm_coef_rows(alphas_cumprod: torch.Tensor, t_desc: Sequence[int], order: int = 2,
+                  dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """Coefficient rows for ctsi_dpm_step: multistep DPM-Solver++ in data prediction (Lu et al. 2022, "DPM-Solver++",
     Algorithm 2) on the timestep list `t_desc`, the last target being abar = 1 as in the reference DDIM.
 
@@ -144,7 +210,8 @@ def dpm_coef_rows(alphas_cumprod: torch.Tensor, t_desc: Sequence[int], order: in
       first order (step 0, order=1):  a = sigma_{i+1}/sigma_i,  b = alpha_{i+1} (1 - e^-h),  c = 0  (= DDIM, eta 0)
       second order:  r = h_{i-1}/h_i,  b = alpha_{i+1} (1 - e^-h) (1 + 1/2r),  c = -alpha_{i+1} (1 - e^-h) / 2r
       final step (sigma = 0, lambda = +inf): first order, exactly a = 0, b = 1, c = 0.
-    Rows [1/alpha_i, sigma_i/alpha_i, a_i, b_i, c_i, 0, 0, 0], computed in float64 and rounded once to fp32."""
+    Rows [1/alpha_i, sigma_i/alpha_i, a_i, b_i, c_i, 0, 0, 0], computed in float64 and rounded once to fp32 (`dtype`
+    = torch.float64 returns them unrounded)."""
     if order not in (1, 2):
         raise ValueError(f"DPM-Solver++ order must be 1 or 2, got {order}")
     ac = alphas_cumprod.detach().double().cpu().numpy()
@@ -170,10 +237,140 @@ def dpm_coef_rows(alphas_cumprod: torch.Tensor, t_desc: Sequence[int], order: in
             rows[i, 3] = alpha[i + 1] * phi * (1.0 + 0.5 / r)
             rows[i, 4] = -alpha[i + 1] * phi * (0.5 / r)
         h_prev = h
-    return torch.from_numpy(rows).to(torch.float32)
+    return torch.from_numpy(rows).to(dtype)
 
 
-def _coef_rows(diffusion, kind: str, t_desc: Sequence[int], eta: float, order: int) -> torch.Tensor:
+# ---------------------------------------------------------------------------------------------------------------------
+# EDM (Karras et al. 2022, Algorithm 2) on the VP model: sigma = sqrt((1 - abar) / abar), x = z * a(sigma),
+# a(sigma) = sqrt(1 + sigma^2).  Host side in float64; the device update is ctsi_heun_step.
+# ---------------------------------------------------------------------------------------------------------------------
+def sigma_table(alphas_cumprod: torch.Tensor) -> np.ndarray:
+    """sigma_k = sqrt((1 - abar_k) / abar_k), k = 0..T-1, float64 (increasing)."""
+    ac = alphas_cumprod.detach().double().cpu().numpy()
+    return np.sqrt((1.0 - ac) / ac)
+
+
+def karras_sigmas(n: int, sigma_min: float, sigma_max: float, rho: float = 7.0) -> np.ndarray:
+    """The rho-schedule (Karras et al. 2022, eq. 5): sigma_i = (sigma_max^(1/rho) + i/(n-1) (sigma_min^(1/rho) -
+    sigma_max^(1/rho)))^rho for i < n, then sigma_n = 0; n = 1 gives [sigma_max, 0].  float64, n + 1 entries."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"the EDM schedule needs at least one step, got {n}")
+    if not (0.0 < sigma_min <= sigma_max and math.isfinite(sigma_max)):
+        raise ValueError(f"need 0 < sigma_min <= sigma_max < inf, got {sigma_min}, {sigma_max}")
+    if not rho > 0:
+        raise ValueError(f"rho must be positive, got {rho}")
+    if n == 1:
+        return np.array([float(sigma_max), 0.0])
+    lo, hi = float(sigma_min) ** (1.0 / rho), float(sigma_max) ** (1.0 / rho)
+    s = (hi + np.arange(n, dtype=np.float64) / (n - 1) * (lo - hi)) ** rho
+    s[0], s[-1] = sigma_max, sigma_min            # the endpoints exactly (pow(pow(x, 1/rho), rho) rounds)
+    return np.append(s, 0.0)
+
+
+def sigma_to_t(sigma, alphas_cumprod: torch.Tensor):
+    """The (fractional) timestep of a noise level: for sigma_k <= sigma <= sigma_{k+1},
+    t = k + (ln sigma - ln sigma_k) / (ln sigma_{k+1} - ln sigma_k), clamped to [0, T-1].  Exactly k at a table value.
+    Scalar in, float out; array in, float64 array out."""
+    table = sigma_table(alphas_cumprod)
+    T = len(table)
+    sig = np.asarray(sigma, dtype=np.float64)
+    k = np.clip(np.searchsorted(table, sig, side="right") - 1, 0, T - 2)
+    ls = np.log(table)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = k + (np.log(np.maximum(sig, table[0])) - ls[k]) / (ls[k + 1] - ls[k])
+    t = np.where(sig <= table[0], 0.0, np.where(sig >= table[-1], float(T - 1), t))
+    t = np.clip(t, 0.0, float(T - 1))
+    return float(t) if t.ndim == 0 else t
+
+
+class HeunRows(NamedTuple):
+    """What ctsi_heun_step needs for one sampling run (sampler.heun_coef_rows)."""
+    rows: torch.Tensor            # (E, 8) coefficient rows, one per U-Net evaluation (fp32 unless asked otherwise)
+    t: np.ndarray                 # (E,) float64 timestep of every evaluation
+    sigma_eval: np.ndarray        # (E,) float64 noise level of every evaluation
+    sigmas: np.ndarray            # (N + 1,) the schedule, ending in 0
+    sigma_hat: np.ndarray         # (N,) sigma_i (1 + gamma_i)
+    gammas: np.ndarray            # (N,)
+    noise_step: List[int]         # (E,) step i whose churn noise eps_i the row consumes, or -1
+    closes: List[bool]            # (E,) True for the row that completes a step
+    init: Tuple[float, float]     # zhat_0 = init[0] eps + init[1] eps_0 (eps_0: step 0's churn noise)
+
+
+def heun_coef_rows(alphas_cumprod: torch.Tensor, sigmas: Sequence[float], order: int = 2, s_churn: float = 0.0,
+                   s_tmin: float = 0.0, s_tmax: float = float("inf"), s_noise: float = 1.0,
+                   dtype: torch.dtype = torch.float32) -> HeunRows:
+    """Coefficient rows for ctsi_heun_step: EDM (Karras et al. 2022, Algorithm 2) on the descending noise levels
+    `sigmas` (a trailing 0 is appended when missing), with the denoiser D(x, sigma) = clamp(nan_to_num(x - sigma
+    eps(x / a(sigma), t(sigma))), -10, 10) of the reference DDIM.
+
+    Step i: gamma_i = min(S_churn / N, sqrt 2 - 1) on S_tmin <= sigma_i <= S_tmax (else 0), sigma_hat = sigma_i (1 +
+    gamma_i), xhat = x_i + S_noise sqrt(sigma_hat^2 - sigma_i^2) eps_i; Euler predictor x' = xhat + (sigma_{i+1} -
+    sigma_hat) (xhat - D1) / sigma_hat; at order 2 with sigma_{i+1} > 0 the corrector averages the two slopes.
+
+    The device state is zhat = xhat / a(sigma_hat), so with A = a(sigma_hat), p = A sigma_{i+1} / sigma_hat,
+    q = 1 - sigma_{i+1} / sigma_hat, a' = a(sigma_{i+1}), A' = a(sigma_hat_{i+1}) and k' = S_noise sqrt(sigma_hat_{i+1}^2 -
+    sigma_{i+1}^2) / A' (the next step's churn, fused into this step's closing row):
+      predictor  [A, 0, sigma_hat, 0, p/a', q/a', 0, 0]              zin = z' = x'/a'
+      corrector  [p, q, sigma_{i+1}, 1, p/A', -h/(2 sigma_{i+1} A'), h (1/sigma_{i+1} - 2/sigma_hat) / (2 A'), k']
+                 with h = sigma_{i+1} - sigma_hat  (x' = p zhat + q D1 is recomputed, not stored)
+      Euler      [A, 0, sigma_hat, 1, p/A', q/A', 0, k']
+      final      [A, 0, sigma_hat, 1, 0, 1, 0, 0]                      (sigma_{i+1} = 0: x_N = D1 exactly)
+    Order 2 costs 2N - 1 evaluations, order 1 N.  Computed in float64, rounded once to `dtype`."""
+    if order not in (1, 2):
+        raise ValueError(f"the EDM sampler's order must be 1 (Euler) or 2 (Heun), got {order}")
+    sig = np.asarray([float(v) for v in sigmas], dtype=np.float64)
+    if sig.ndim != 1 or len(sig) == 0 or not np.isfinite(sig).all():
+        raise ValueError("sigmas must be a non-empty list of finite noise levels")
+    if sig[-1] != 0.0:
+        sig = np.append(sig, 0.0)
+    if len(sig) < 2 or not (sig[:-1] > 0).all() or not (np.diff(sig) < 0).all():
+        raise ValueError(f"sigmas must be strictly descending and positive (then 0), got {sig.tolist()}")
+    if not (s_churn >= 0 and s_noise >= 0 and s_tmin <= s_tmax):
+        raise ValueError(f"bad churn settings: s_churn={s_churn}, s_noise={s_noise}, s_tmin={s_tmin}, s_tmax={s_tmax}")
+    T = int(alphas_cumprod.shape[0])
+    N = len(sig) - 1
+    evals = 2 * N - 1 if order == 2 else N
+    if evals > T + 1:
+        raise ValueError(f"{N} EDM steps of order {order} need {evals} U-Net evaluations; at most T + 1 = {T + 1}")
+    a = lambda v: math.sqrt(1.0 + v * v)
+    gam = np.array([min(s_churn / N, math.sqrt(2.0) - 1.0) if (s_tmin <= sig[i] <= s_tmax and s_churn > 0) else 0.0
+                    for i in range(N)])
+    sh = sig[:N] * (1.0 + gam)
+    churn = np.array([s_noise * math.sqrt(max(sh[i] ** 2 - sig[i] ** 2, 0.0)) if gam[i] > 0 else 0.0
+                      for i in range(N)])
+    rows, sev, noise_step, closes = [], [], [], []
+    for i in range(N):
+        s_hat, s1, A = sh[i], sig[i + 1], a(sh[i])
+        if s1 == 0.0:
+            rows.append([A, 0.0, s_hat, 1.0, 0.0, 1.0, 0.0, 0.0])
+            sev.append(s_hat), noise_step.append(-1), closes.append(True)
+            continue
+        p, q = A * s1 / s_hat, 1.0 - s1 / s_hat
+        A_next = a(sh[i + 1])
+        k_next = churn[i + 1] / A_next
+        nxt = i + 1 if gam[i + 1] > 0 else -1
+        if order == 1:
+            rows.append([A, 0.0, s_hat, 1.0, p / A_next, q / A_next, 0.0, k_next])
+            sev.append(s_hat), noise_step.append(nxt), closes.append(True)
+            continue
+        a1, hh = a(s1), s1 - s_hat
+        rows.append([A, 0.0, s_hat, 0.0, p / a1, q / a1, 0.0, 0.0])
+        sev.append(s_hat), noise_step.append(-1), closes.append(False)
+        rows.append([p, q, s1, 1.0, p / A_next, -hh / (2.0 * s1) / A_next,
+                     0.5 * hh * (1.0 / s1 - 2.0 / s_hat) / A_next, k_next])
+        sev.append(s1), noise_step.append(nxt), closes.append(True)
+    sev = np.asarray(sev)
+    A0 = a(sh[0])
+    return HeunRows(rows=torch.from_numpy(np.asarray(rows, dtype=np.float64)).to(dtype),
+                    t=np.asarray(sigma_to_t(sev, alphas_cumprod), dtype=np.float64).reshape(-1),
+                    sigma_eval=sev, sigmas=sig, sigma_hat=sh, gammas=gam, noise_step=noise_step, closes=closes,
+                    init=(sig[0] / A0, churn[0] / A0))
+
+
+def _coef_rows(diffusion, kind: str, t_desc: Sequence[int], eta: float, order: int, heun=None) -> torch.Tensor:
+    if kind == "heun":
+        return heun.rows
     if kind == "dpmpp":
         return dpm_coef_rows(diffusion.alphas_cumprod, t_desc, order)
     if kind == "ddim":
@@ -182,7 +379,7 @@ def _coef_rows(diffusion, kind: str, t_desc: Sequence[int], eta: float, order: i
 
 
 def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, t_desc, eta, noise_fn, comm,
-                        trajectory=None, order=2):
+                        trajectory=None, order=2, heun=None):
     """Depth-sharded reverse loop: this process owns depth slab `comm.rank` of the volume (parallel.RcclComm: RCCL
     issued by libctsi on the engine stream; parallel.DistComm under the gloo tests).  Every rank passes the full
     conditioning / initial noise and gets the full result back (all-gather along depth).  A batch runs volume by
@@ -190,20 +387,22 @@ def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, 
     With a capture-safe transport and CTSI_SHARD_CAPTURE=1 the step -- kernels AND collectives -- is replayed as one
     hipGraph, like the single-GPU step.
     DPM-Solver++ ('dpmpp'): the update is elementwise over the rank's own slab (its history buffer too), and step 0's
-    row (c = 0) overwrites that history, so volume b + 1 starts clean."""
+    row (c = 0) overwrites that history, so volume b + 1 starts clean.
+    Heun ('heun', rows `heun`): one launch per evaluation, elementwise over the slab; D1 is written by every predictor
+    before its corrector reads it, and the churn noise slab is copied only before the rows that consume it."""
     import os
     from .engine import cached_program
     from .parallel import ShardSpec
     n, L, d, h, w = [int(v) for v in shape]
     spec = ShardSpec(comm.rank, comm.world, comm, d)
     dl = spec.depth_local
-    with_noise = (kind == "ddpm") or eta > 0
+    with_noise = _with_noise(kind, eta, heun)
     steps = len(t_desc)
     capture = bool(getattr(comm, "capturable", False)) and os.environ.get("CTSI_SHARD_CAPTURE") == "1"
-    outs, trajs = [], [[] for _ in range(steps)]
+    outs, trajs = [], [[] for _ in range(sum(heun.closes) if kind == "heun" else steps)]
     with ctx.scope():
         key = ("sampler-shard", ctx.device.index, 1, d, h, w, comm.rank, comm.world, kind, with_noise)
-        if kind == "dpmpp":
+        if kind in ("dpmpp", "heun"):
             key += (order,)
 
         def build():
@@ -212,24 +411,27 @@ def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, 
             return prog
 
         prog = cached_program(unet, key, build)
-        coef = _coef_rows(diffusion, kind, t_desc, eta, order)
+        coef = _coef_rows(diffusion, kind, t_desc, eta, order, heun)
         lo = spec.depth_start
         noises = {}
         for b in range(n):
             prog.load_latents(z0[b:b + 1], conditioning[b:b + 1])
-            prog.set_schedule([int(t) for t in t_desc], coef.to(ctx.device))
+            prog.set_schedule(t_desc if kind == "heun" else [int(t) for t in t_desc], coef.to(ctx.device))
             if capture and prog.graph is None:
                 prog.capture()
                 prog.step_ptr.zero_()
+            done = 0
             for i in range(steps):
-                if with_noise:
-                    if i not in noises:   # one draw per step for the whole batch, as the unsharded loop makes it
-                        noises[i] = (noise_fn(i, tuple(shape)) if noise_fn is not None
-                                     else torch.randn(tuple(shape), device=ctx.device))
-                    prog.noise.copy_(noises[i][b:b + 1, :, lo:lo + dl].to(ctx.device, torch.float32))
+                ni = (heun.noise_step[i] if kind == "heun" else i) if with_noise else -1
+                if ni >= 0:
+                    if ni not in noises:   # one draw per step for the whole batch, as the unsharded loop makes it
+                        noises[ni] = (noise_fn(ni, tuple(shape)) if noise_fn is not None
+                                      else torch.randn(tuple(shape), device=ctx.device))
+                    prog.noise.copy_(noises[ni][b:b + 1, :, lo:lo + dl].to(ctx.device, torch.float32))
                 prog.launch() if capture else prog.run()
-                if trajectory is not None:
-                    trajs[i].append(comm.gather_depth(comm.rank, prog.z_ncdhw(), counts=spec.depth_counts))
+                if trajectory is not None and (kind != "heun" or heun.closes[i]):
+                    trajs[done].append(comm.gather_depth(comm.rank, prog.z_ncdhw(), counts=spec.depth_counts))
+                    done += 1
             outs.append(comm.gather_depth(comm.rank, prog.z_ncdhw(), counts=spec.depth_counts))
         if trajectory is not None:
             trajectory.extend(torch.cat(t, dim=0) for t in trajs)
@@ -239,11 +441,24 @@ def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, 
         return res
 
 
+def _with_noise(kind: str, eta: float, heun) -> bool:
+    if kind == "heun":
+        return bool((heun.gammas > 0).any())        # churn on
+    return (kind == "ddpm") or eta > 0
+
+
 def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_desc: Sequence[int],
                 progress: bool, eta: float = 0.0, noise_fn=None, z_init: Optional[torch.Tensor] = None,
-                trajectory: Optional[list] = None, order: int = 2, eps_trajectory: Optional[list] = None):
-    """Shared reverse loop.  kind: 'ddim' | 'ddpm' | 'dpmpp' (DPM-Solver++ of `order` 1 or 2); t_desc: descending
-    timestep list.  `eps_trajectory` (unsharded runs only): receives the noise prediction of every step, fp32 NCDHW."""
+                trajectory: Optional[list] = None, order: int = 2, eps_trajectory: Optional[list] = None,
+                heun: Optional[HeunRows] = None):
+    """Shared reverse loop.  kind: 'ddim' | 'ddpm' | 'dpmpp' (DPM-Solver++ of `order` 1 or 2) | 'heun' (EDM of `order` 1
+    or 2 on the rows `heun` = heun_coef_rows(...), t_desc = heun.t); t_desc: descending timestep list.
+    `eps_trajectory` (unsharded runs only): receives the noise prediction of every U-Net evaluation, fp32 NCDHW.
+    'heun': `trajectory` receives the state after every completed step (the VP latent zhat_{i+1}, which already holds
+    step i+1's churn; the output last); the initial draw eps becomes zhat_0 = (sigma_0 eps + churn_0 eps_0) / a(sigma_hat_0),
+    eps_0 = noise_fn(0, shape) drawn only when step 0 churns."""
+    if kind == "heun" and (heun is None or len(heun.t) != len(t_desc)):
+        raise ValueError("kind='heun' needs the rows of heun_coef_rows(...) (heun=) and t_desc = heun.t")
     if not _is_engine_unet(model) and not callable(model):
         raise CtsiError(f"the samplers need a model(z, t, c) callable; got {type(model).__name__}")
     unet = model
@@ -251,7 +466,7 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
     ctx = Ctx.get(device if device.type == "cuda" else conditioning.device)
     n, L, d, h, w = [int(v) for v in shape]
     steps = len(t_desc)
-    with_noise = (kind == "ddpm") or eta > 0
+    with_noise = _with_noise(kind, eta, heun)
     max_rows = (diffusion.timesteps + 1) * n
     # initial noise is drawn exactly where the reference draws it (on the caller's stream/generator)
     if z_init is not None:
@@ -260,10 +475,15 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
         z0 = noise_fn(-1, tuple(shape)).to(ctx.device)
     else:
         z0 = torch.randn(tuple(shape), device=ctx.device)
+    if kind == "heun":
+        zh = heun.init[0] * z0.to(ctx.device, torch.float64)
+        if heun.gammas[0] > 0:
+            zh += heun.init[1] * _draw_noise(noise_fn, 0, shape, ctx.device).double()
+        z0 = zh.float()
     if not _is_engine_unet(model):
         return _run_sampler_generic(diffusion, model, shape, conditioning, ctx, z0, kind=kind, t_desc=t_desc, eta=eta,
                                     noise_fn=noise_fn, progress=progress, trajectory=trajectory, order=order,
-                                    eps_trajectory=eps_trajectory)
+                                    eps_trajectory=eps_trajectory, heun=heun)
     precision = check_precision(getattr(unet, "inference_precision", "bf16"))
     comm = getattr(unet, "depth_shard_comm", None)
     if comm is not None and comm.world > 1:
@@ -273,10 +493,10 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
         if eps_trajectory is not None:
             raise CtsiError("eps_trajectory is not recorded by the depth-sharded sampler")
         return run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, kind=kind, t_desc=t_desc, eta=eta,
-                                   noise_fn=noise_fn, comm=comm, trajectory=trajectory, order=order)
+                                   noise_fn=noise_fn, comm=comm, trajectory=trajectory, order=order, heun=heun)
     with ctx.scope():
         key = ("sampler", ctx.device.index, n, d, h, w, max_rows, kind, with_noise, unet.attention_mode, precision)
-        if kind == "dpmpp":
+        if kind in ("dpmpp", "heun"):
             key += (order,)
         from .engine import cached_program
 
@@ -297,8 +517,11 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
         cnd = conditioning.detach().to(ctx.device, torch.float32).contiguous()
         ctx.lib.count_nonfinite_f32(_ptr(cnd), cnd.numel(), 0, C.c_void_p(nf_tail + 24), ctx.sptr)
         cnd.record_stream(ctx.stream)
-        coef = _coef_rows(diffusion, kind, t_desc, eta, order)
-        t_rows = [int(t) for t in t_desc for _ in range(n)]
+        coef = _coef_rows(diffusion, kind, t_desc, eta, order, heun)
+        if kind == "heun":
+            t_rows = [float(t) for t in t_desc for _ in range(n)]
+        else:
+            t_rows = [int(t) for t in t_desc for _ in range(n)]
         prog.set_schedule(t_rows, coef.to(ctx.device))
         if prog.graph is None:
             # one eager warm-up step is not needed: capture records launches without executing them
@@ -308,13 +531,15 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
         if progress and tqdm is not None:
             it = tqdm(it, desc=f"{kind.upper()} Sampling", total=steps)
         for i in it:
-            if with_noise:
+            # 'heun': row i consumes step heun.noise_step[i]'s churn noise (only closing rows followed by a churning step)
+            ni = (heun.noise_step[i] if kind == "heun" else i) if with_noise else -1
+            if ni >= 0:
                 if noise_fn is not None:
-                    prog.noise.copy_(noise_fn(i, tuple(shape)).to(ctx.device, torch.float32))
+                    prog.noise.copy_(noise_fn(ni, tuple(shape)).to(ctx.device, torch.float32))
                 else:
                     prog.noise.normal_()
             prog.launch()
-            if trajectory is not None:
+            if trajectory is not None and (kind != "heun" or heun.closes[i]):
                 trajectory.append(prog.z_ncdhw())
             if eps_trajectory is not None:
                 eps_trajectory.append(prog.eps_ncdhw())
@@ -436,6 +661,71 @@ class DPMSolverSampler:
         if window_batch is None:
             window_batch = 0
         if window_batch != 1:
+            batched = lambda shp, cond, z_init: self.sample(shp, cond, num_inference_steps, device, progress=False,
+                                                            z_init=z_init)
+        return _stitched(self, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress,
+                         lambda shp, cond: self.sample(shp, cond, num_inference_steps, device, progress=False),
+                         batched_fn=batched, window_batch=window_batch, dp_group=dp_group)
+
+    def _create_gaussian_weight(self, d, h, w):
+        return gaussian_weight(d, h, w)
+
+
+class HeunSampler:
+    """EDM sampling (Karras et al. 2022, Algorithm 2): second-order Heun (order=2, 2N - 1 U-Net evaluations) or Euler
+    (order=1, N evaluations) steps on freely chosen noise levels -- by default the rho-schedule between sigma_min and
+    sigma_max -- with optional stochastic churn.  The U-Net sees the VP latent x / a(sigma) at the fractional timestep
+    t(sigma) (sigma_to_t).  Additive: the reference's EDMSampler is an unimplemented stub (kept as is).
+    Defaults follow the paper clamped to the model's range: sigma_min = max(0.002, sigma_0), sigma_max = min(80,
+    sigma_{T-1}), rho = 7.  Noise: eps from z_init / noise_fn(-1, shape) / torch.randn, then eps_i = noise_fn(i, shape)
+    (else torch.randn) only for the steps that churn (gamma_i > 0)."""
+
+    def __init__(self, diffusion, model, order=2, sigma_min=None, sigma_max=None, rho=7.0, s_churn=0.0, s_tmin=0.0,
+                 s_tmax=float("inf"), s_noise=1.0):
+        if order not in (1, 2):
+            raise ValueError(f"the EDM sampler's order must be 1 (Euler) or 2 (Heun), got {order}")
+        self.diffusion = diffusion
+        self.model = model
+        self.order = int(order)
+        self.timesteps = diffusion.timesteps
+        table = sigma_table(diffusion.alphas_cumprod)
+        self.sigma_min = float(max(0.002, table[0]) if sigma_min is None else sigma_min)
+        self.sigma_max = float(min(80.0, table[-1]) if sigma_max is None else sigma_max)
+        self.rho = float(rho)
+        self.s_churn, self.s_tmin, self.s_tmax, self.s_noise = float(s_churn), float(s_tmin), float(s_tmax), float(s_noise)
+
+    def sigmas(self, num_inference_steps) -> np.ndarray:
+        """The default schedule: N levels from sigma_max down to sigma_min, then 0 (float64)."""
+        return karras_sigmas(num_inference_steps, self.sigma_min, self.sigma_max, self.rho)
+
+    def coef_rows(self, num_inference_steps=None, sigmas=None) -> HeunRows:
+        if sigmas is None:
+            if num_inference_steps is None:
+                raise ValueError("give num_inference_steps or sigmas")
+            sigmas = self.sigmas(num_inference_steps)
+        return heun_coef_rows(self.diffusion.alphas_cumprod, sigmas, self.order, self.s_churn, self.s_tmin, self.s_tmax,
+                              self.s_noise)
+
+    @torch.no_grad()
+    def sample(self, shape, conditioning, num_inference_steps, device, progress=True, noise_fn=None, trajectory=None,
+               z_init=None, sigmas=None):
+        """`sigmas` (optional): explicit descending noise levels (a trailing 0 is appended when missing); they override
+        the schedule and num_inference_steps."""
+        rows = self.coef_rows(num_inference_steps, sigmas)
+        return run_sampler(self.diffusion, self.model, shape, conditioning, device, kind="heun", t_desc=list(rows.t),
+                           progress=progress, noise_fn=noise_fn, trajectory=trajectory, z_init=z_init,
+                           order=self.order, heun=rows)
+
+    @torch.no_grad()
+    def sample_with_stitching(self, v_thick_full, vae, num_inference_steps=20, patch_size=(8, 192, 192),
+                              target_patch_size=(48, 192, 192), stride=(4, 96, 96), device='cuda', progress=True,
+                              window_batch=None, dp_group=None):
+        """DDIMSampler.sample_with_stitching without `eta`: windows are batched when s_churn == 0 and run one by one
+        otherwise (each window then draws its own churn noise, as stochastic DDIM does)."""
+        batched = None
+        if window_batch is None:
+            window_batch = 0
+        if self.s_churn == 0.0 and window_batch != 1:
             batched = lambda shp, cond, z_init: self.sample(shp, cond, num_inference_steps, device, progress=False,
                                                             z_init=z_init)
         return _stitched(self, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress,

@@ -206,6 +206,9 @@ class UNet3D(nn.Module):
             if getattr(prog, "sampler_kind", None) is not None:
                 raise CtsiError("internal: plain forward reuses a sampler program")
             prog_plain.load_latents(x, c)
-            prog_plain.set_schedule([int(v) for v in t.reshape(-1).tolist()])
+            # an integer-valued t keeps the int32 embedding; a fractional floating t is embedded as is (the reference
+            # embeds t as a float, models/unet3d.py:25-32)
+            t_vals = torch.as_tensor(t).reshape(-1).tolist()
+            prog_plain.set_schedule([int(v) if float(v).is_integer() else float(v) for v in t_vals])
             prog_plain.launch()
             return prog_plain.eps_ncdhw()
