@@ -8,7 +8,12 @@ conditioning and every weight resident in HBM when the timed region starts.  The
 `VideoToVideoDiffusion(yaml.safe_load(config/slice_interpolation_full_medium.yaml))` builds in the
 reference (264.66 M-param U-Net, latent 8), random-init (seed 0), synthetic input.
 
-Extra objects on the same line:
+A plain run does only what the headline figure needs: set up, warm up, time the steps, --dump-outputs if asked, print
+the line.  Everything else it can measure or check runs only with --full (the objects below, and in --mode train the
+optimizer-step figures and the roofline); without it they are null on the line.  --no-roofline / --no-cpu / --no-volume
+drop single legs of a --full run.
+
+Extra objects on the same line (--full):
   roofline     — the dominant kernel (the one with the most time per step; currently the 3x3x3 LDS
                  halo-tile conv): algorithmic FLOPs of its launches in one U-Net evaluation / their
                  summed duration, measured with HIP events on the engine stream around every launch
@@ -62,9 +67,12 @@ def parse():
     ap.add_argument("--depth-out", type=int, default=48)
     ap.add_argument("--ddim-steps", type=int, default=50)
     ap.add_argument("--batch", type=int, default=1, help="volumes per GPU")
-    ap.add_argument("--no-volume", action="store_true", help="skip the end-to-end generate() timing")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU oracle baseline")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure: roofline, CPU oracle baseline, end-to-end generate() "
+                         "and VAE timings, the captured-vs-eager check (dp); optimizer-step figures and roofline (train)")
+    ap.add_argument("--no-volume", action="store_true", help="--full without the end-to-end generate() timing")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="host threads for the CPU oracle leg (0 = every core this process may run on)")
     ap.add_argument("--cpu-config1", action="store_true",
@@ -86,7 +94,12 @@ def parse():
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (e.g. bench_outputs; float32, at most "
                          "64 MB in all; larger outputs are a fixed seeded sample): dp/shard -> z (the sampler state after the "
                          "step) and eps (its noise prediction); train -> loss and unet_grads")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        if args.cpu_config1 or args.sampler != "ddim":
+            ap.error("--cpu-config1 and --sampler choose what the --full legs measure: add --full")
+        args.no_volume = args.no_cpu = args.no_roofline = True
+    return args
 
 
 DUMP_MAX_BYTES = 60 * 10**6     # array data of one --dump-outputs, below 64 MB with room for the .npy headers
@@ -415,30 +428,38 @@ def bench_train(args, pkg, E, model, ctx, dev, rank, world, dist):
     #   fused  = optim.FusedAdamW.step(): ONE multi-tensor AdamW launch + the engine's fast re-pack of every bf16 kernel image
     #            and fp32 operand of the training program (tables of pointers: csrc/optim.hip, engine.Program.fast_repack)
     #   torch  = torch.optim.AdamW.step() + the generic re-pack through torch (what round 2 measured: 41 + 6 ms)
-    def timed(fn):
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t1) * 1e3
+    after_opt = None
+    if args.full:
+        def timed(fn):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t1) * 1e3
 
-    def fresh():
-        with ctx.scope():
-            prog.ensure_fresh()
+        def fresh():
+            with ctx.scope():
+                prog.ensure_fresh()
 
-    fopt = pkg.FusedAdamW(params, lr=1e-6, engine_modules=[model.unet])
-    fopt.step()                       # first calls: build the optimizer's and the program's tables, record the re-pack graph
-    fopt.step()
-    fused_ms = min(timed(fopt.step) for _ in range(3))
-    fused_left_ms = timed(fresh)      # nothing is left to re-pack (this is the fingerprint check every forward makes)
-    fopt.engine_modules = []
-    fused_only_ms = min(timed(fopt.step) for _ in range(3))     # the optimizer alone (kernel + host bookkeeping)
-    fresh()
-    del fopt
-    opt = torch.optim.AdamW(params, lr=1e-6)
-    opt.step()
-    adamw_ms = min(timed(opt.step) for _ in range(2))
-    repack_ms = timed(fresh)
+        fopt = pkg.FusedAdamW(params, lr=1e-6, engine_modules=[model.unet])
+        fopt.step()                       # first calls: build the optimizer's and the program's tables, record the re-pack graph
+        fopt.step()
+        fused_ms = min(timed(fopt.step) for _ in range(3))
+        fused_left_ms = timed(fresh)      # nothing is left to re-pack (this is the fingerprint check every forward makes)
+        fopt.engine_modules = []
+        fused_only_ms = min(timed(fopt.step) for _ in range(3))     # the optimizer alone (kernel + host bookkeeping)
+        fresh()
+        del fopt
+        opt = torch.optim.AdamW(params, lr=1e-6)
+        opt.step()
+        adamw_ms = min(timed(opt.step) for _ in range(2))
+        repack_ms = timed(fresh)
+        after_opt = {"fused_adamw_step_and_repack_ms": fused_ms, "fused_adamw_step_alone_ms": fused_only_ms,
+                     "left_to_repack_after_fused_ms": fused_left_ms, "torch_adamw_step_ms": adamw_ms,
+                     "generic_repack_ms": repack_ms,
+                     "note": "not inside the timed micro-steps (no optimizer step there); paid once per optimizer step, "
+                             "i.e. per accumulation window; fused = optim.FusedAdamW (one ctsi_adamw_multi launch + fast "
+                             "re-pack), torch = torch.optim.AdamW + the generic re-pack"}
     groups = {}
     if rank == 0 and not args.no_roofline:
         with ctx.scope():
@@ -487,17 +508,10 @@ def bench_train(args, pkg, E, model, ctx, dev, rank, world, dist):
             "config": {"workload": f"config 3 micro-step: v_in ({B},1,{args.depth_in},{hw},{hw}), v_gt ({B},1,"
                                    f"{args.depth_out},{hw},{hw}); frozen-VAE encode x2 + U-Net forward + backward "
                                    "(264.66M params), every activation kept in HBM (no recomputation)",
-                       "micro_batch_per_gpu": B, "parallelism": f"dp{world}", "finite": finite,
+                       "micro_batch_per_gpu": B, "parallelism": f"dp{world}", "full": args.full, "finite": finite,
                        "samples_per_sec": args.steps * world * B / dt,
                        "unet_fwd_bwd_tflop": prog.flops / 1e12,
-                       "after_optimizer_step": {"fused_adamw_step_and_repack_ms": fused_ms,
-                                                "fused_adamw_step_alone_ms": fused_only_ms,
-                                                "left_to_repack_after_fused_ms": fused_left_ms,
-                                                "torch_adamw_step_ms": adamw_ms, "generic_repack_ms": repack_ms,
-                                                "note": "not inside the timed micro-steps (no optimizer step there); "
-                                                        "paid once per optimizer step, i.e. per accumulation window; "
-                                                        "fused = optim.FusedAdamW (one ctsi_adamw_multi launch + fast "
-                                                        "re-pack), torch = torch.optim.AdamW + the generic re-pack"}},
+                       "after_optimizer_step": after_opt},
             "roofline": roof, "cpu_baseline": None}))
     if dist is not None:
         dist.destroy_process_group()
@@ -678,29 +692,33 @@ def main():
             torch.cuda.synchronize()
             dump_outputs(args.dump_outputs, {"z": z_out, "eps": eps_out}, f"_rank{rank}" if world > 1 else "")
         finite = bool(torch.isfinite(z_out).all().item())
-        # What the timed graph computes, checked beyond "finite": one more replay of the captured step against the same
-        # step launched eagerly from the same state (z, conditioning, step counter): identical kernels in identical order, so
-        # the noise predictions must agree to the last bit.
-        z_keep, xin_keep, sp_keep = prog.z.clone(), prog.xin.t.clone(), prog.step_ptr.clone()
-        prog.launch()
-        eps_graph = prog.eps.clone()
-        prog.z.copy_(z_keep)
-        prog.xin.t.copy_(xin_keep)
-        prog.step_ptr.copy_(sp_keep)
-        prog.run()
-        eps_eager = prog.eps.clone()
-        cap_vs_eager = float(((eps_graph.double() - eps_eager.double()).norm() / eps_eager.double().norm().clamp_min(1e-30)).item())
-        finite = finite and bool(torch.isfinite(eps_graph).all().item()) and float(eps_graph.abs().sum().item()) > 0.0
-        checksum = eps_graph.double().sum().reshape(1)
-    rank_checksums = None
+        cap_vs_eager, rank_checksums = None, None
+        if not args.full:       # the last timed step's noise prediction, as it stands
+            finite = finite and bool(torch.isfinite(prog.eps).all().item()) and float(prog.eps.abs().sum().item()) > 0.0
+        else:
+            # What the timed graph computes, checked beyond "finite": one more replay of the captured step against the same
+            # step launched eagerly from the same state (z, conditioning, step counter): identical kernels in identical order,
+            # so the noise predictions must agree to the last bit.
+            z_keep, xin_keep, sp_keep = prog.z.clone(), prog.xin.t.clone(), prog.step_ptr.clone()
+            prog.launch()
+            eps_graph = prog.eps.clone()
+            prog.z.copy_(z_keep)
+            prog.xin.t.copy_(xin_keep)
+            prog.step_ptr.copy_(sp_keep)
+            prog.run()
+            eps_eager = prog.eps.clone()
+            cap_vs_eager = float(((eps_graph.double() - eps_eager.double()).norm() / eps_eager.double().norm().clamp_min(1e-30)).item())
+            finite = finite and bool(torch.isfinite(eps_graph).all().item()) and float(eps_graph.abs().sum().item()) > 0.0
+            checksum = eps_graph.double().sum().reshape(1)
     if dist is not None:      # data parallel, N > 1: one checksum of the captured step's noise prediction per rank
-        allc = [torch.zeros_like(checksum) for _ in range(world)]
-        dist.all_gather(allc, checksum)
-        rank_checksums = [float(c.item()) for c in allc]
-        fin = torch.tensor([1.0 if (finite and cap_vs_eager == 0.0) else 0.0], device=dev)
+        if args.full:
+            allc = [torch.zeros_like(checksum) for _ in range(world)]
+            dist.all_gather(allc, checksum)
+            rank_checksums = [float(c.item()) for c in allc]
+        fin = torch.tensor([1.0 if (finite and cap_vs_eager in (None, 0.0)) else 0.0], device=dev)
         dist.all_reduce(fin, op=dist.ReduceOp.MIN)
         finite = bool(fin.item() > 0.5)
-    else:
+    elif args.full:
         rank_checksums = [float(checksum.item())]
 
     unet_flops = prog.flops
@@ -749,7 +767,7 @@ def main():
                                    + ("effective 264.66M U-Net (128x(1,2,4,4), latent 8)" if args.model == "effective"
                                       else "legacy 163.4M U-Net (128x(1,2,4), latent 4)")
                                    + ", one volume per GPU, hipGraph-captured step",
-                       "volumes_per_gpu": n, "parallelism": f"dp{world}", "finite_outputs": finite,
+                       "volumes_per_gpu": n, "parallelism": f"dp{world}", "full": args.full, "finite_outputs": finite,
                        "captured_vs_eager_rel_l2": cap_vs_eager, "eps_checksum_per_rank": rank_checksums,
                        "unet_tflop_per_step": unet_flops / 1e12,
                        "unet_tflops_achieved_per_gpu": unet_flops * args.steps / dt / 1e12},
@@ -757,7 +775,7 @@ def main():
             "cpu_baseline": None if (args.no_cpu or world > 1) else cpu_baseline(args.cpu_threads, args.hw // 4,
                                                                                   args.depth_out, args.cpu_config1),
             "volume_wall_s": volume_wall, "volume_wall_first_call_s": volume_wall_first,
-            "volume_sampler": (f"ddim-{args.ddim_steps}" if args.sampler == "ddim" else "ddpm-1000"),
+            "volume_sampler": None if volume_wall is None else (f"ddim-{args.ddim_steps}" if args.sampler == "ddim" else "ddpm-1000"),
             "vae": vae_legs if (not args.no_volume and world == 1) else None,
         }
         print(json.dumps(res))
