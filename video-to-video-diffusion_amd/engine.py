@@ -18,7 +18,7 @@ import contextlib
 import ctypes as C
 import os
 import weakref
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -1034,6 +1034,36 @@ class Program:
 # ==========================================================================================================
 # U-Net
 # ==========================================================================================================
+class SamplerStep(NamedTuple):
+    """How a sampler kind's update is called: the ctsi_<entry> / ctsi_<entry>_f32 pair and its optional operands."""
+    entry: str
+    noise: bool         # takes the fp32 NCDHW noise (may still be NULL at run time)
+    hist: bool          # takes a persistent fp32 NDHWC history buffer of z's shape
+    nonfinite: bool     # takes the nonfinite table
+
+
+# Every sampler update.  A new sampler adds one row here and one branch in sampler._step_plan.
+SAMPLER_STEPS = {
+    "ddim": SamplerStep("ddim_step", noise=True, hist=False, nonfinite=True),
+    "ddpm": SamplerStep("ddpm_step", noise=True, hist=False, nonfinite=False),
+    "dpmpp": SamplerStep("dpm_step", noise=False, hist=True, nonfinite=True),      # history: x0_{i-1}
+    "heun": SamplerStep("heun_step", noise=True, hist=True, nonfinite=True),       # history: the predictor's D1
+}
+
+
+def sampler_step_launcher(lib, kind: str, f32: bool) -> Callable:
+    """The update of `kind` behind one argument list, (z, eps, hist, noise, zin, c_total, coef, step_ptr, n, L, d, h,
+    w, nonfinite, stream); operands the entry does not take are dropped.  `f32`: the entry that writes an fp32 zin."""
+    s = SAMPLER_STEPS[kind]
+    fn = getattr(lib, s.entry + ("_f32" if f32 else ""))
+
+    def launch(z, eps, hist, noise, zin, c_total, coef, step_ptr, n, L, d, h, w, nonfinite, stream):
+        ops = [z, eps] + ([hist] if s.hist else []) + ([noise] if s.noise else [])
+        tail = [nonfinite] if s.nonfinite else []
+        fn(*ops, zin, c_total, 0, coef, step_ptr, n, L, d, h, w, *tail, stream)
+    return launch
+
+
 class UNetProgram(Program):
     """One U-Net evaluation (models/unet3d.py:357-413) at a fixed latent shape, followed optionally by
     a sampler update; `step_ptr` selects the timestep row, so one captured graph serves all steps."""
@@ -1201,45 +1231,41 @@ class UNetProgram(Program):
                                         self.ctx.sptr)
         return out
 
+    def _sampler_zin(self):
+        """The U-Net input slice the sampler update writes the new z into: (pointer, channels per voxel, bytes per
+        element, fp32 entry).  Here the z half of the bf16 [z | cond] tensor."""
+        return self.xin.ip, 2 * self.L, 2, False
+
     def add_sampler_step(self, kind: str, with_noise: bool):
-        """Append the DDIM/DDPM/DPM-Solver++/Heun update and the step-counter increment (done once, before capture).
-        'heun': one update per U-Net evaluation (predictor, corrector or final row); `with_noise` = churn on."""
+        """Append the update of sampler `kind` (a SAMPLER_STEPS key) and the step-counter increment (done once, before
+        capture).  'heun': one update per U-Net evaluation (predictor, corrector or final row); `with_noise` = churn on."""
         lib, sptr = self.lib, self.ctx.sptr
         n, L, d, h, w = self.n, self.L, self.d, self.h, self.w
+        entry = SAMPLER_STEPS[kind]
         if with_noise and self.noise is None:
             self.noise = self.persistent((n, L, d, h, w), torch.float32, zero=True)
-        zp, ep, xp, cp, sp = _ptr(self.z), _ptr(self.eps), self.xin.ip, _ptr(self.coef), _ptr(self.step_ptr)
+        xp, c_total, zin_bytes, f32 = self._sampler_zin()
+        step = sampler_step_launcher(lib, kind, f32)
+        zp, ep, cp, sp = _ptr(self.z), _ptr(self.eps), _ptr(self.coef), _ptr(self.step_ptr)
         npz = _ptr(self.noise if with_noise else None)
         # what the reference's NaN/Inf checkpoints would report: rows 0..max_rows-1 = per step {noise_pred, z_0_pred, z}
         # x {NaN, Inf}; the two extra rows = initial noise and conditioning (sampler.py:268-275).  Read once per sample().
         self.nonfinite = self.persistent((self.max_rows + 2, 6), torch.int32, zero=True)
         nfp = _ptr(self.nonfinite)
-        if kind == "dpmpp":
-            # the multistep history x0_{i-1} (fp32 NDHWC, zeroed: ctsi_dpm_step only ever stores finite values in it)
-            self.x0_prev = self.persistent((n, d, h, w, L), torch.float32, zero=True)
-            x0p = _ptr(self.x0_prev)
-        if kind == "heun":
-            # the predictor's data prediction D1 (fp32 NDHWC, zeroed: ctsi_heun_step only ever stores finite values in it)
-            self.d1 = self.persistent((n, d, h, w, L), torch.float32, zero=True)
-            d1p = _ptr(self.d1)
-
+        # the kind's history (fp32 NDHWC, zeroed: the update only ever stores finite values in it)
+        self.hist = self.persistent((n, d, h, w, L), torch.float32, zero=True) if entry.hist else None
+        hp = _ptr(self.hist)
         xin = self.xin
 
         def run_step():
-            if kind == "heun":
-                lib.heun_step(zp, ep, d1p, npz, xp, 2 * L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
-            elif kind == "dpmpp":
-                lib.dpm_step(zp, ep, x0p, xp, 2 * L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
-            elif kind == "ddim":
-                lib.ddim_step(zp, ep, npz, xp, 2 * L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
-            else:
-                lib.ddpm_step(zp, ep, npz, xp, 2 * L, 0, cp, sp, n, L, d, h, w, sptr)
-            xin.dirty = True
+            step(zp, ep, hp, npz, xp, c_total, cp, sp, n, L, d, h, w, nfp, sptr)
+            if not f32:
+                xin.dirty = True
 
         def run_adv():
             lib.step_advance(sp, sptr)
 
-        step_bytes = (4 + 4 + 4 + 2 + (4 if with_noise else 0) + (8 if kind in ("dpmpp", "heun") else 0)) * float(
+        step_bytes = (4 + 4 + 4 + zin_bytes + (4 if with_noise else 0) + (8 if entry.hist else 0)) * float(
             n * L * d * h * w)
         self._emit(run_step, "sampler.step", nbytes=step_bytes)
         self._emit(run_adv, "sampler.advance")

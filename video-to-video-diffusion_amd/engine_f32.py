@@ -10,8 +10,8 @@ capture and launch machinery (one captured hipGraph per sampler step); only the 
   GroupNorm     ctsi_gn_colsum_f32 / conv column sums -> ctsi_gn_finalize (fp64) -> ctsi_gn_apply_f32
   attention     fast mode only: ctsi_attn_depthsum_f32 / _normsum_f32, the folded (proj_out . W_v) matrix (fp64 product,
                 rounded once) as one fp32 1x1x1 conv, ctsi_attn_broadcast_add_f32
-  sampler       ctsi_ddim_step_f32 / ctsi_ddpm_step_f32 / ctsi_dpm_step_f32 / ctsi_heun_step_f32 (the U-Net's z input
-                written in fp32)
+  sampler       the `_f32` entry of every engine.SAMPLER_STEPS row (the U-Net's z input written in fp32): the update
+                is engine.UNetProgram.add_sampler_step, only the input slice differs (_sampler_zin)
 
 Not supported here (CtsiError): depth sharding, attention_mode='exact', training.  There is no torch conv, MIOpen or BLAS
 call on this path: torch allocates and copies.
@@ -288,40 +288,8 @@ class UNetProgramF32(_F32Ops, UNetProgram):
             lib.ncdhw_f32_to_ndhwc_f32(_ptr(cnd), _ptr(self.xin2.t), n, L, d, h, w, sptr)
             cnd.record_stream(self.ctx.stream)
 
-    def add_sampler_step(self, kind: str, with_noise: bool):
-        lib, sptr = self.lib, self.ctx.sptr
-        n, L, d, h, w = self.n, self.L, self.d, self.h, self.w
-        if with_noise and self.noise is None:
-            self.noise = self.persistent((n, L, d, h, w), torch.float32, zero=True)
-        zp, ep, xp, cp, sp = _ptr(self.z), _ptr(self.eps), _ptr(self.xin.t), _ptr(self.coef), _ptr(self.step_ptr)
-        npz = _ptr(self.noise if with_noise else None)
-        self.nonfinite = self.persistent((self.max_rows + 2, 6), torch.int32, zero=True)
-        nfp = _ptr(self.nonfinite)
-        if kind == "dpmpp":
-            self.x0_prev = self.persistent((n, d, h, w, L), torch.float32, zero=True)
-            x0p = _ptr(self.x0_prev)
-        if kind == "heun":
-            self.d1 = self.persistent((n, d, h, w, L), torch.float32, zero=True)
-            d1p = _ptr(self.d1)
-
-        def run_step():
-            if kind == "heun":
-                lib.heun_step_f32(zp, ep, d1p, npz, xp, L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
-            elif kind == "dpmpp":
-                lib.dpm_step_f32(zp, ep, x0p, xp, L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
-            elif kind == "ddim":
-                lib.ddim_step_f32(zp, ep, npz, xp, L, 0, cp, sp, n, L, d, h, w, nfp, sptr)
-            else:
-                lib.ddpm_step_f32(zp, ep, npz, xp, L, 0, cp, sp, n, L, d, h, w, sptr)
-
-        def run_adv():
-            lib.step_advance(sp, sptr)
-
-        step_bytes = (4 + 4 + 4 + 4 + (4 if with_noise else 0) + (8 if kind in ("dpmpp", "heun") else 0)) * float(
-            n * L * d * h * w)
-        self._emit(run_step, "sampler.step", nbytes=step_bytes)
-        self._emit(run_adv, "sampler.advance")
-        self.sampler_kind = (kind, with_noise)
+    def _sampler_zin(self):
+        return _ptr(self.xin.t), self.L, 4, True
 
 
 # ==========================================================================================================

@@ -4,23 +4,12 @@ from __future__ import annotations
 
 import torch
 
-from .sampler import DDIMSampler, DDPMSampler, DPMSolverSampler, HeunSampler
+from .sampler import SAMPLERS
 
 
 def _sample(model, z_cond, sampler_type, num_inference_steps, device, progress, noise_fn=None):
-    if sampler_type == 'ddim':
-        return DDIMSampler(model.diffusion, model.unet).sample(z_cond.shape, z_cond, num_inference_steps, device,
-                                                               progress=progress, noise_fn=noise_fn)
-    if sampler_type == 'ddpm':
-        return DDPMSampler(model.diffusion, model.unet).sample(z_cond.shape, z_cond, device, progress=progress,
-                                                               noise_fn=noise_fn)
-    if sampler_type == 'dpmpp_2m':
-        return DPMSolverSampler(model.diffusion, model.unet, order=2).sample(z_cond.shape, z_cond, num_inference_steps,
-                                                                             device, progress=progress, noise_fn=noise_fn)
-    if sampler_type == 'heun':
-        return HeunSampler(model.diffusion, model.unet).sample(z_cond.shape, z_cond, num_inference_steps, device,
-                                                               progress=progress, noise_fn=noise_fn)
-    raise ValueError(f"Unknown sampler type: {sampler_type}")
+    return SAMPLERS[sampler_type](model.diffusion, model.unet, z_cond.shape, z_cond, num_inference_steps, device,
+                                  progress=progress, noise_fn=noise_fn)
 
 
 @torch.no_grad()
@@ -28,7 +17,7 @@ def generate_batch(model, input_videos, sampler_type='ddim', num_inference_steps
                    noise_fn=None):
     """encode -> sample at the input's latent shape (no depth change) -> decode (generate.py:98-155).
     sampler_type: 'ddim', 'ddpm' or (additive) 'dpmpp_2m' or 'heun'."""
-    if sampler_type not in ('ddim', 'ddpm', 'dpmpp_2m', 'heun'):
+    if sampler_type not in SAMPLERS:
         raise ValueError(f"Unknown sampler type: {sampler_type}")
     model.eval()
     model.to(device)

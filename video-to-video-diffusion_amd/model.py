@@ -12,6 +12,7 @@ from .diffusion import GaussianDiffusion
 from .engine import Ctx, nan_to_num_, trilinear_depth
 from .engine_f32 import check_precision
 from .lib import CtsiError
+from .sampler import SAMPLERS
 from .unet3d import UNet3D
 from .vae import VideoVAE
 
@@ -136,7 +137,7 @@ class VideoToVideoDiffusion(nn.Module):
                 return self.generate(v_in, sampler, num_inference_steps, guidance_scale, target_depth, noise_fn)
             finally:
                 self.unet.inference_precision, self.vae.inference_precision = saved
-        if sampler not in ('ddpm', 'ddim', 'dpmpp_2m', 'heun'):
+        if sampler not in SAMPLERS:
             raise ValueError(f"Unknown sampler: {sampler}")
         if not v_in.is_cuda:
             raise CtsiError("generate runs on the HIP engine: move the input to a ROCm device")
@@ -154,21 +155,8 @@ class VideoToVideoDiffusion(nn.Module):
         latent_shape = tuple(z_cond.shape)
         if noise_fn is None:
             torch.randn(latent_shape, device=device)  # model.py:303 draws (and discards) one latent
-        if sampler == 'ddpm':
-            z_0 = self.diffusion.p_sample_loop(self.unet, latent_shape, z_cond, device, progress=True,
-                                               noise_fn=noise_fn)
-        elif sampler == 'heun':
-            from .sampler import HeunSampler
-            z_0 = HeunSampler(self.diffusion, self.unet).sample(latent_shape, z_cond, num_inference_steps, device,
-                                                                noise_fn=noise_fn)
-        elif sampler == 'dpmpp_2m':
-            from .sampler import DPMSolverSampler
-            z_0 = DPMSolverSampler(self.diffusion, self.unet, order=2).sample(latent_shape, z_cond, num_inference_steps,
-                                                                              device, noise_fn=noise_fn)
-        else:
-            from .sampler import DDIMSampler
-            z_0 = DDIMSampler(self.diffusion, self.unet).sample(latent_shape, z_cond, num_inference_steps,
-                                                                device, noise_fn=noise_fn)
+        z_0 = SAMPLERS[sampler](self.diffusion, self.unet, latent_shape, z_cond, num_inference_steps, device,
+                                noise_fn=noise_fn)
         with ctx.scope():
             nan_to_num_(ctx, z_0)
         v_out = self.vae.decode(z_0)

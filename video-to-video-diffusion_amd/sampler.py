@@ -2,15 +2,19 @@
 (DPMSolverSampler) and EDM Heun / Euler on Karras sigmas (HeunSampler), both additive: not in the reference.
 
 One denoising step = one replay of a captured hipGraph holding every kernel of a U-Net evaluation,
-the elementwise x_{t-1} update (ctsi_ddim_step / ctsi_ddpm_step / ctsi_dpm_step / ctsi_heun_step) and the increment of
-the device-side
-step counter.  Per-step scalars (timestep embedding rows, update coefficients) come from device
-tables indexed by that counter, so the same graph serves all steps and the host never synchronises
-inside the loop.  The reference's five isnan/isinf host checks per step are folded into the update
-kernel as unconditional nan_to_num (identity on finite values).
+the elementwise x_{t-1} update (the sampler's engine.SAMPLER_STEPS entry: ctsi_ddim_step / ctsi_ddpm_step /
+ctsi_dpm_step / ctsi_heun_step) and the increment of the device-side step counter.  Per-step scalars (timestep
+embedding rows, update coefficients) come from device tables indexed by that counter, so the same graph serves all
+steps and the host never synchronises inside the loop.  The reference's five isnan/isinf host checks per step are
+folded into the update kernel as unconditional nan_to_num (identity on finite values).
+
+The sampler kinds are data: _step_plan turns a kind and its settings into a StepPlan (coefficient rows, timesteps, noise
+index and trajectory flag per U-Net evaluation, cache key, initial state), which the captured, depth-sharded and
+generic-callable loops read.  Adding a sampler = one _step_plan branch + one engine.SAMPLER_STEPS row (and its kernel).
 """
 from __future__ import annotations
 
+import ctypes as C
 import logging
 import math
 from typing import List, NamedTuple, Optional, Sequence, Tuple
@@ -18,7 +22,8 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .engine import Ctx, UNetProgram, _ptr, check_device_errors, nan_to_num_, trilinear_depth
+from .engine import (SAMPLER_STEPS, Ctx, UNetProgram, _ptr, check_device_errors, nan_to_num_, sampler_step_launcher,
+                     trilinear_depth)
 from .engine_f32 import UNetProgramF32, check_precision
 from .lib import CtsiError
 
@@ -34,11 +39,9 @@ def _is_engine_unet(model) -> bool:
     return type(model).__name__ == "UNet3D" and hasattr(model, "program")
 
 
-def _log_nonfinite(kind: str, table: torch.Tensor, steps: int, max_rows: int):
+def _log_nonfinite(table: torch.Tensor, steps: int, max_rows: int):
     """What the reference's five NaN/Inf checkpoints log (inference/sampler.py:268-275, 288-292, 307-311, 331-334), from
     the device-side counters the update kernel keeps: one host read after the loop instead of five syncs per step."""
-    if kind not in ("ddim", "dpmpp", "heun"):
-        return            # the reference's DDPM loop (models/diffusion.py:340-367) has no such checkpoints
     t = table.cpu()
     if not bool(t.any()):
         return
@@ -57,123 +60,10 @@ def _log_nonfinite(kind: str, table: torch.Tensor, steps: int, max_rows: int):
             logger.error(f"[Step {i}/{steps}] NaN/Inf in z after update! NaN: {r[4]}, Inf: {r[5]}")
 
 
-def _run_sampler_generic(diffusion, model, shape, conditioning, ctx, z0, *, kind, t_desc, eta, noise_fn, progress,
-                         trajectory, order=2, eps_trajectory=None, heun=None):
-    """Reverse loop over an ARBITRARY `model(z, t, c) -> eps` callable (the reference's samplers accept any,
-    inference/sampler.py:211-219): the network evaluation is the caller's (any torch code on the ROCm device), the
-    x_{t-1} update with its guards is the engine's ctsi_ddim_step / ctsi_ddpm_step / ctsi_dpm_step.  Not captured: the callable is
-    opaque.  The engine's own UNet3D takes the hipGraph path in run_sampler instead."""
-    if kind == "heun":
-        return _run_heun_generic(model, shape, conditioning, ctx, z0, heun, noise_fn=noise_fn, progress=progress,
-                                 trajectory=trajectory, eps_trajectory=eps_trajectory)
-    import ctypes as C
-    lib, sptr = ctx.lib, ctx.sptr
-    n, L, d, h, w = [int(v) for v in shape]
-    steps = len(t_desc)
-    with_noise = (kind == "ddpm") or eta > 0
-    dev = ctx.device
-    coef = _coef_rows(diffusion, kind, t_desc, eta, order).to(dev, torch.float32).contiguous()
-    z_nd = torch.empty((n, d, h, w, L), dtype=torch.float32, device=dev)
-    eps_nd = torch.empty_like(z_nd)
-    x0_prev = torch.zeros_like(z_nd) if kind == "dpmpp" else None
-    step_ptr = torch.zeros(1, dtype=torch.int32, device=dev)
-    nonfinite = torch.zeros((steps + 2, 6), dtype=torch.int32, device=dev)
-    cond = conditioning.to(dev)
-    z = z0.to(dev, torch.float32).contiguous()
-    with ctx.scope():
-        lib.count_nonfinite_f32(_ptr(z), z.numel(), 1, C.c_void_p(nonfinite.data_ptr() + steps * 24), sptr)
-        cf = cond.float().contiguous()
-        lib.count_nonfinite_f32(_ptr(cf), cf.numel(), 0, C.c_void_p(nonfinite.data_ptr() + (steps + 1) * 24), sptr)
-    it = range(steps)
-    if progress and tqdm is not None:
-        it = tqdm(it, desc=f"{kind.upper()} Sampling", total=steps)
-    for i in it:
-        t = torch.full((n,), int(t_desc[i]), device=dev, dtype=torch.long)
-        eps = model(z, t, cond)
-        if not (torch.is_tensor(eps) and tuple(eps.shape) == tuple(shape) and eps.is_cuda):
-            raise CtsiError("the model callable must return a ROCm tensor of the latent's shape "
-                            f"{tuple(shape)}, got {type(eps).__name__} {tuple(getattr(eps, 'shape', ()))}")
-        eps = eps.detach().to(torch.float32).contiguous()
-        if eps_trajectory is not None:
-            eps_trajectory.append(eps.clone())
-        noise = None
-        if with_noise:
-            noise = (noise_fn(i, tuple(shape)) if noise_fn is not None else torch.randn(tuple(shape), device=dev))
-            noise = noise.to(dev, torch.float32).contiguous()
-        with ctx.scope():
-            lib.ncdhw_f32_to_ndhwc_f32(_ptr(z), _ptr(z_nd), n, L, d, h, w, sptr)
-            lib.ncdhw_f32_to_ndhwc_f32(_ptr(eps), _ptr(eps_nd), n, L, d, h, w, sptr)
-            if kind == "dpmpp":
-                lib.dpm_step(_ptr(z_nd), _ptr(eps_nd), _ptr(x0_prev), None, 0, 0, _ptr(coef), _ptr(step_ptr), n, L, d, h,
-                             w, _ptr(nonfinite), sptr)
-            elif kind == "ddim":
-                lib.ddim_step(_ptr(z_nd), _ptr(eps_nd), _ptr(noise), None, 0, 0, _ptr(coef), _ptr(step_ptr), n, L, d, h, w,
-                              _ptr(nonfinite), sptr)
-            else:
-                lib.ddpm_step(_ptr(z_nd), _ptr(eps_nd), _ptr(noise), None, 0, 0, _ptr(coef), _ptr(step_ptr), n, L, d, h, w,
-                              sptr)
-            lib.step_advance(_ptr(step_ptr), sptr)
-            z = torch.empty((n, L, d, h, w), dtype=torch.float32, device=dev)
-            lib.ndhwc_f32_to_ncdhw_f32(_ptr(z_nd), _ptr(z), n, L, d, h, w, sptr)
-        if trajectory is not None:
-            trajectory.append(z.clone())
-    _log_nonfinite(kind, nonfinite, steps, steps)
-    return z
-
-
 def _check_eps(eps, shape):
     if not (torch.is_tensor(eps) and tuple(eps.shape) == tuple(shape) and eps.is_cuda):
         raise CtsiError("the model callable must return a ROCm tensor of the latent's shape "
                         f"{tuple(shape)}, got {type(eps).__name__} {tuple(getattr(eps, 'shape', ()))}")
-
-
-def _run_heun_generic(model, shape, conditioning, ctx, z0, plan, *, noise_fn, progress, trajectory, eps_trajectory):
-    """The generic-callable loop for 'heun': one ctsi_heun_step_f32 per evaluation.  The model sees the fractional
-    timestep of every evaluation as an fp32 tensor (the reference embeds t as a float); its input after a predictor
-    row is the corrector's z', which the update writes to `zin` (z keeps zhat)."""
-    import ctypes as C
-    lib, sptr = ctx.lib, ctx.sptr
-    n, L, d, h, w = [int(v) for v in shape]
-    evals = len(plan.t)
-    dev = ctx.device
-    coef = plan.rows.to(dev, torch.float32).contiguous()
-    z_nd = torch.empty((n, d, h, w, L), dtype=torch.float32, device=dev)
-    zin_nd = torch.empty_like(z_nd)
-    eps_nd = torch.empty_like(z_nd)
-    d1 = torch.zeros_like(z_nd)
-    step_ptr = torch.zeros(1, dtype=torch.int32, device=dev)
-    nonfinite = torch.zeros((evals + 2, 6), dtype=torch.int32, device=dev)
-    cond = conditioning.to(dev)
-    z = z0.to(dev, torch.float32).contiguous()
-    with ctx.scope():
-        lib.count_nonfinite_f32(_ptr(z), z.numel(), 1, C.c_void_p(nonfinite.data_ptr() + evals * 24), sptr)
-        cf = cond.float().contiguous()
-        lib.count_nonfinite_f32(_ptr(cf), cf.numel(), 0, C.c_void_p(nonfinite.data_ptr() + (evals + 1) * 24), sptr)
-        lib.ncdhw_f32_to_ndhwc_f32(_ptr(z), _ptr(z_nd), n, L, d, h, w, sptr)
-    it = range(evals)
-    if progress and tqdm is not None:
-        it = tqdm(it, desc="HEUN Sampling", total=evals)
-    for e in it:
-        t = torch.full((n,), float(plan.t[e]), device=dev, dtype=torch.float32)
-        eps = model(z, t, cond)
-        _check_eps(eps, shape)
-        eps = eps.detach().to(torch.float32).contiguous()
-        if eps_trajectory is not None:
-            eps_trajectory.append(eps.clone())
-        noise = None
-        if plan.noise_step[e] >= 0:
-            noise = _draw_noise(noise_fn, plan.noise_step[e], shape, dev).contiguous()
-        with ctx.scope():
-            lib.ncdhw_f32_to_ndhwc_f32(_ptr(eps), _ptr(eps_nd), n, L, d, h, w, sptr)
-            lib.heun_step_f32(_ptr(z_nd), _ptr(eps_nd), _ptr(d1), _ptr(noise), _ptr(zin_nd), L, 0, _ptr(coef),
-                              _ptr(step_ptr), n, L, d, h, w, _ptr(nonfinite), sptr)
-            lib.step_advance(_ptr(step_ptr), sptr)
-            z = torch.empty((n, L, d, h, w), dtype=torch.float32, device=dev)
-            lib.ndhwc_f32_to_ncdhw_f32(_ptr(zin_nd), _ptr(z), n, L, d, h, w, sptr)
-        if trajectory is not None and plan.closes[e]:
-            trajectory.append(z.clone())
-    _log_nonfinite("heun", nonfinite, evals, evals)
-    return z
 
 
 def _draw_noise(noise_fn, i, shape, dev) -> torch.Tensor:
@@ -368,14 +258,124 @@ def heun_coef_rows(alphas_cumprod: torch.Tensor, sigmas: Sequence[float], order:
                     init=(sig[0] / A0, churn[0] / A0))
 
 
-def _coef_rows(diffusion, kind: str, t_desc: Sequence[int], eta: float, order: int, heun=None) -> torch.Tensor:
+class StepPlan(NamedTuple):
+    """One sampling run as data, per U-Net evaluation e (E = len(t)).  run_sampler, run_sampler_sharded and the
+    generic-callable loop read it and never test the sampler kind; only _step_plan builds one."""
+    kind: str                       # the engine.SAMPLER_STEPS row of the update (and the progress-bar label)
+    coef: torch.Tensor              # (E, 8) update coefficient rows
+    t: tuple                        # (E,) timestep: int (ddim, ddpm, dpmpp) or float (heun)
+    t_dtype: torch.dtype            # the generic callable's t: torch.long, or torch.float32 (heun, integral or not)
+    noise_step: Tuple[int, ...]     # (E,) the noise_fn index consumed before evaluation e's update, or -1
+    closes: Tuple[bool, ...]        # (E,) evaluation e completes a step (gets a trajectory entry)
+    with_noise: bool                # the step program holds a noise buffer
+    logs_nonfinite: bool            # the reference logs NaN / Inf for this sampler (its DDPM loop does not)
+    key: tuple                      # (kind, with_noise): the sampler's part of the program cache keys ...
+    key_order: tuple                # ... and their last element: (order,) for dpmpp / heun, else ()
+    init: Optional[Tuple[float, float]] = None     # z_0 = init[0] eps + init[1] eps_0; None: z_0 = eps
+    init_noise: bool = False                       # eps_0 = noise_fn(0, shape) is drawn (step 0 churns)
+
+    def initial_state(self, z0: torch.Tensor, noise_fn, shape, dev) -> torch.Tensor:
+        """The loop's start from the initial draw eps = z0 (Heun's zhat_0 is formed in float64)."""
+        if self.init is None:
+            return z0
+        zh = self.init[0] * z0.to(dev, torch.float64)
+        if self.init_noise:
+            zh += self.init[1] * _draw_noise(noise_fn, 0, shape, dev).double()
+        return zh.float()
+
+
+def _step_plan(diffusion, kind: str, t_desc: Sequence, eta: float, order: int, heun: Optional[HeunRows]) -> StepPlan:
+    """The only place that branches on the sampler kind.  A new sampler adds one branch here and one row to
+    engine.SAMPLER_STEPS (its update entry and operands).  'heun' takes the rows `heun` (t_desc = heun.t)."""
+    E = len(t_desc)
     if kind == "heun":
-        return heun.rows
-    if kind == "dpmpp":
-        return dpm_coef_rows(diffusion.alphas_cumprod, t_desc, order)
+        if heun is None or len(heun.t) != E:
+            raise ValueError("kind='heun' needs the rows of heun_coef_rows(...) (heun=) and t_desc = heun.t")
+        with_noise = bool((heun.gammas > 0).any())        # churn on
+        return StepPlan(kind, heun.rows, tuple(float(t) for t in t_desc), torch.float32, tuple(heun.noise_step),
+                        tuple(heun.closes), with_noise, True, (kind, with_noise), (order,), init=heun.init,
+                        init_noise=bool(heun.gammas[0] > 0))
     if kind == "ddim":
-        return ddim_coef_rows(diffusion.alphas_cumprod, t_desc, eta)
-    return diffusion.ddpm_coef_rows(t_desc)
+        coef = ddim_coef_rows(diffusion.alphas_cumprod, t_desc, eta)
+    elif kind == "ddpm":
+        coef = diffusion.ddpm_coef_rows(t_desc)
+    elif kind == "dpmpp":
+        coef = dpm_coef_rows(diffusion.alphas_cumprod, t_desc, order)
+    else:
+        raise ValueError(f"unknown sampler kind {kind!r}: expected 'ddim', 'ddpm', 'dpmpp' or 'heun'")
+    with_noise = kind == "ddpm" or eta > 0
+    return StepPlan(kind, coef, tuple(int(t) for t in t_desc), torch.long,
+                    tuple(range(E)) if with_noise else (-1,) * E, (True,) * E, with_noise, kind != "ddpm",
+                    (kind, with_noise), (order,) if kind == "dpmpp" else ())
+
+
+def _progress(plan: StepPlan, progress: bool):
+    it = range(len(plan.t))
+    if progress and tqdm is not None:
+        it = tqdm(it, desc=f"{plan.kind.upper()} Sampling", total=len(plan.t))
+    return it
+
+
+def _replay(plan: StepPlan, evals, load_noise, launch):
+    """The per-evaluation body of the step-program loops (run_sampler, run_sampler_sharded): the noise the update
+    consumes is loaded first (load_noise(noise_fn index)), then one launch.  Yields closes[e]: the caller records a
+    trajectory entry on the evaluations that complete a step."""
+    for e in evals:
+        if plan.noise_step[e] >= 0:
+            load_noise(plan.noise_step[e])
+        launch()
+        yield plan.closes[e]
+
+
+def _run_generic(plan: StepPlan, model, shape, conditioning, ctx, z0, *, noise_fn, progress, trajectory,
+                 eps_trajectory):
+    """Reverse loop over an ARBITRARY `model(z, t, c) -> eps` callable (the reference's samplers accept any,
+    inference/sampler.py:211-219): the network evaluation is the caller's (any torch code on the ROCm device), the
+    update with its guards is the engine's `_f32` entry of the plan's kind, once per evaluation.  Not captured: the
+    callable is opaque.  The engine's own UNet3D takes the hipGraph path in run_sampler instead.
+    The model sees t as plan.t_dtype (Heun's fractional timesteps as fp32, as the reference embeds t) and as z the
+    input the update writes to `zin`: the new state, or after a Heun predictor row the corrector's z' (z keeps zhat)."""
+    lib, sptr = ctx.lib, ctx.sptr
+    n, L, d, h, w = [int(v) for v in shape]
+    evals = len(plan.t)
+    dev = ctx.device
+    step = sampler_step_launcher(lib, plan.kind, f32=True)
+    coef = plan.coef.to(dev, torch.float32).contiguous()
+    z_nd = torch.empty((n, d, h, w, L), dtype=torch.float32, device=dev)
+    zin_nd = torch.empty_like(z_nd)
+    eps_nd = torch.empty_like(z_nd)
+    hist = torch.zeros_like(z_nd) if SAMPLER_STEPS[plan.kind].hist else None
+    step_ptr = torch.zeros(1, dtype=torch.int32, device=dev)
+    nonfinite = torch.zeros((evals + 2, 6), dtype=torch.int32, device=dev)
+    cond = conditioning.to(dev)
+    z = z0.to(dev, torch.float32).contiguous()
+    with ctx.scope():
+        lib.count_nonfinite_f32(_ptr(z), z.numel(), 1, C.c_void_p(nonfinite.data_ptr() + evals * 24), sptr)
+        cf = cond.float().contiguous()
+        lib.count_nonfinite_f32(_ptr(cf), cf.numel(), 0, C.c_void_p(nonfinite.data_ptr() + (evals + 1) * 24), sptr)
+        lib.ncdhw_f32_to_ndhwc_f32(_ptr(z), _ptr(z_nd), n, L, d, h, w, sptr)
+    for e in _progress(plan, progress):
+        t = torch.full((n,), plan.t[e], device=dev, dtype=plan.t_dtype)
+        eps = model(z, t, cond)
+        _check_eps(eps, shape)
+        eps = eps.detach().to(torch.float32).contiguous()
+        if eps_trajectory is not None:
+            eps_trajectory.append(eps.clone())
+        noise = None
+        if plan.noise_step[e] >= 0:
+            noise = _draw_noise(noise_fn, plan.noise_step[e], shape, dev).contiguous()
+        with ctx.scope():
+            lib.ncdhw_f32_to_ndhwc_f32(_ptr(eps), _ptr(eps_nd), n, L, d, h, w, sptr)
+            step(_ptr(z_nd), _ptr(eps_nd), _ptr(hist), _ptr(noise), _ptr(zin_nd), L, _ptr(coef), _ptr(step_ptr), n, L,
+                 d, h, w, _ptr(nonfinite), sptr)
+            lib.step_advance(_ptr(step_ptr), sptr)
+            z = torch.empty((n, L, d, h, w), dtype=torch.float32, device=dev)
+            lib.ndhwc_f32_to_ncdhw_f32(_ptr(zin_nd), _ptr(z), n, L, d, h, w, sptr)
+        if trajectory is not None and plan.closes[e]:
+            trajectory.append(z.clone())
+    if plan.logs_nonfinite:
+        _log_nonfinite(nonfinite, evals, evals)
+    return z
 
 
 def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, t_desc, eta, noise_fn, comm,
@@ -393,43 +393,37 @@ def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, 
     import os
     from .engine import cached_program
     from .parallel import ShardSpec
+    plan = _step_plan(diffusion, kind, t_desc, eta, order, heun)
     n, L, d, h, w = [int(v) for v in shape]
     spec = ShardSpec(comm.rank, comm.world, comm, d)
-    dl = spec.depth_local
-    with_noise = _with_noise(kind, eta, heun)
-    steps = len(t_desc)
+    dl, lo = spec.depth_local, spec.depth_start
     capture = bool(getattr(comm, "capturable", False)) and os.environ.get("CTSI_SHARD_CAPTURE") == "1"
-    outs, trajs = [], [[] for _ in range(sum(heun.closes) if kind == "heun" else steps)]
+    outs, trajs = [], [[] for _ in range(sum(plan.closes))]
     with ctx.scope():
-        key = ("sampler-shard", ctx.device.index, 1, d, h, w, comm.rank, comm.world, kind, with_noise)
-        if kind in ("dpmpp", "heun"):
-            key += (order,)
+        key = ("sampler-shard", ctx.device.index, 1, d, h, w, comm.rank, comm.world) + plan.key + plan.key_order
 
         def build():
             prog = UNetProgram(ctx, unet, 1, dl, h, w, diffusion.timesteps + 1, "fast", shard=spec)
-            prog.add_sampler_step(kind, with_noise)
+            prog.add_sampler_step(plan.kind, plan.with_noise)
             return prog
 
         prog = cached_program(unet, key, build)
-        coef = _coef_rows(diffusion, kind, t_desc, eta, order, heun)
-        lo = spec.depth_start
         noises = {}
         for b in range(n):
+            def load_noise(i, b=b):
+                if i not in noises:   # one draw per step for the whole batch, as the unsharded loop makes it
+                    noises[i] = (noise_fn(i, tuple(shape)) if noise_fn is not None
+                                 else torch.randn(tuple(shape), device=ctx.device))
+                prog.noise.copy_(noises[i][b:b + 1, :, lo:lo + dl].to(ctx.device, torch.float32))
+
             prog.load_latents(z0[b:b + 1], conditioning[b:b + 1])
-            prog.set_schedule(t_desc if kind == "heun" else [int(t) for t in t_desc], coef.to(ctx.device))
+            prog.set_schedule(list(plan.t), plan.coef.to(ctx.device))
             if capture and prog.graph is None:
                 prog.capture()
                 prog.step_ptr.zero_()
             done = 0
-            for i in range(steps):
-                ni = (heun.noise_step[i] if kind == "heun" else i) if with_noise else -1
-                if ni >= 0:
-                    if ni not in noises:   # one draw per step for the whole batch, as the unsharded loop makes it
-                        noises[ni] = (noise_fn(ni, tuple(shape)) if noise_fn is not None
-                                      else torch.randn(tuple(shape), device=ctx.device))
-                    prog.noise.copy_(noises[ni][b:b + 1, :, lo:lo + dl].to(ctx.device, torch.float32))
-                prog.launch() if capture else prog.run()
-                if trajectory is not None and (kind != "heun" or heun.closes[i]):
+            for closes in _replay(plan, range(len(plan.t)), load_noise, prog.launch if capture else prog.run):
+                if trajectory is not None and closes:
                     trajs[done].append(comm.gather_depth(comm.rank, prog.z_ncdhw(), counts=spec.depth_counts))
                     done += 1
             outs.append(comm.gather_depth(comm.rank, prog.z_ncdhw(), counts=spec.depth_counts))
@@ -439,12 +433,6 @@ def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, 
         torch.cuda.current_stream(ctx.device).synchronize()
         check_device_errors(ctx)
         return res
-
-
-def _with_noise(kind: str, eta: float, heun) -> bool:
-    if kind == "heun":
-        return bool((heun.gammas > 0).any())        # churn on
-    return (kind == "ddpm") or eta > 0
 
 
 def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_desc: Sequence[int],
@@ -457,16 +445,13 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
     'heun': `trajectory` receives the state after every completed step (the VP latent zhat_{i+1}, which already holds
     step i+1's churn; the output last); the initial draw eps becomes zhat_0 = (sigma_0 eps + churn_0 eps_0) / a(sigma_hat_0),
     eps_0 = noise_fn(0, shape) drawn only when step 0 churns."""
-    if kind == "heun" and (heun is None or len(heun.t) != len(t_desc)):
-        raise ValueError("kind='heun' needs the rows of heun_coef_rows(...) (heun=) and t_desc = heun.t")
+    plan = _step_plan(diffusion, kind, t_desc, eta, order, heun)
     if not _is_engine_unet(model) and not callable(model):
         raise CtsiError(f"the samplers need a model(z, t, c) callable; got {type(model).__name__}")
     unet = model
     device = torch.device(device)
     ctx = Ctx.get(device if device.type == "cuda" else conditioning.device)
     n, L, d, h, w = [int(v) for v in shape]
-    steps = len(t_desc)
-    with_noise = _with_noise(kind, eta, heun)
     max_rows = (diffusion.timesteps + 1) * n
     # initial noise is drawn exactly where the reference draws it (on the caller's stream/generator)
     if z_init is not None:
@@ -475,15 +460,10 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
         z0 = noise_fn(-1, tuple(shape)).to(ctx.device)
     else:
         z0 = torch.randn(tuple(shape), device=ctx.device)
-    if kind == "heun":
-        zh = heun.init[0] * z0.to(ctx.device, torch.float64)
-        if heun.gammas[0] > 0:
-            zh += heun.init[1] * _draw_noise(noise_fn, 0, shape, ctx.device).double()
-        z0 = zh.float()
+    z0 = plan.initial_state(z0, noise_fn, shape, ctx.device)
     if not _is_engine_unet(model):
-        return _run_sampler_generic(diffusion, model, shape, conditioning, ctx, z0, kind=kind, t_desc=t_desc, eta=eta,
-                                    noise_fn=noise_fn, progress=progress, trajectory=trajectory, order=order,
-                                    eps_trajectory=eps_trajectory, heun=heun)
+        return _run_generic(plan, model, shape, conditioning, ctx, z0, noise_fn=noise_fn, progress=progress,
+                            trajectory=trajectory, eps_trajectory=eps_trajectory)
     precision = check_precision(getattr(unet, "inference_precision", "bf16"))
     comm = getattr(unet, "depth_shard_comm", None)
     if comm is not None and comm.world > 1:
@@ -495,20 +475,18 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
         return run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, kind=kind, t_desc=t_desc, eta=eta,
                                    noise_fn=noise_fn, comm=comm, trajectory=trajectory, order=order, heun=heun)
     with ctx.scope():
-        key = ("sampler", ctx.device.index, n, d, h, w, max_rows, kind, with_noise, unet.attention_mode, precision)
-        if kind in ("dpmpp", "heun"):
-            key += (order,)
+        key = (("sampler", ctx.device.index, n, d, h, w, max_rows) + plan.key + (unet.attention_mode, precision)
+               + plan.key_order)
         from .engine import cached_program
 
         def build():
             cls = UNetProgramF32 if precision == "fp32" else UNetProgram
             prog = cls(ctx, unet, n, d, h, w, max_rows, unet.attention_mode)
-            prog.add_sampler_step(kind, with_noise)
+            prog.add_sampler_step(plan.kind, plan.with_noise)
             return prog
 
         prog: UNetProgram = cached_program(unet, key, build)
         prog.load_latents(z0, conditioning)
-        import ctypes as C
         prog.nonfinite.zero_()
         nf_tail = prog.nonfinite.data_ptr() + prog.max_rows * 24
         # sampler.py:268-275: checkpoint 1 sanitises the initial noise (identity on finite values), checkpoint 2 only
@@ -517,45 +495,67 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
         cnd = conditioning.detach().to(ctx.device, torch.float32).contiguous()
         ctx.lib.count_nonfinite_f32(_ptr(cnd), cnd.numel(), 0, C.c_void_p(nf_tail + 24), ctx.sptr)
         cnd.record_stream(ctx.stream)
-        coef = _coef_rows(diffusion, kind, t_desc, eta, order, heun)
-        if kind == "heun":
-            t_rows = [float(t) for t in t_desc for _ in range(n)]
-        else:
-            t_rows = [int(t) for t in t_desc for _ in range(n)]
-        prog.set_schedule(t_rows, coef.to(ctx.device))
+        prog.set_schedule([t for t in plan.t for _ in range(n)], plan.coef.to(ctx.device))
         if prog.graph is None:
             # one eager warm-up step is not needed: capture records launches without executing them
             prog.capture()
             prog.step_ptr.zero_()
-        it = range(steps)
-        if progress and tqdm is not None:
-            it = tqdm(it, desc=f"{kind.upper()} Sampling", total=steps)
-        for i in it:
-            # 'heun': row i consumes step heun.noise_step[i]'s churn noise (only closing rows followed by a churning step)
-            ni = (heun.noise_step[i] if kind == "heun" else i) if with_noise else -1
-            if ni >= 0:
-                if noise_fn is not None:
-                    prog.noise.copy_(noise_fn(ni, tuple(shape)).to(ctx.device, torch.float32))
-                else:
-                    prog.noise.normal_()
-            prog.launch()
-            if trajectory is not None and (kind != "heun" or heun.closes[i]):
+
+        def load_noise(i):
+            if noise_fn is not None:
+                prog.noise.copy_(noise_fn(i, tuple(shape)).to(ctx.device, torch.float32))
+            else:
+                prog.noise.normal_()
+
+        for closes in _replay(plan, _progress(plan, progress), load_noise, prog.launch):
+            if trajectory is not None and closes:
                 trajectory.append(prog.z_ncdhw())
             if eps_trajectory is not None:
                 eps_trajectory.append(prog.eps_ncdhw())
         out = prog.z_ncdhw()
-        _log_nonfinite(kind, prog.nonfinite, steps, prog.max_rows)     # (one host read: the loop itself never synchronises)
+        if plan.logs_nonfinite:     # (one host read: the loop itself never synchronises)
+            _log_nonfinite(prog.nonfinite, len(plan.t), prog.max_rows)
         check_device_errors(ctx)
         return out
 
 
-class DDPMSampler:
-    """Ancestral sampling over all `diffusion.timesteps` steps (reference sampler.py:17-61)."""
+class _Sampler:
+    """What the samplers share: the model pair, the DDIM timestep list, the blend window and the stitching driver."""
 
     def __init__(self, diffusion, model):
         self.diffusion = diffusion
         self.model = model
         self.timesteps = diffusion.timesteps
+
+    def _get_timesteps(self, num_inference_steps):
+        """arange(0, T, T // N) plus T-1 when the stride misses it, descending — N+1 entries whenever
+        T % N == 0 and N < T (sampler.py:221-239)."""
+        stride = self.timesteps // num_inference_steps
+        ts = np.arange(0, self.timesteps, stride)
+        if ts[-1] != self.timesteps - 1:
+            ts = np.append(ts, self.timesteps - 1)
+        return ts[::-1]
+
+    def _create_gaussian_weight(self, d, h, w):
+        return gaussian_weight(d, h, w)
+
+    def _stitch(self, v_thick_full, vae, num_inference_steps, patch_size, target_patch_size, stride, device, progress,
+                window_batch, dp_group, batchable, **kw):
+        """sample_with_stitching on `num_inference_steps` steps (`kw`: more sample() arguments).  Windows are batched
+        (up to `window_batch`; None / 0: as many as the device memory holds, see _stitched) only when `batchable`, i.e.
+        when the sampler draws no noise after the initial latent."""
+        def sample(shp, cond, z_init=None):
+            return self.sample(shp, cond, num_inference_steps, device, progress=False, z_init=z_init, **kw)
+
+        if window_batch is None:
+            window_batch = 0
+        return _stitched(self, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress, sample,
+                         batched_fn=sample if batchable and window_batch != 1 else None, window_batch=window_batch,
+                         dp_group=dp_group)
+
+
+class DDPMSampler(_Sampler):
+    """Ancestral sampling over all `diffusion.timesteps` steps (reference sampler.py:17-61)."""
 
     @torch.no_grad()
     def sample(self, shape, conditioning, device, progress=True, noise_fn=None, num_steps=None,
@@ -571,26 +571,9 @@ class DDPMSampler:
         return _stitched(self, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress,
                          lambda shp, cond: self.sample(shp, cond, device, progress=False), dp_group=dp_group)
 
-    def _create_gaussian_weight(self, d, h, w):
-        return gaussian_weight(d, h, w)
 
-
-class DDIMSampler:
+class DDIMSampler(_Sampler):
     """Deterministic (eta = 0) or stochastic DDIM over a strided timestep subset (sampler.py:201-336)."""
-
-    def __init__(self, diffusion, model):
-        self.diffusion = diffusion
-        self.model = model
-        self.timesteps = diffusion.timesteps
-
-    def _get_timesteps(self, num_inference_steps):
-        """arange(0, T, T // N) plus T-1 when the stride misses it, descending — N+1 entries whenever
-        T % N == 0 and N < T (sampler.py:221-239)."""
-        stride = self.timesteps // num_inference_steps
-        ts = np.arange(0, self.timesteps, stride)
-        if ts[-1] != self.timesteps - 1:
-            ts = np.append(ts, self.timesteps - 1)
-        return ts[::-1]
 
     @torch.no_grad()
     def sample(self, shape, conditioning, num_inference_steps, device, eta=0.0, progress=True, noise_fn=None,
@@ -611,22 +594,11 @@ class DDIMSampler:
         idle (its coarsest level has 28 conv tiles for 256 CUs).  None / 0 (default): as many as a fifth of the device
         memory holds (13 windows of 48 x 192 x 192 on a 288 GB part); 1: one by one, like the reference.  The initial noise of every window is still drawn
         with its own `torch.randn` call in window order, exactly as the reference's one-by-one loop draws it."""
-        batched = None
-        if window_batch is None:
-            window_batch = 0          # 0 = as many windows per batch as the device memory holds (see _stitched)
-        if float(eta) == 0.0 and window_batch != 1:
-            batched = lambda shp, cond, z_init: self.sample(shp, cond, num_inference_steps, device, eta=0.0,
-                                                            progress=False, z_init=z_init)
-        return _stitched(self, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress,
-                         lambda shp, cond: self.sample(shp, cond, num_inference_steps, device, eta=eta,
-                                                       progress=False),
-                         batched_fn=batched, window_batch=window_batch, dp_group=dp_group)
-
-    def _create_gaussian_weight(self, d, h, w):
-        return gaussian_weight(d, h, w)
+        return self._stitch(v_thick_full, vae, num_inference_steps, patch_size, target_patch_size, stride, device,
+                            progress, window_batch, dp_group, float(eta) == 0.0, eta=eta)
 
 
-class DPMSolverSampler:
+class DPMSolverSampler(_Sampler):
     """DPM-Solver++(2M) (Lu et al. 2022): the training-free multistep ODE solver in data prediction, on the DDIM
     timestep list (N steps = the same N + 1 U-Net evaluations as DDIM-N).  Additive: the reference has no such sampler.
     order=1 is the DDIM (eta = 0) update written in data-prediction form.  Deterministic: no noise is drawn after the
@@ -635,13 +607,8 @@ class DPMSolverSampler:
     def __init__(self, diffusion, model, order=2):
         if order not in (1, 2):
             raise ValueError(f"DPM-Solver++ order must be 1 or 2, got {order}")
-        self.diffusion = diffusion
-        self.model = model
+        super().__init__(diffusion, model)
         self.order = int(order)
-        self.timesteps = diffusion.timesteps
-
-    def _get_timesteps(self, num_inference_steps):
-        return DDIMSampler._get_timesteps(self, num_inference_steps)
 
     @torch.no_grad()
     def sample(self, shape, conditioning, num_inference_steps, device, progress=True, noise_fn=None, trajectory=None,
@@ -657,21 +624,11 @@ class DPMSolverSampler:
                               window_batch=None, dp_group=None):
         """DDIMSampler.sample_with_stitching without `eta`: the same windows, blend, `window_batch` and `dp_group`
         behaviour (the solver is deterministic, so windows are always batchable)."""
-        batched = None
-        if window_batch is None:
-            window_batch = 0
-        if window_batch != 1:
-            batched = lambda shp, cond, z_init: self.sample(shp, cond, num_inference_steps, device, progress=False,
-                                                            z_init=z_init)
-        return _stitched(self, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress,
-                         lambda shp, cond: self.sample(shp, cond, num_inference_steps, device, progress=False),
-                         batched_fn=batched, window_batch=window_batch, dp_group=dp_group)
-
-    def _create_gaussian_weight(self, d, h, w):
-        return gaussian_weight(d, h, w)
+        return self._stitch(v_thick_full, vae, num_inference_steps, patch_size, target_patch_size, stride, device,
+                            progress, window_batch, dp_group, True)
 
 
-class HeunSampler:
+class HeunSampler(_Sampler):
     """EDM sampling (Karras et al. 2022, Algorithm 2): second-order Heun (order=2, 2N - 1 U-Net evaluations) or Euler
     (order=1, N evaluations) steps on freely chosen noise levels -- by default the rho-schedule between sigma_min and
     sigma_max -- with optional stochastic churn.  The U-Net sees the VP latent x / a(sigma) at the fractional timestep
@@ -684,10 +641,8 @@ class HeunSampler:
                  s_tmax=float("inf"), s_noise=1.0):
         if order not in (1, 2):
             raise ValueError(f"the EDM sampler's order must be 1 (Euler) or 2 (Heun), got {order}")
-        self.diffusion = diffusion
-        self.model = model
+        super().__init__(diffusion, model)
         self.order = int(order)
-        self.timesteps = diffusion.timesteps
         table = sigma_table(diffusion.alphas_cumprod)
         self.sigma_min = float(max(0.002, table[0]) if sigma_min is None else sigma_min)
         self.sigma_max = float(min(80.0, table[-1]) if sigma_max is None else sigma_max)
@@ -722,18 +677,18 @@ class HeunSampler:
                               window_batch=None, dp_group=None):
         """DDIMSampler.sample_with_stitching without `eta`: windows are batched when s_churn == 0 and run one by one
         otherwise (each window then draws its own churn noise, as stochastic DDIM does)."""
-        batched = None
-        if window_batch is None:
-            window_batch = 0
-        if self.s_churn == 0.0 and window_batch != 1:
-            batched = lambda shp, cond, z_init: self.sample(shp, cond, num_inference_steps, device, progress=False,
-                                                            z_init=z_init)
-        return _stitched(self, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress,
-                         lambda shp, cond: self.sample(shp, cond, num_inference_steps, device, progress=False),
-                         batched_fn=batched, window_batch=window_batch, dp_group=dp_group)
+        return self._stitch(v_thick_full, vae, num_inference_steps, patch_size, target_patch_size, stride, device,
+                            progress, window_batch, dp_group, self.s_churn == 0.0)
 
-    def _create_gaussian_weight(self, d, h, w):
-        return gaussian_weight(d, h, w)
+
+# generate() / generate_batch() sampler names -> how each samples a latent: (diffusion, model, shape, conditioning,
+# num_inference_steps, device, **sample kwargs).  DDPM runs all T steps: it ignores the step count.
+SAMPLERS = {
+    'ddim': lambda df, m, shape, c, n, dev, **kw: DDIMSampler(df, m).sample(shape, c, n, dev, **kw),
+    'ddpm': lambda df, m, shape, c, n, dev, **kw: DDPMSampler(df, m).sample(shape, c, dev, **kw),
+    'dpmpp_2m': lambda df, m, shape, c, n, dev, **kw: DPMSolverSampler(df, m, order=2).sample(shape, c, n, dev, **kw),
+    'heun': lambda df, m, shape, c, n, dev, **kw: HeunSampler(df, m).sample(shape, c, n, dev, **kw),
+}
 
 
 def gaussian_weight(d: int, h: int, w: int) -> torch.Tensor:
