@@ -138,6 +138,20 @@ double ctsi_conv_plan_flops(const ctsi_conv_plan* plan);
 /* which kernel variant the plan launches: MFMA tile (bm x bn) and staging mode
  * (0: general gather, 1: small-cin tap-packed K, 2: buffer-addressed whole-chunk gather)      */
 int ctsi_conv_plan_config(const ctsi_conv_plan* plan, int* bm, int* bn, int* mode);
+/* which packed-weight image ctsi_conv_plan_pack_weights writes for this plan, as far as the descriptor's channel / kernel
+ * fields, ctsi_conv_plan_cout_pad and the weight cin (ctsi_conv_plan_set_weight_cin) do not already say: bits 0-3 the
+ * kernel family (CTSI_PACK_*); k32 plans add their form << 4 (0 Conv3d 3x3x3, 1 ConvTranspose3d, 2 strided Conv3d), the
+ * cout-permuted direct-store image << 6 and bn / 16 << 8; head plans set bit 4 when the image carries the conv3_head2
+ * part; stream-tail plans add their n-tile count << 8.  Plans of equal descriptor channel / kernel fields, cout_pad, weight
+ * cin and pack layout pack byte-identical images (a cache of packed images may key on exactly these).  0: null plan. */
+#define CTSI_PACK_GATHER 1
+#define CTSI_PACK_GATHER_SMALL 2
+#define CTSI_PACK_HALO 3
+#define CTSI_PACK_K32 4
+#define CTSI_PACK_HEAD 5
+#define CTSI_PACK_STREAM_TAIL 6
+#define CTSI_PACK_STEM 7
+int ctsi_conv_plan_pack_layout(const ctsi_conv_plan* plan);
 /* re-layout reference weights (fp32, PyTorch layout: Conv3d (cout,cin,kd,kh,kw),
  * ConvTranspose3d (cin,cout,kd,kh,kw)) into the kernel's bf16 [class][cout_pad][K] image. */
 int ctsi_conv_plan_pack_weights(const ctsi_conv_plan* plan, const float* w_f32, void* packed,

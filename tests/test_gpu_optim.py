@@ -119,6 +119,63 @@ def test_fast_repack_equals_generic_repack_and_training_continues(pkg):
         assert rel_l2(p1.detach(), p2.detach()) < 5e-2
 
 
+def test_fast_repack_after_parameters_move(pkg):
+    """Every U-Net parameter moved to new storage between two optimizer steps (`p.data = p.data.clone()`): the fast re-pack
+    rebuilds its tables against the NEW addresses -- every operand is still a table entry (none left to the slow path), the
+    images equal the generic re-pack's bit for bit -- and training continues like a torch.optim.AdamW twin's."""
+    model, sd, cfg = tiny_model_sd(pkg)
+    twin, _, _ = tiny_model_sd(pkg)
+    model.to(DEV)
+    twin.to(DEV)
+    v_in = formula_input((2, 1, 2, 16, 16), 16).clamp(-1, 1).to(DEV)
+    v_gt = formula_input((2, 1, 4, 16, 16), 19).clamp(-1, 1).to(DEV)
+    t, nz = torch.tensor([612, 77], device=DEV), formula_noise(-1, (2, 8, 4, 4, 4)).to(DEV)
+    for p in list(model.vae.parameters()) + list(twin.vae.parameters()):
+        p.requires_grad_(False)
+    o1 = pkg.FusedAdamW(model.unet.parameters(), lr=2e-3, weight_decay=0.01, engine_modules=[model.unet])
+    o2 = torch.optim.AdamW(twin.unet.parameters(), lr=2e-3, weight_decay=0.01)
+    losses = []
+    for it in range(3):
+        if it == 1:
+            old = [p.data_ptr() for p in model.unet.parameters()]
+            keep = [p.data for p in model.unet.parameters()]     # the old storage stays allocated through the step
+            for p in model.unet.parameters():
+                p.data = p.data.clone()
+            assert all(p.data_ptr() != a for p, a in zip(model.unet.parameters(), old))
+        l1, _ = model(v_in, v_gt, t=t, noise=nz)
+        l2, _ = twin(v_in, v_gt, t=t, noise=nz)
+        losses.append((float(l1), float(l2)))
+        l1.backward()
+        l2.backward()
+        o1.step()
+        o2.step()
+        o1.zero_grad(set_to_none=True)
+        o2.zero_grad(set_to_none=True)
+        prog = [pr for k, pr in model.unet.__dict__["_ctsi_programs"].items() if k[0] == "unet-train"][0]
+        assert prog._fast is not None and prog._fingerprint() == prog._versions
+        if it == 0:
+            built = prog._fast
+            assert len(built["slow"]) == 0
+        if it == 1:
+            assert prog._fast is not built and prog._fast["ptrs"] == tuple(p.data_ptr() for p in prog._params)
+            assert len(prog._fast["slow"]) == 0, \
+                f"{len(prog._fast['slow'])} operands fell to the slow path after the parameters moved"
+            fast = [h["holder"][0].clone() for h in prog._pack_meta] + [e["buf"].clone() for e in prog._f32_meta]
+            with prog.ctx.scope():
+                prog.repack()
+            torch.cuda.synchronize()
+            slow = [h["holder"][0] for h in prog._pack_meta] + [e["buf"] for e in prog._f32_meta]
+            assert all(torch.equal(a, b) for a, b in zip(fast, slow))
+            del keep
+    print("losses (fused, parameters moved after step 1 / torch twin):", losses)
+    assert losses[0][0] == pytest.approx(losses[0][1], rel=1e-6)
+    for a, b in losses[1:]:
+        assert abs(a - b) <= 2e-2 * abs(b)
+    assert losses[2][0] < losses[0][0]
+    for p1, p2 in zip(model.unet.parameters(), twin.unet.parameters()):
+        assert rel_l2(p1.detach(), p2.detach()) < 5e-2
+
+
 def test_fused_optimizer_under_gradscaler_and_lr_scheduler(pkg):
     """The reference's loop steps its optimizer through a GradScaler under AMP (training/trainer.py:237-247) and drives the
     learning rate with a torch scheduler: both work on the drop-in unchanged, and match torch.optim.AdamW under the same."""

@@ -1332,6 +1332,23 @@ extern "C" int ctsi_conv_plan_config(const ctsi_conv_plan* p, int* bm, int* bn, 
     return CTSI_OK;
 }
 
+// The packed-image layout ctsi_conv_plan_pack_weights writes, beyond the descriptor's channel / kernel fields, the cout
+// padding and the weight's cin (see ctsi.h): the kernel family, and for the k32 kernel its form and whether the image is
+// cout-permuted for the direct-store epilogue.  Mirrors the branches of ctsi_conv_plan_pack_weights below.
+extern "C" int ctsi_conv_plan_pack_layout(const ctsi_conv_plan* p) {
+    if (!p) return 0;
+    if (p->stem) return CTSI_PACK_STEM;
+    if (p->stream1) return CTSI_PACK_STREAM_TAIL | (p->stream1 << 8);
+    if (p->halo3 == 7) {
+        const int form = p->ds ? 2 : p->d.transposed;
+        const int direct = ctsi_conv3_halo_k32_direct(p->m512_w16, p->ksplit, p->ds);
+        return CTSI_PACK_K32 | (form << 4) | (direct << 6) | ((p->BN / 16) << 8);
+    }
+    if (p->halo3 == 6) return CTSI_PACK_HEAD | (ctsi_conv3_head2_supported(p->Cin, p->d.cout) ? 1 << 4 : 0);
+    if (p->halo3) return CTSI_PACK_HALO;
+    return p->small ? CTSI_PACK_GATHER_SMALL : CTSI_PACK_GATHER;
+}
+
 // A 1x1x1 stride-1 conv that will run with the fused GroupNorm tail (ctsi_conv_out.gn_x) or as a plain bf16 conv + bias may
 // take the streaming kernel of conv1_stream.hip (another packed-weight layout: call this BEFORE ctsi_conv_plan_weight_bytes /
 // _pack_weights).  on = 1 selects it where the layer qualifies (whole 128-channel chunks per source, cout in whole n-tiles)

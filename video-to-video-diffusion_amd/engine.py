@@ -28,14 +28,26 @@ from .lib import ConvDesc, ConvOut, CtsiError, get_lib
 _CTX: Dict[int, "Ctx"] = {}
 
 # Packed-weight cache ("weight pre-packing cache keyed by checkpoint hash").  The bf16 kernel-layout
-# image of a layer's weights is content-addressed: key = (layout signature of the plan, 2 x 64-bit checksum of the fp32
-# weight tensor the layer's weight_fn returns).  Every program built from the same weights -- the sampler program, the
+# image of a layer's weights is content-addressed: key = (layout signature of the plan, _pack_sig; 2 x 64-bit checksum of
+# the fp32 weight tensor the layer's weight_fn returns).  Every program built from the same weights -- the sampler program, the
 # plain forward, other latent shapes, window batches, the depth-sharded variants: 265 M parameters = 0.53 GB of packed
 # bf16 per program otherwise -- shares ONE image and packs it once.  Entries are immutable and die with their last user
 # (weak values); a program whose weights changed looks up / packs new images and drops its captured graph.
 _PACKED: Dict[int, "weakref.WeakValueDictionary"] = {}
 # every live program (weak): check_device_errors re-zeroes their split-K hand-off workspaces after a reported device error
 _LIVE_PROGRAMS: "weakref.WeakSet" = weakref.WeakSet()
+
+
+def _pack_sig(lib, plan, transposed, k, s, c1: int, c2: int, cout: int, cin_w: Optional[int]) -> tuple:
+    """The layout half of a packed-image cache key: everything ctsi_conv_plan_pack_weights reads besides the weight values.
+    ctsi_conv_plan_pack_layout names the image layout the plan's kernel consumes (family; for the k32 kernel also its form
+    and the cout-permuted image of the direct-store epilogue, which the tile and split-K choice -- hence the batch size and
+    the depth-sharded view -- decide); the rest are the descriptor's channel / kernel fields and the plan's sizes."""
+    bm, bn, mode = C.c_int(), C.c_int(), C.c_int()
+    lib.conv_plan_config(plan, C.byref(bm), C.byref(bn), C.byref(mode))
+    return (lib.conv_plan_pack_layout(plan), int(transposed), tuple(k), tuple(s), c1, c2, cout, cin_w,
+            lib.conv_plan_cout_pad(plan), lib.conv_plan_weight_bytes(plan), bn.value, bm.value,
+            bool(lib.conv_plan_workspace_bytes(plan)))
 
 
 _KEY_CHUNK = 1 << 22
@@ -352,17 +364,15 @@ class Program:
         if not (torch.is_tensor(t) and t.is_cuda and t.device == self.ctx.device and t.dtype == torch.float32
                 and t.is_contiguous() and t.numel() > 0):
             return False
-        homes = getattr(self, "_param_storages", None)
-        if homes is None or self._param_storages_n != len(self._params):
-            homes = self._param_storages = {p.untyped_storage().data_ptr() for p in self._params if torch.is_tensor(p)}
-            self._param_storages_n = len(self._params)
-        return t.untyped_storage().data_ptr() in homes
+        return t.untyped_storage().data_ptr() in self._param_storages
 
     def _build_fast(self):
         import struct
         if self._fast and self._fast.get("graph") is not None:      # (a parameter moved: the recorded pointers are stale)
             self.lib.graph_destroy(self._fast["graph"])
             self._fast["graph"] = None
+        # where the parameters live NOW (this runs again exactly when one of them moved: the old addresses may be reused)
+        self._param_storages = {p.untyped_storage().data_ptr() for p in self._params if torch.is_tensor(p)}
         segs, slow, packs = [], [], []
         for ent in self._f32_meta:
             parts = ent["parts"] if ent["parts"] is not None else [ent["make"]]
@@ -549,10 +559,7 @@ class Program:
         sptr = self.ctx.sptr
         bm, bn, mode = C.c_int(), C.c_int(), C.c_int()
         lib.conv_plan_config(plan, C.byref(bm), C.byref(bn), C.byref(mode))
-        layout = "gather" if mode.value in (0, 2) else mode.value      # the packed image depends on the kernel family,
-        sig = (layout, int(transposed), tuple(k), tuple(s), x1.c, 0 if x2 is None else x2.c, cout, cin_w,   # not the shape
-               lib.conv_plan_cout_pad(plan), wbytes, bn.value, bm.value, bool(lib.conv_plan_workspace_bytes(plan)))   # (k32: the
-                                                                                   # epilogue form, hence the cout order, goes by tile / split-K)
+        sig = _pack_sig(lib, plan, transposed, k, s, x1.c, 0 if x2 is None else x2.c, cout, cin_w)
         holder: List[Optional[torch.Tensor]] = [None]
         prog = self
 
@@ -698,9 +705,7 @@ class Program:
             wbytes = lib.conv_plan_weight_bytes(plan)
             bm, bn, mode = C.c_int(), C.c_int(), C.c_int()
             lib.conv_plan_config(plan, C.byref(bm), C.byref(bn), C.byref(mode))
-            layout = "gather" if mode.value in (0, 2) else mode.value
-            sig = (layout, 0, tuple(k), (1, 1), x1.c, 0 if x2 is None else x2.c, cout, cin_w, lib.conv_plan_cout_pad(plan),
-                   wbytes, bn.value, bm.value, bool(lib.conv_plan_workspace_bytes(plan)))
+            sig = _pack_sig(lib, plan, 0, k, (1, 1), x1.c, 0 if x2 is None else x2.c, cout, cin_w)
             holder: List[Optional[torch.Tensor]] = [None]
 
             def pack(plan=plan, sig=sig, wbytes=wbytes, holder=holder):

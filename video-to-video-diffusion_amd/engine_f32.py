@@ -32,6 +32,14 @@ from .lib import ConvDesc, ConvOut, CtsiError
 PRECISIONS = ("bf16", "fp32")
 
 
+def _f32_pack_sig(desc: ConvDesc, cout_pad: int, wbytes: int) -> tuple:
+    """The layout half of an fp32 packed-image cache key: ctsi_conv_f32_pack_weights reads the descriptor's channel / kernel
+    fields only (never the batch or the spatial size; each supported kernel geometry has one padding).  The precision leads
+    the key, so a bf16 program never finds it."""
+    return ("fp32", int(desc.transposed), (desc.kd, desc.kh, desc.kw), (desc.sh, desc.sw), desc.c1, desc.c2, desc.cout,
+            cout_pad, wbytes)
+
+
 def check_precision(p) -> str:
     """Validate an inference precision value ('bf16' | 'fp32'); raises ValueError otherwise."""
     if not isinstance(p, str) or p not in PRECISIONS:
@@ -80,8 +88,7 @@ class _F32Ops:
         bias = (self.dev_f32(bias_fn, parts=getattr(bias_fn, "parts", None), scale=getattr(bias_fn, "scale", 1.0))
                 if bias_fn is not None else None)
         sptr = self.ctx.sptr
-        # the fp32 image is its own cache family: the precision leads the key, so a bf16 program never finds it
-        sig = ("fp32", int(transposed), tuple(k), tuple(s), x1.c, c2, cout, cpad, wbytes)
+        sig = _f32_pack_sig(desc, cpad, wbytes)
         holder: List[Optional[torch.Tensor]] = [None]
 
         def pack():
