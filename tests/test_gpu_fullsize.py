@@ -309,12 +309,8 @@ def test_training_microstep_config3(full_model):
     loss, _ = model(v_in, v_gt, t=t, noise=noise)
     loss.backward()
     torch.cuda.synchronize()
-    names = ["unet.conv_in.weight", "unet.conv_out.2.weight", "unet.mid_block1.conv1.conv.weight",
-             "unet.down_blocks.0.0.0.conv2.0.weight", "unet.up_blocks.3.0.0.conv1.conv.weight",
-             "unet.up_blocks.3.0.0.residual_conv.weight", "unet.down_samples.0.conv.weight",
-             "unet.up_samples.2.conv.weight", "unet.down_blocks.1.0.0.conv1.norm.weight",
-             "unet.time_embed.time_mlp.1.weight", "unet.mid_attn.proj_out.weight", "unet.up_blocks.0.2.0.time_mlp.1.bias"]
     pm = dict(model.named_parameters())
+    names = [k for k in pm if k.startswith("unet.")]         # every U-Net parameter
     hip = {k: pm[k].grad.detach().float().clone() for k in names}
     hip_loss = float(loss)
     for p in model.parameters():
@@ -344,8 +340,11 @@ def test_training_microstep_config3(full_model):
     ac_loss, ac_g = oracle(True)
     print(f"config-3 micro-step loss: hip {hip_loss:.6f}, fp32 oracle {ref_loss:.6f}, oracle under bf16 autocast {ac_loss:.6f}")
     assert abs(hip_loss - ref_loss) <= 2e-2 * abs(ref_loss)
+    bad = []
     for k in names:
         e_h, e_a = rel_l2(hip[k], ref_g[k]), rel_l2(ac_g[k], ref_g[k])
         print(f"  grad {k}: hip {e_h:.3g}, autocast {e_a:.3g}")
-        assert e_h <= 2 * e_a + 2e-2, k
+        if not e_h <= 2 * e_a + 2e-2:
+            bad.append((k, e_h, e_a))
+    assert not bad, bad
     _free()

@@ -188,6 +188,7 @@ class Program:
         self.op_meta: List[Tuple[str, float, str]] = []
         self.op_bytes: List[float] = []
         self.op_alg_bytes: List[float] = []   # convs: algorithmic HBM bytes (inputs + outputs + weights, each once)
+        self.op_audit: List[Optional[dict]] = []   # per op: what it computes from which buffers (training backward), or None
         self.pool = _Pool(ctx.device)
         self.keep: List[object] = []       # tensors / ctypes structs that must outlive the ops
         self.plans: List[C.c_void_p] = []  # conv plan handles (destroyed with the program)
@@ -215,12 +216,16 @@ class Program:
         _LIVE_PROGRAMS.add(self)
 
     def _emit(self, fn: Callable[[], None], name: str = "op", flops: float = 0.0, kernel: str = "", nbytes: float = 0.0,
-              alg_bytes: float = 0.0):
-        """`nbytes`: algorithmic HBM bytes of an HBM-bound op (what bench.py divides by the launch time for GB/s)."""
+              alg_bytes: float = 0.0, audit: Optional[dict] = None):
+        """`nbytes`: algorithmic HBM bytes of an HBM-bound op (what bench.py divides by the launch time for GB/s).
+        `audit`: a description of what the op computes -- its kind, the Acts / tensors it reads and writes and the scalars of
+        the formula (references only; it changes nothing about the launch).  The training programs attach one to every
+        backward op so that a test can re-derive each launch's result from its own operands (tests/train_audit.py)."""
         self.ops.append(fn)
         self.op_meta.append((name, flops, kernel))
         self.op_bytes.append(float(nbytes))
         self.op_alg_bytes.append(float(alg_bytes))
+        self.op_audit.append(audit)
 
     # ---- buffers -------------------------------------------------------------------------------------
     def act(self, n, c, d, h, w, halo: Optional[int] = None) -> Act:
@@ -498,7 +503,7 @@ class Program:
              k=(3, 3, 3), s=(1, 1), p=(1, 1, 1), cout: int, cin_w: Optional[int] = None,
              out: Optional[Act] = None, want_stats=False, f32_out: Optional[torch.Tensor] = None,
              f32_strides: Optional[Sequence[int]] = None, act: int = 0, fuse_gn=None, ext_out: bool = False,
-             norm_in=None):
+             norm_in=None, audit: Optional[dict] = None):
         """Emit one convolution.  weight_fn/bias_fn return the *current* fp32 parameter tensors
         (possibly derived, e.g. scaled or pre-multiplied).  Returns (out_act, stats_handle).
         `fuse_gn` = (h: Act, slot, gn: nn.GroupNorm, silu: bool): the epilogue stores silu?(gn(h) + conv result)
@@ -647,7 +652,9 @@ class Program:
         alg = (2.0 * x1.n * di * x1.h * x1.w * cin_all + float(wbytes)
                + (4.0 if f32_out is not None else 2.0) * x1.n * do * ho * wo * cout
                + (2.0 * x1.n * do * ho * wo * cout if fuse_gn is not None else 0.0))
-        self._emit(run, name, fl, kernel, alg_bytes=alg)
+        if audit is not None:
+            audit = dict(audit, out=out_act)
+        self._emit(run, name, fl, kernel, alg_bytes=alg, audit=audit)
         return out_act, stats
 
     def _conv_overlapped(self, name, weight_fn, bias_fn, x1: Act, x2: Optional[Act], k, p, cout, cin_w, want_stats):

@@ -79,7 +79,7 @@ class TrainProgram(Program):
         def run():
             lib.add_bf16(gp, tp, cnt, sptr)
 
-        self._emit(run, "grad.add")
+        self._emit(run, "grad.add", audit=dict(kind="add", dst=a.grad, src=tmp))
         self.release(tmp)
 
     # ---- conv ----------------------------------------------------------------------------------------------------
@@ -138,7 +138,7 @@ class TrainProgram(Program):
             def run_b():
                 lib.channel_sum(gp, rows, gc, gc, prog._ws_ptr("chsum"), gbp, b_scale, sptr)
 
-            self._emit(run_b, name + ".bgrad")
+            self._emit(run_b, name + ".bgrad", audit=dict(kind="chsum", src=g, out=gb[gb_off:gb_off + gc], scale=float(b_scale)))
         # weight
         srcs = [(x1, 0)] + ([(x2, x1.c)] if x2 is not None else [])
         for xa, coff in ([] if (defer_wb or not emit_wgrad) else srcs):
@@ -161,16 +161,24 @@ class TrainProgram(Program):
             def run_w(desc=desc, rp=rp, gp2=gp2, dwp=dwp, sr=sr, sg=sg):
                 lib.wgrad(C.byref(desc), rp, gp2, prog._ws_ptr("wgrad"), prog._ws["wgrad"].numel(), dwp, sr, sg, 1, w_scale, sptr)
 
-            self._emit(run_w, name + ".wgrad", fl, "conv_wgrad")
+            # audit: dW[r, g, t] of the conv R = conv3d(G, W) lands at dwp + r * sr + g * sg + t
+            dst = gw.as_strided((r_act.c, g_act.c, T), (sr, sg, 1), gw.storage_offset() + off)
+            self._emit(run_w, name + ".wgrad", fl, "conv_wgrad",
+                       audit=dict(kind="wgrad", r=r_act, r_ch=r_act.c, g=g_act, g_ch=g_act.c, k=k, s=s, p=p, out=dst,
+                                  scale=float(w_scale)))
         # data
         if not need_dx:
             return
         if transposed:      # ConvTranspose3d layer: dx = strided Conv3d of g with the same weight tensor
             self.into_grad(x1, lambda dst: self.conv(name + ".dgrad", lambda: wparam, None, g, None, k=k, s=s, p=p,
-                                                     cout=x1.c, out=dst))
+                                                     cout=x1.c, out=dst,
+                                                     audit=dict(kind="dgrad", op="conv", g=g, weight=lambda: wparam,
+                                                                w_ci=None, k=k, s=s, p=p)))
         elif s != (1, 1):   # strided Conv3d layer: dx = ConvTranspose3d of g with the same weight tensor
             self.into_grad(x1, lambda dst: self.conv(name + ".dgrad", lambda: wparam, None, g, None, transposed=True,
-                                                     k=k, s=s, p=p, cout=x1.c, out=dst))
+                                                     k=k, s=s, p=p, cout=x1.c, out=dst,
+                                                     audit=dict(kind="dgrad", op="convT", g=g, weight=lambda: wparam,
+                                                                w_ci=None, k=k, s=s, p=p)))
         else:               # stride-1 'same' conv: flipped, transposed weights, one launch per concatenated source
             co_w, ci_w = wparam.shape[0], wparam.shape[1]
             if w_src is not None:
@@ -187,9 +195,12 @@ class TrainProgram(Program):
                 # (fast_repack: the same re-layout from a pointer table, into a buffer the program keeps)
                 wfn.fast_layout = ((w_src if w_src is not None else (lambda: wparam)), co_w, ci_w, T, coff, xa.c)
 
-                self.into_grad(xa, lambda dst, wfn=wfn, cnt=xa.c: self.conv(
+                # audit: dx = conv_transpose3d(g, W[:co_w, coff:coff + cnt]) with the layer's own weight
+                aud = dict(kind="dgrad", op="convT", g=g, weight=(w_src if w_src is not None else (lambda: wparam)),
+                           w_ci=(coff, xa.c), k=k, s=(1, 1), p=p)
+                self.into_grad(xa, lambda dst, wfn=wfn, cnt=xa.c, aud=aud: self.conv(
                     name + ".dgrad", wfn, None, g, None, k=k, s=(1, 1), p=p, cout=cnt, out=dst,
-                    cin_w=(co_w if co_w != g.c else None)))
+                    cin_w=(co_w if co_w != g.c else None), audit=aud))
 
     # ---- GroupNorm chain ---------------------------------------------------------------------------------------------
     def t_gn(self, x: Act, slot: int, gn: nn.GroupNorm, *, silu_pre: bool, tb_off: Optional[int] = None,
@@ -252,14 +263,19 @@ class TrainProgram(Program):
                        groups, eps, int(silu_pre), rp, int(silu_post), ap, gbp, dxp, prog._ws_ptr("gn"), dgp, dbp, dtp,
                        tstride, dxsp, sptr)
 
-        self._emit(run, "gn.bwd")
+        nsum = n * groups * 2
+        self._emit(run, "gn.bwd", audit=dict(
+            kind="gn_bwd", x=x, dy=gy, bcast=bool(bcast), sums=lambda: prog._gn_sums[slot:slot + nsum], gamma=gamma, beta=beta,
+            groups=groups, eps=eps, silu_pre=bool(silu_pre), residual=residual, silu_post=bool(silu_post), add=add, g_out=gbuf,
+            dx=x.grad, dgamma=dgam, dbeta=dbet, dxsum=dxsum,
+            dtbias=None if tb_off is None else self.d_tbias[:, tb_off:tb_off + c]))
         if add_to_res:
             rgp, cnt = residual.grad.ip, n * x.vox * c
 
             def run_add():
                 lib.add_bf16(rgp, gbp, cnt, sptr)
 
-            self._emit(run_add, "grad.add")
+            self._emit(run_add, "grad.add", audit=dict(kind="add", dst=residual.grad, src=gbuf))
         if tmp is not None:
             self.release(tmp)
 
@@ -392,7 +408,9 @@ class UNetTrainProgram(TrainProgram):
             lib.mse_loss_bwd(_ptr(prog.eps), _ptr(prog.noise), _ptr(prog.mask) if prog.use_mask else None,
                              _ptr(prog.norm), _ptr(prog.gscale), n, L, d, h, w, prog.d_eps.ip, prog.Lp, sptr)
 
-        self._emit(run_loss_bwd, "loss.bwd")
+        self._emit(run_loss_bwd, "loss.bwd", audit=dict(
+            kind="loss_bwd", pred=self.eps, noise=self.noise, mask=lambda: prog.mask if prog.use_mask else None, norm=self.norm,
+            gscale=self.gscale, out=self.d_eps))
         for fn in reversed(self.tape):
             fn()
         self._emit_deferred_lin()
@@ -426,7 +444,11 @@ class UNetTrainProgram(TrainProgram):
             lib.linear_wgrad_multi(_ptr(et), _ptr(bt), nb, sptr)
 
         self.flops += fl
-        self._emit(run, "attn.wgrad+bgrad.batched", fl, "linear_wgrad_multi")
+        layers = [dict(x=xa, g=ga, dw=gw.as_strided((cout, cin), (dw_stride, 1), gw.storage_offset() + gw_off),
+                       db=None if gb is None else gb[gb_off:gb_off + cout], scale=b_scale)
+                  for (xa, ga, gw, gw_off, gb, gb_off, b_scale, rows, cin, cout, dw_stride) in self._deferred_lin]
+        self._emit(run, "attn.wgrad+bgrad.batched", fl, "linear_wgrad_multi",
+                   audit=dict(kind="linear_wgrad_multi", layers=layers))
         for (xa, ga, *_rest) in self._deferred_lin:
             self.release(ga)
 
@@ -510,7 +532,7 @@ class UNetTrainProgram(TrainProgram):
                 lib.attn_depthsum(gyp, dsp2, _ptr(prog._colsum), n, c, d, h, w, sptr)
                 lib.f32_to_bf16(dsp2, dPp, n * h * w * c, sptr)
 
-            self._emit(run_dsum, "attn.bwd.depthsum")
+            self._emit(run_dsum, "attn.bwd.depthsum", audit=dict(kind="depthsum", src=gy, out=dP))
             # proj_out: dW_p, db_p, du
             defer = not os.environ.get("CTSI_TRAIN_NO_LIN_BATCH")     # (A/B timing, tests: one wgrad + bgrad launch pair per layer)
             self._conv_bwd("attn.proj", m.proj_out.weight, m.proj_out.bias, u, None, dP, False, (1, 1, 1), (1, 1),
@@ -550,7 +572,11 @@ class UNetTrainProgram(TrainProgram):
             lib.linear_bwd(_ptr(sincos), _ptr(prog.w1), _ptr(prog.g_lin1), n, dim, td, 0, _ptr(gw1), _ptr(gb1), None,
                            sptr)
 
-        self._emit(run, "time_embed.bwd")
+        self._emit(run, "time_embed.bwd", audit=dict(kind="linear_bwd_chain", steps=[
+            dict(x=temb, w=self.w_all, dy=self.d_tbias, rows=n, cin=td, cout=tot, silu_in=True, dw=self.g_w_all, db=self.g_b_all,
+                 dx=self.g_temb),
+            dict(x=lin1, w=self.w2, dy=self.g_temb, rows=n, cin=td, cout=td, silu_in=True, dw=gw2, db=gb2, dx=self.g_lin1),
+            dict(x=sincos, w=self.w1, dy=self.g_lin1, rows=n, cin=dim, cout=td, silu_in=False, dw=gw1, db=gb1, dx=None)]))
         # the per-block Linear gradients are row slices of the stacked buffers
         for m in self.blocks:
             off = self.tb_off[id(m)]

@@ -118,7 +118,8 @@ class VAETrainProgram(TrainProgram):
                 if prog.use_gz:
                     lib.vae_head_grad(_ptr(prog.g_z), None, n, L, d, hl, wl, sf, 1, zg.ip, zg.c, sptr)
 
-            prog._emit(run_gz, "seam.grad_z")
+            prog._emit(run_gz, "seam.grad_z", audit=dict(kind="head_grad", mode=1, g=prog.g_z, y=None, scale=sf, out=zg,
+                                                        active=lambda: prog.use_gz))
 
         self.tape.append(seam_bwd)
 
@@ -155,7 +156,8 @@ class VAETrainProgram(TrainProgram):
         def run_head():
             lib.vae_head_grad(_ptr(prog.g_recon), _ptr(prog.recon), n, co, d, ho, wo, 1.0, 0, hp.ip, hp.c, sptr)
 
-        self._emit(run_head, "head.grad")
+        self._emit(run_head, "head.grad", audit=dict(kind="head_grad", mode=0, g=self.g_recon, y=self.recon, scale=1.0, out=hp,
+                                                     active=None))
         for fn in reversed(self.tape):
             fn()
         self.finalize_layout()
@@ -214,7 +216,13 @@ class VAETrainProgram(TrainProgram):
                            dwp, 1.0, sptr)
 
         self.flops += fl
-        self._emit(run, name + ".wgrad.thin", fl, "thin_wgrad")
+        # audit: the weight gradient of R = conv3d(G, W) with R = output gradient, G = layer input (one channel of the thin one)
+        if head:
+            aud = dict(r=g, r_ch=1, g=x1, g_ch=c, out=gw[0:1].reshape(1, c, 27))
+        else:
+            aud = dict(r=g, r_ch=c, g=x1, g_ch=1, out=gw.reshape(c, 1, 27))
+        self._emit(run, name + ".wgrad.thin", fl, "thin_wgrad",
+                   audit=dict(aud, kind="wgrad", k=(3, 3, 3), s=(1, 1), p=(1, 1, 1), scale=1.0))
 
     def conv_gn_act(self, name, m, x: Act, *, cin_w=None, k=(3, 3, 3), s=(1, 1), transposed=False, stem=False) -> Act:
         c, st = self.v_conv(name, m.conv, x, cin_w=cin_w, k=k, s=s, transposed=transposed, want_stats=True,
