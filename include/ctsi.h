@@ -409,6 +409,31 @@ int ctsi_adamw_chunk_elems(void);
 int ctsi_adamw_multi(const void* tensors, const void* groups, const void* chunks, int nchunks, void* stream);
 int ctsi_copy_scale_multi(const void* segs, const void* pieces, int npieces, void* stream);
 
+/* ---- the rest of the device-side optimizer step: EMA of the weights and global-norm clipping ----
+ * All of these take a tensor table of their own plus a chunk table laid out as ctsi_adamw_multi's ({ int tensor; int
+ * first_element / 4 }, ctsi_adamw_chunk_elems() elements per block); null tables / negative counts return CTSI_ERR_INVALID
+ * before any launch, nchunks == 0 returns CTSI_OK.  16-byte accesses where every pointer of a row is 16-byte aligned.
+ * ctsi_ema_multi: ema = ema + w (p - ema) over tensors[i] = { float* ema; const float* p; long long numel; int group; int pad },
+ *   w = weights[group] = (float)(1 - decay), a device row (torch's lerp_ for w < 0.5).
+ * ctsi_swap_multi: exchanges the values of a and b over pairs[i] = { float* a; float* b; long long numel; long long pad }.
+ * ctsi_grad_norm_multi: partials[b] = sum over chunk b of (scale * g)^2 in fp64, tensors[i] = { float* grad; long long numel;
+ *   float scale; int pad }.  ctsi_grad_norm_finalize: ONE block adds the partials in a fixed order and writes out = { float
+ *   total_norm; float clip_coef = min(1, max_norm / (total_norm + 1e-6)) } (torch.nn.utils.clip_grad_norm_'s fp32 arithmetic;
+ *   a NaN norm gives a NaN coefficient).  No atomics: the same bits on every run.
+ * ctsi_grad_scale_multi: grad *= *dev_scale in place over the table of the norm pass (nothing is written when it is 1).
+ * ctsi_adamw_ema_multi: ctsi_adamw_multi's update over the wider row tensors[i] = { float* param; const float* grad; float*
+ *   exp_avg; float* exp_avg_sq; float* ema (NULL: none); long long numel; int group; int ema_group; long long pad } (64 bytes);
+ *   dev_grad_scale (nullable) is ONE device float multiplied into every group's grad_scale (the clip_coef above: out + 1),
+ *   ema_weights (nullable: no shadow is touched) holds (float)(1 - decay) per ema group; the shadow is updated from the NEW
+ *   parameter.  With both NULL, param / exp_avg / exp_avg_sq come out as ctsi_adamw_multi's, bit for bit. */
+int ctsi_ema_multi(const void* tensors, const void* weights, const void* chunks, int nchunks, void* stream);
+int ctsi_swap_multi(const void* pairs, const void* chunks, int nchunks, void* stream);
+int ctsi_grad_norm_multi(const void* tensors, const void* chunks, int nchunks, double* partials, void* stream);
+int ctsi_grad_norm_finalize(const double* partials, int nchunks, float max_norm, float* out, void* stream);
+int ctsi_grad_scale_multi(const void* tensors, const void* chunks, int nchunks, const float* dev_scale, void* stream);
+int ctsi_adamw_ema_multi(const void* tensors, const void* groups, const void* chunks, int nchunks,
+                         const float* dev_grad_scale, const float* ema_weights, void* stream);
+
 /* Device-side errors recorded since the last call with reset != 0 (0 on a healthy run): today the only source is a split-K
  * conv block whose bounded wait for its partner's partial sums expired (csrc/conv3_halo_k32.hip): that tile's output is
  * then invalid, and this sticky count is what tells the host so.  *detail (may be NULL) = that tile's index.

@@ -12,7 +12,8 @@ from .diffusion import GaussianDiffusion  # noqa: F401
 from .model import VideoToVideoDiffusion  # noqa: F401
 from .sampler import DDIMSampler, DDPMSampler, DPMSolverSampler, EDMSampler, HeunSampler  # noqa: F401
 from .generate import generate_batch, interpolate_videos  # noqa: F401
-from .optim import FusedAdam, FusedAdamW  # noqa: F401
+from .ema import EMAWeights  # noqa: F401
+from .optim import FusedAdam, FusedAdamW, clip_grad_norm_  # noqa: F401
 from . import parallel  # noqa: F401,E402
 
 

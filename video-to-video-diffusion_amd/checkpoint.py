@@ -61,10 +61,22 @@ def load_checkpoint(checkpoint_path: str, device: str = 'cpu', weights_only: boo
     return ckpt
 
 
-def load_model_from_checkpoint(model, checkpoint_path: str, device: str = 'cuda', strict: bool = True) -> Tuple[object, Dict]:
+def load_model_from_checkpoint(model, checkpoint_path: str, device: str = 'cuda', strict: bool = True,
+                               use_ema: bool = False) -> Tuple[object, Dict]:
     """Load weights (new dict format or a bare state dict), move the model to `device`, switch to eval mode.
-    The engine re-packs its bf16 kernel-layout weights by itself on the next call (parameter versions change)."""
+    The engine re-packs its bf16 kernel-layout weights by itself on the next call (parameter versions change).
+    `use_ema` (additive): overlay the averaged weights a trainer stored with
+    `save_checkpoint(..., ema_state_dict=ema.state_dict())` (ema.EMAWeights) on the raw ones before loading; raises when the
+    checkpoint holds none or a shadow name is not a key of its `model_state_dict`."""
     ckpt = load_checkpoint(checkpoint_path, device='cpu')
+    if use_ema:
+        if not (isinstance(ckpt, dict) and 'model_state_dict' in ckpt and 'ema_state_dict' in ckpt):
+            raise KeyError(f"use_ema=True, but {checkpoint_path} has no 'ema_state_dict' beside its 'model_state_dict'")
+        shadow = ckpt['ema_state_dict']['shadow']
+        unknown = sorted(set(shadow) - set(ckpt['model_state_dict']))
+        if unknown:
+            raise KeyError(f"use_ema=True: shadow names that are no keys of the model_state_dict: {unknown[:8]}")
+        ckpt['model_state_dict'] = {**ckpt['model_state_dict'], **shadow}
     if isinstance(ckpt, dict) and 'model_state_dict' in ckpt:
         state = ckpt['model_state_dict']
         meta = {'epoch': ckpt.get('epoch', 0), 'best_loss': ckpt.get('best_loss', float('inf')),

@@ -152,6 +152,12 @@ SIGNATURES = {
     "ctsi_adamw_chunk_elems": (_i, [], False),
     "ctsi_adamw_multi": (_i, [_vp, _vp, _vp, _i, _vp], True),
     "ctsi_copy_scale_multi": (_i, [_vp, _vp, _i, _vp], True),
+    "ctsi_ema_multi": (_i, [_vp, _vp, _vp, _i, _vp], True),
+    "ctsi_swap_multi": (_i, [_vp, _vp, _i, _vp], True),
+    "ctsi_grad_norm_multi": (_i, [_vp, _vp, _i, _vp, _vp], True),
+    "ctsi_grad_norm_finalize": (_i, [_vp, _i, _f, _vp, _vp], True),
+    "ctsi_grad_scale_multi": (_i, [_vp, _vp, _i, _vp, _vp], True),
+    "ctsi_adamw_ema_multi": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp], True),
     "ctsi_device_error_status": (_i, [C.POINTER(C.c_uint), C.POINTER(C.c_uint), _i], True),
     "ctsi_conv_f32_supported": (_i, [C.POINTER(ConvDesc)], False),
     "ctsi_conv_f32_weight_bytes": (_sz, [C.POINTER(ConvDesc)], False),

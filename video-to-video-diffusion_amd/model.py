@@ -166,7 +166,8 @@ class VideoToVideoDiffusion(nn.Module):
 
     def save_checkpoint(self, path, optimizer=None, scheduler=None, scaler=None, epoch=None, global_step=None,
                         current_phase=None, best_loss=None, **kwargs):
-        """Same dict layout as the reference (model.py:362-387)."""
+        """Same dict layout as the reference (model.py:362-387).  Extra keyword arguments go into the dict as they are:
+        `ema_state_dict=ema.state_dict()` (ema.EMAWeights) is what `load_model_from_checkpoint(..., use_ema=True)` reads."""
         ckpt = {'model_state_dict': self.state_dict(), 'config': self.config}
         for key, obj in (('optimizer_state_dict', optimizer), ('scheduler_state_dict', scheduler),
                          ('scaler_state_dict', scaler)):
