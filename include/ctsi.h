@@ -434,6 +434,25 @@ int ctsi_grad_scale_multi(const void* tensors, const void* chunks, int nchunks, 
 int ctsi_adamw_ema_multi(const void* tensors, const void* groups, const void* chunks, int nchunks,
                          const float* dev_grad_scale, const float* ema_weights, void* stream);
 
+/* ---- differentiable MS-SSIM loss on the device (models/losses.py:149-276; csrc/msssim.hip) ----
+ * pred, target: fp32, `planes` = B*C*D contiguous h x w images in [-1, 1] (the NCDHW tensor as it lies); five levels, the
+ * zero-padded Gaussian window (sigma 1.5, `window` odd, 1..15), 2 x 2 average pools between levels (floor),
+ * loss = 1 - prod_i mean_i ^ w_i.  min(h, w) >= 16, planes <= 65535.  fp32 arithmetic, fp64 sums in a fixed order, no
+ * atomics: loss and gradient are the same bits on every run.  No allocation, no synchronisation, capture-safe; bad arguments
+ * return CTSI_ERR_INVALID before any launch (ctsi_msssim_workspace_bytes returns 0 and sets ctsi_last_error).
+ * ctsi_msssim_workspace_bytes: with n_i = planes (h >> i)(w >> i) and t_i = planes ceil((h >> i) / 32) ceil((w >> i) / 32):
+ *     8 sum_{i=0..4} t_i  (fp64 partials)  +  64  (factor table)  +  8 sum_{i=1..4} n_i  (pooled images)
+ *     + (want_grad ? 12 sum_{i=0..4} n_i  (coefficient maps)  +  4 sum_{i=1..4} n_i  (level gradients) : 0).
+ * ctsi_msssim_fwd: 5 level launches + 1 finalize; out[0] = loss, out[1..5] = the five level means (device floats).  With
+ *   want_grad = 0 the coefficient maps are neither part of the workspace nor written.
+ * ctsi_msssim_bwd: 5 level launches, coarse to fine, on the workspace of a want_grad = 1 forward of the same operands;
+ *   grad_pred = *grad_loss * d loss / d pred (grad_loss is a DEVICE float), fp32 in pred's layout.  target gets no gradient. */
+size_t ctsi_msssim_workspace_bytes(int planes, int h, int w, int window, int want_grad);
+int ctsi_msssim_fwd(const float* pred, const float* target, int planes, int h, int w, int window, int want_grad,
+                    void* workspace, float* out, void* stream);
+int ctsi_msssim_bwd(const float* pred, const float* target, int planes, int h, int w, int window, void* workspace,
+                    const float* grad_loss, float* grad_pred, void* stream);
+
 /* Device-side errors recorded since the last call with reset != 0 (0 on a healthy run): today the only source is a split-K
  * conv block whose bounded wait for its partner's partial sums expired (csrc/conv3_halo_k32.hip): that tile's output is
  * then invalid, and this sticky count is what tells the host so.  *detail (may be NULL) = that tile's index.

@@ -158,6 +158,9 @@ SIGNATURES = {
     "ctsi_grad_norm_finalize": (_i, [_vp, _i, _f, _vp, _vp], True),
     "ctsi_grad_scale_multi": (_i, [_vp, _vp, _i, _vp, _vp], True),
     "ctsi_adamw_ema_multi": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp], True),
+    "ctsi_msssim_workspace_bytes": (_sz, [_i, _i, _i, _i, _i], False),
+    "ctsi_msssim_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp], True),
+    "ctsi_msssim_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp], True),
     "ctsi_device_error_status": (_i, [C.POINTER(C.c_uint), C.POINTER(C.c_uint), _i], True),
     "ctsi_conv_f32_supported": (_i, [C.POINTER(ConvDesc)], False),
     "ctsi_conv_f32_weight_bytes": (_sz, [C.POINTER(ConvDesc)], False),
