@@ -535,6 +535,28 @@ int ctsi_heun_step_f32(float* z, const float* eps, float* d1, const float* noise
                        const float* coef, const int* step_ptr, int n, int c, int d, int h, int w, int* nonfinite,
                        void* stream);
 
+/* Classifier-free guidance between the U-Net and the sampler update (csrc/guidance.hip).  `eps` is
+ * the fp32 NDHWC noise prediction of a batch of 2n: rows [0, n) conditional (eps_c), rows [n, 2n) evaluated on the null
+ * conditioning (eps_u).  Row scale[*step_ptr] = {s, phi} (row 0 when step_ptr is NULL): a device table, so a captured
+ * graph serves every guidance scale.
+ * ctsi_cfg_combine: rows [0, n) <- m_b (eps_u + s (eps_c - eps_u)) in place, m_b = phi stats[4 b + 2] + (1 - phi); m_b = 1
+ *   when stats is NULL or phi == 0 (no statistics are read).  fp32 arithmetic, one fma per element.
+ * ctsi_cfg_stats: partials[(b * ctsi_cfg_stats_blocks(c d h w) + x) * 4 ..] = fp64 sums of eps_c, eps_c^2, eps_g, eps_g^2
+ *   (eps_g = eps_u + s (eps_c - eps_u) in fp64) over block x's share of sample b.
+ * ctsi_cfg_stats_finalize: one block per sample adds its partials in a fixed order and writes stats[4 b ..] = { std_b(eps_c),
+ *   std_b(eps_g), their ratio (1 when std_b(eps_g) == 0), element count }, unbiased as torch.std.  No atomics: the same
+ *   bits on every run.
+ * ctsi_cfg_mirror: `rows` rows of row_bytes at a pitch of stride_bytes copied from src to dst (the z half of the network
+ *   input, rows [0, n) -> rows [n, 2n), after the update); sizes even, 16-byte accesses when sizes and pointers allow.
+ * Null pointers / non-positive sizes return CTSI_ERR_INVALID before any launch.  Capture-safe. */
+int ctsi_cfg_stats_blocks(long long per_sample);
+int ctsi_cfg_combine(float* eps, const float* scale, const int* step_ptr, const double* stats, int n, int c, int d, int h,
+                     int w, void* stream);
+int ctsi_cfg_stats(const float* eps, const float* scale, const int* step_ptr, double* partials, int n, int c, int d, int h,
+                   int w, void* stream);
+int ctsi_cfg_stats_finalize(const double* partials, double* stats, int n, int c, int d, int h, int w, void* stream);
+int ctsi_cfg_mirror(const void* src, void* dst, long long rows, int row_bytes, int stride_bytes, void* stream);
+
 /* hipGraph helpers (one captured graph per denoising step) -------------------------------- */
 typedef struct ctsi_graph ctsi_graph;
 int ctsi_graph_begin_capture(void* stream);

@@ -84,16 +84,18 @@ class GaussianDiffusion(nn.Module):
         return rows
 
     @torch.no_grad()
-    def p_sample_loop(self, model, shape, c, device, progress=True, noise_fn=None, num_steps=None):
+    def p_sample_loop(self, model, shape, c, device, progress=True, noise_fn=None, num_steps=None, guidance_scale=1.0,
+                      guidance_rescale=0.0):
         """z_T ~ N(0, I); for t = T-1..0: one U-Net evaluation + ctsi_ddpm_step (clip to [-1, 1]).
 
         `noise_fn(i, shape)` (optional, additive kwarg) supplies the initial noise (i = -1) and the
         per-step noise tensors instead of torch.randn; `num_steps` truncates the loop to its first
-        steps (both are test hooks; defaults reproduce the reference)."""
+        steps (both are test hooks; defaults reproduce the reference).  `guidance_scale` / `guidance_rescale`
+        (additive): classifier-free guidance, see sampler.run_sampler."""
         from .sampler import run_sampler  # local import: sampler imports this module
         return run_sampler(self, model, shape, c, device, kind="ddpm",
                            t_desc=list(reversed(range(self.timesteps)))[:num_steps], progress=progress,
-                           noise_fn=noise_fn)
+                           noise_fn=noise_fn, guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
 
     # ---- single reverse steps with per-sample timesteps (diffusion.py:249-338) -------------------------------------
     def _posterior_rows(self, t):
@@ -160,7 +162,7 @@ class GaussianDiffusion(nn.Module):
         return self._posterior(z_t, t, noise_pred, noise, clip_denoised, False, True)[1]
 
     def training_loss(self, model, z_0, c, mask=None, vae=None, v_gt=None, use_ssim=False, ssim_weight=0.0,
-                      t=None, noise=None):
+                      t=None, noise=None, cond_drop_prob=0.0, cond_keep=None):
         """Min-SNR-5 weighted epsilon-prediction loss (diffusion.py:108-247) with forward AND backward on the HIP
         engine: the returned scalar carries an autograd node whose backward launches the engine's gradient kernels
         and feeds the U-Net parameters' .grad.
@@ -170,7 +172,20 @@ class GaussianDiffusion(nn.Module):
         reference (no mask; mask with equal valid counts; mask with per-sample counts) are folded into one
         per-sample factor.  The optional MS-SSIM term (a gradient-free logging term: the reference decodes under no_grad)
         needs the third-party `pytorch_msssim`; without it the reference warns and returns the MSE loss, and so does this
-        engine (see the end of the function)."""
+        engine (see the end of the function).
+
+        Conditioning dropout (additive; what makes a checkpoint guidable): sample b trains on the null
+        conditioning c = 0 where keep[b] is False.  keep = torch.rand(B) >= cond_drop_prob is drawn AFTER t and noise, and
+        only when cond_drop_prob > 0, `cond_keep` is None and the U-Net is in training mode -- so cond_drop_prob = 0 leaves
+        the generator where it was, and a seed gives the same t and noise at every probability.  `cond_keep` (bool, (B,))
+        injects the mask.  The conditioning carries no gradient, so the backward is unchanged.  loss_dict gains
+        'cond_dropped' (the number of dropped samples) when a mask was in force."""
+        p_drop = float(cond_drop_prob)
+        if not 0.0 <= p_drop <= 1.0:
+            raise ValueError(f"cond_drop_prob must lie in [0, 1], got {cond_drop_prob!r}")
+        if cond_keep is not None and (not torch.is_tensor(cond_keep) or cond_keep.dtype != torch.bool
+                                      or tuple(cond_keep.shape) != (z_0.shape[0],)):
+            raise ValueError(f"cond_keep must be a bool tensor of shape ({z_0.shape[0]},)")
         from .train_engine import UNetTrainProgram, train_step
         from .engine import Ctx, cached_program
         if not z_0.is_cuda:
@@ -181,6 +196,12 @@ class GaussianDiffusion(nn.Module):
             t = torch.randint(0, self.timesteps, (B,), device=device, dtype=torch.long)
         if noise is None:
             noise = torch.randn_like(z_0)
+        keep = cond_keep
+        if keep is None and p_drop > 0.0 and getattr(model, "training", False):
+            keep = torch.rand(B, device=device) >= p_drop
+        if keep is not None:
+            keep = keep.to(device)
+            c = c * keep.to(c.dtype)[:, None, None, None, None]
         snr = self.alphas_cumprod[t] / (1 - self.alphas_cumprod[t] + 1e-8)
         snr_weight = torch.clamp(snr, max=5.0) / (snr + 1e-8)
         if mask is not None:
@@ -204,6 +225,8 @@ class GaussianDiffusion(nn.Module):
             prog.set_diffusion(self)
         loss = train_step(prog, z_0.detach().float(), c.detach().float(), t, noise.float(), norm, m)
         loss_dict = {'mse': loss.item()}
+        if keep is not None:
+            loss_dict['cond_dropped'] = int((~keep).sum().item())
         prog.check_errors()     # (the stream is synchronised by the .item() above: a sticky split-K hand-off error of this forward,
                                 #  or of the previous step's backward, surfaces here)
         # Optional MS-SSIM term (diffusion.py:204-240).  The reference decodes the predicted z_0 under torch.no_grad(), so the

@@ -1078,18 +1078,29 @@ def sampler_step_launcher(lib, kind: str, f32: bool) -> Callable:
 
 class UNetProgram(Program):
     """One U-Net evaluation (models/unet3d.py:357-413) at a fixed latent shape, followed optionally by
-    a sampler update; `step_ptr` selects the timestep row, so one captured graph serves all steps."""
+    a sampler update; `step_ptr` selects the timestep row, so one captured graph serves all steps.
+
+    `guided` (classifier-free guidance): the network runs at batch 2n -- rows [0, n) on the
+    conditioning, rows [n, 2n) on the null conditioning, the all-zero latent -- and add_sampler_step puts ctsi_cfg_combine
+    between the network and the update and ctsi_cfg_mirror behind it.  z, hist, noise, the nonfinite table and
+    z_ncdhw() / eps_ncdhw() stay n-sized; timestep rows are per (evaluation, network row): 2n per evaluation.
+    `rescale` adds the statistics pass of the guidance rescale (phi > 0)."""
 
     def __init__(self, ctx: Ctx, unet, n: int, d: int, h: int, w: int, max_rows: int, attention_mode="fast",
-                 shard=None):
+                 shard=None, guided: bool = False, rescale: bool = False):
         """`d` is the depth this program owns: the whole volume on one GPU, or the rank's slab of
         `shard.depth_total // shard.world` slices when `shard` (parallel.ShardSpec) is given."""
         super().__init__(ctx)
         self.shard = shard
         if shard is not None and n != 1:
             raise CtsiError("depth-sharded programs support one volume per rank")
+        if shard is not None and guided:
+            raise CtsiError("classifier-free guidance does not support depth sharding: the sharded program holds one "
+                            "volume per rank and the rescale statistics would need a collective")
         self.unet = unet
+        self.guided, self.rescale = bool(guided), bool(guided and rescale)
         self.n, self.d, self.h, self.w = n, d, h, w
+        n = self.nb = 2 * n if guided else n        # the network's batch; self.n stays the number of samples
         L = unet.latent_dim
         self.L = L
         dev = ctx.device
@@ -1098,7 +1109,7 @@ class UNetProgram(Program):
         halo = 0 if shard is None else 1
         self.xin, self.xin2 = self._input_acts(n, d, h, w, halo)
         self.eps = self.persistent((n, d, h, w, L), torch.float32)
-        self.z = self.persistent((n, d, h, w, L), torch.float32, zero=True)
+        self.z = self.persistent((self.n, d, h, w, L), torch.float32, zero=True)
         self.step_ptr = self.persistent((1,), torch.int32, zero=True)
         self.t_rows = self.persistent((max_rows,), torch.int32, zero=True)
         self.t_rows_f = self.persistent((max_rows,), torch.float32, zero=True)   # fractional timesteps (EDM sampler)
@@ -1200,6 +1211,8 @@ class UNetProgram(Program):
             z = z_ncdhw.detach()[:, :, lo:lo + d].to(device=self.ctx.device, dtype=torch.float32).contiguous()
             lib.ncdhw_f32_to_ndhwc_f32(_ptr(z), _ptr(self.z), n, L, d, h, w, sptr)
             lib.ncdhw_f32_to_ndhwc_bf16(_ptr(z), self.xin.ip, n, L, d, h, w, 2 * L, 0, sptr)
+            if self.guided:     # both halves of z; rows [n, 2n) of the conditioning stay zero (the null conditioning)
+                lib.ncdhw_f32_to_ndhwc_bf16(_ptr(z), self._uncond_zin(), n, L, d, h, w, 2 * L, 0, sptr)
             z.record_stream(self.ctx.stream)
             self.xin.dirty = True
         if cond_ncdhw is not None:
@@ -1207,10 +1220,21 @@ class UNetProgram(Program):
             lib.ncdhw_f32_to_ndhwc_bf16(_ptr(cnd), self.xin.ip, n, L, d, h, w, 2 * L, L, sptr)
             cnd.record_stream(self.ctx.stream)
 
+    def set_guidance(self, scale: float, rescale: float = 0.0):
+        """Write {s, phi} into every row of the guided program's scale table (read at *step_ptr by ctsi_cfg_combine /
+        ctsi_cfg_stats): a plain device write, the captured graph is untouched."""
+        if not self.guided:
+            raise CtsiError("internal: set_guidance on a program built without guidance")
+        if rescale > 0.0 and not self.rescale:
+            raise CtsiError("internal: guidance_rescale > 0 needs a program built with the statistics pass")
+        row = torch.tensor([float(scale), float(rescale)], dtype=torch.float32)
+        self.cfg_scale.copy_(row.expand(self.cfg_scale.shape[0], 2))
+
     def set_schedule(self, t_rows: Sequence[float], coef_rows: Optional[torch.Tensor] = None):
-        """Upload the timestep of every (step, sample) row, embed all of them in one go and rewind the
-        device-side step counter.  Integer-valued rows take the int32 entry (ctsi_time_embed_fwd); a schedule with any
-        fractional timestep is embedded from fp32 rows (ctsi_time_embed_fwd_tf)."""
+        """Upload the timestep of every (step, network row) row -- n per evaluation, 2n in a guided program -- embed all
+        of them in one go and rewind the device-side step counter.  Integer-valued rows take the int32 entry
+        (ctsi_time_embed_fwd); a schedule with any fractional timestep is embedded from fp32 rows
+        (ctsi_time_embed_fwd_tf)."""
         rows = len(t_rows)
         if rows > self.max_rows:
             raise CtsiError(f"schedule needs {rows} rows but the program was built for {self.max_rows}")
@@ -1230,6 +1254,7 @@ class UNetProgram(Program):
               _ptr(self.w_all), _ptr(self.b_all), self.total_out, _ptr(self.te_scratch), _ptr(self.tbias), sptr)
 
     def eps_ncdhw(self) -> torch.Tensor:
+        """The noise prediction the update reads, fp32 NCDHW: rows [0, n) of `eps` (the guided eps in a guided program)."""
         out = torch.empty((self.n, self.L, self.d, self.h, self.w), dtype=torch.float32, device=self.ctx.device)
         self.lib.ndhwc_f32_to_ncdhw_f32(_ptr(self.eps), _ptr(out), self.n, self.L, self.d, self.h, self.w,
                                         self.ctx.sptr)
@@ -1248,12 +1273,48 @@ class UNetProgram(Program):
         element, fp32 entry).  Here the z half of the bf16 [z | cond] tensor."""
         return self.xin.ip, 2 * self.L, 2, False
 
+    def _uncond_zin(self) -> C.c_void_p:
+        """Guided programs: where rows [n, 2n) of the slice of _sampler_zin start."""
+        _, c_total, nbytes, _ = self._sampler_zin()
+        return C.c_void_p(self._sampler_zin()[0].value + self.n * self.d * self.h * self.w * c_total * nbytes)
+
+    def _add_guidance_combine(self):
+        """ctsi_cfg_combine (behind the statistics pass when the program rescales) over the batch-2n eps."""
+        lib, sptr = self.lib, self.ctx.sptr
+        n, L, d, h, w = self.n, self.L, self.d, self.h, self.w
+        numel = float(n * L * d * h * w)
+        rows = max(self.max_rows // (2 * n), 1)                    # one {s, phi} row per evaluation
+        self.cfg_scale = self.persistent((rows, 2), torch.float32, zero=True)
+        self.cfg_scale[:, 0] = 1.0
+        ep, cs, sp = _ptr(self.eps), _ptr(self.cfg_scale), _ptr(self.step_ptr)
+        self.cfg_stats = None
+        if self.rescale:
+            bps = lib.cfg_stats_blocks(L * d * h * w)
+            self.cfg_partials = self.persistent((n * bps * 4,), torch.float64, zero=True)
+            self.cfg_stats = self.persistent((n, 4), torch.float64, zero=True)
+            pp, stp = _ptr(self.cfg_partials), _ptr(self.cfg_stats)
+            self._emit(lambda: lib.cfg_stats(ep, cs, sp, pp, n, L, d, h, w, sptr), "cfg.stats", nbytes=8.0 * numel)
+            self._emit(lambda: lib.cfg_stats_finalize(pp, stp, n, L, d, h, w, sptr), "cfg.stats_finalize")
+        stp = _ptr(self.cfg_stats)
+        self._emit(lambda: lib.cfg_combine(ep, cs, sp, stp, n, L, d, h, w, sptr), "cfg.combine", nbytes=12.0 * numel)
+
+    def _add_guidance_mirror(self):
+        """ctsi_cfg_mirror: the z the update wrote into rows [0, n) of the network input, copied to rows [n, 2n)."""
+        lib, sptr = self.lib, self.ctx.sptr
+        src, c_total, nbytes, _ = self._sampler_zin()
+        dst = self._uncond_zin()
+        rows, L = self.n * self.d * self.h * self.w, self.L
+        self._emit(lambda: lib.cfg_mirror(src, dst, rows, L * nbytes, c_total * nbytes, sptr), "cfg.mirror",
+                   nbytes=2.0 * rows * L * nbytes)
+
     def add_sampler_step(self, kind: str, with_noise: bool):
         """Append the update of sampler `kind` (a SAMPLER_STEPS key) and the step-counter increment (done once, before
         capture).  'heun': one update per U-Net evaluation (predictor, corrector or final row); `with_noise` = churn on."""
         lib, sptr = self.lib, self.ctx.sptr
         n, L, d, h, w = self.n, self.L, self.d, self.h, self.w
         entry = SAMPLER_STEPS[kind]
+        if self.guided:
+            self._add_guidance_combine()
         if with_noise and self.noise is None:
             self.noise = self.persistent((n, L, d, h, w), torch.float32, zero=True)
         xp, c_total, zin_bytes, f32 = self._sampler_zin()
@@ -1280,6 +1341,8 @@ class UNetProgram(Program):
         step_bytes = (4 + 4 + 4 + zin_bytes + (4 if with_noise else 0) + (8 if entry.hist else 0)) * float(
             n * L * d * h * w)
         self._emit(run_step, "sampler.step", nbytes=step_bytes)
+        if self.guided:
+            self._add_guidance_mirror()
         self._emit(run_adv, "sampler.advance")
         self.sampler_kind = (kind, with_noise)
 

@@ -268,13 +268,14 @@ class UNetProgramF32(_F32Ops, UNetProgram):
     """engine.UNetProgram in fp32.  The network input is two fp32 NDHWC tensors, z and the conditioning, fed to conv_in as
     a concatenated pair (never materialised)."""
 
-    def __init__(self, ctx: Ctx, unet, n: int, d: int, h: int, w: int, max_rows: int, attention_mode="fast", shard=None):
+    def __init__(self, ctx: Ctx, unet, n: int, d: int, h: int, w: int, max_rows: int, attention_mode="fast", shard=None,
+                 guided: bool = False, rescale: bool = False):
         if shard is not None:
             raise CtsiError("the fp32 inference mode does not support depth sharding")
         if attention_mode != "fast":
             raise CtsiError("the fp32 inference mode supports attention_mode='fast' only (the exact mode evaluates the "
                             "same mathematics, DESIGN section 3.2)")
-        super().__init__(ctx, unet, n, d, h, w, max_rows, attention_mode, shard=None)
+        super().__init__(ctx, unet, n, d, h, w, max_rows, attention_mode, shard=None, guided=guided, rescale=rescale)
 
     def _input_acts(self, n, d, h, w, halo) -> Tuple[Act, Optional[Act]]:
         L = self.L
@@ -289,6 +290,8 @@ class UNetProgramF32(_F32Ops, UNetProgram):
             z = z_ncdhw.detach().to(device=self.ctx.device, dtype=torch.float32).contiguous()
             lib.ncdhw_f32_to_ndhwc_f32(_ptr(z), _ptr(self.z), n, L, d, h, w, sptr)
             lib.ncdhw_f32_to_ndhwc_f32(_ptr(z), _ptr(self.xin.t), n, L, d, h, w, sptr)
+            if self.guided:     # both halves of z; rows [n, 2n) of the conditioning stay zero (the null conditioning)
+                lib.ncdhw_f32_to_ndhwc_f32(_ptr(z), self._uncond_zin(), n, L, d, h, w, sptr)
             z.record_stream(self.ctx.stream)
         if cond_ncdhw is not None:
             cnd = cond_ncdhw.detach().to(device=self.ctx.device, dtype=torch.float32).contiguous()

@@ -182,6 +182,11 @@ SIGNATURES = {
     "ctsi_dpm_step_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp], True),
     "ctsi_heun_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp], True),
     "ctsi_heun_step_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp], True),
+    "ctsi_cfg_stats_blocks": (_i, [_ll], False),
+    "ctsi_cfg_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_cfg_stats": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_cfg_stats_finalize": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_cfg_mirror": (_i, [_vp, _vp, _ll, _i, _i, _vp], True),
     "ctsi_graph_begin_capture": (_i, [_vp], True),
     "ctsi_graph_end_capture": (_i, [_vp, C.POINTER(_vp)], True),
     "ctsi_graph_launch": (_i, [_vp, _vp], True),

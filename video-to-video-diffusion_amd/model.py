@@ -12,7 +12,7 @@ from .diffusion import GaussianDiffusion
 from .engine import Ctx, nan_to_num_, trilinear_depth
 from .engine_f32 import check_precision
 from .lib import CtsiError
-from .sampler import SAMPLERS
+from .sampler import SAMPLERS, check_guidance
 from .unet3d import UNet3D
 from .vae import VideoVAE
 
@@ -65,6 +65,10 @@ class VideoToVideoDiffusion(nn.Module):
                                            beta_end=config.get('beta_end', 0.02))
         self.config = config
         self.use_pretrained = use_pretrained
+        # additive key, top level like every U-Net / diffusion key: the conditioning-dropout probability of `forward`
+        self.cond_drop_prob = float(config.get('cond_drop_prob', 0.0))
+        if not 0.0 <= self.cond_drop_prob <= 1.0:
+            raise ValueError(f"cond_drop_prob must lie in [0, 1], got {config.get('cond_drop_prob')!r}")
         # additive key: the arithmetic of generate() / the samplers / encode / decode ('bf16' default, or 'fp32')
         self.set_inference_precision(config.get('hardware', {}).get('inference_precision', 'bf16'))
 
@@ -92,10 +96,13 @@ class VideoToVideoDiffusion(nn.Module):
     def decode_latent(self, z):
         return self.vae.decode(z)
 
-    def forward(self, v_in, v_gt, mask=None, t=None, noise=None):
+    def forward(self, v_in, v_gt, mask=None, t=None, noise=None, cond_keep=None):
         """Training forward (model.py:158-228): frozen-VAE encode of both volumes, depth upsample of the
         conditioning when the depths differ, then `diffusion.training_loss` on the HIP engine.  Returns
-        (loss, metrics); `loss.backward()` runs the engine's backward.  `t=` / `noise=` are test hooks."""
+        (loss, metrics); `loss.backward()` runs the engine's backward.  `t=` / `noise=` are test hooks.
+        In training mode every sample's conditioning is replaced by the null conditioning (zeros) with the probability
+        of the top-level config key `cond_drop_prob` (default 0: never, and no random number is drawn), which is what
+        classifier-free guidance at sampling time needs; `cond_keep` (bool, (B,)) injects the mask instead."""
         if not v_in.is_cuda:
             raise CtsiError("the training forward runs on the HIP engine: move the inputs to a ROCm device")
         ctx = Ctx.get(v_in.device)
@@ -113,28 +120,36 @@ class VideoToVideoDiffusion(nn.Module):
             else:
                 z_cond, z_mask = z_in, mask
         loss, loss_dict = self.diffusion.training_loss(self.unet, z_gt, z_cond, mask=z_mask, vae=self.vae, v_gt=v_gt,
-                                                       use_ssim=False, ssim_weight=0.0, t=t, noise=noise)
+                                                       use_ssim=False, ssim_weight=0.0, t=t, noise=noise,
+                                                       cond_drop_prob=self.cond_drop_prob, cond_keep=cond_keep)
         return loss, {'loss': loss.item(), **loss_dict}
 
     @torch.no_grad()
     def generate(self, v_in, sampler, num_inference_steps=20, guidance_scale=1.0, target_depth=None,
-                 noise_fn=None, precision=None):
+                 noise_fn=None, precision=None, guidance_rescale=0.0):
         """thick slices (B, C, T_in, H, W) -> thin slices (B, C, T_out, H, W), fp32.
 
         encode -> trilinear depth upsample of the conditioning -> DDIM/DDPM -> decode, with the
         reference's nan_to_num guards applied unconditionally on device (model.py:230-343).
-        `guidance_scale` is accepted and ignored, as in the reference.
+        `guidance_scale` s is honoured (the reference accepts and ignores it): classifier-free guidance against the null
+        conditioning, the all-zero latent -- eps = eps_u + s (eps_c - eps_u), both from ONE batch-2n U-Net evaluation per
+        step (sampler.run_sampler).  1.0 (default) is the unguided path, bit for bit; 0 samples
+        unconditionally.  `guidance_rescale` phi in [0, 1] (additive, default 0) rescales eps to the conditional branch's
+        per-sample standard deviation: eps <- phi eps std(eps_c) / std(eps) + (1 - phi) eps.  Encode, depth upsample and
+        decode run once per volume.  Only a model trained with `cond_drop_prob` > 0 has seen the null conditioning.
         `sampler` also accepts 'dpmpp_2m' (additive): DPM-Solver++(2M) with `num_inference_steps` steps
         (sampler.DPMSolverSampler), e.g. 20 steps in place of DDIM-50, and 'heun' (additive): EDM Heun with
         `num_inference_steps` steps on Karras sigmas, 2 N - 1 U-Net evaluations (sampler.HeunSampler).
         `precision` (additive, default None = the models' `inference_precision` attributes): 'bf16' or 'fp32' for this
         call only; the attributes are restored afterwards."""
+        check_guidance(guidance_scale, guidance_rescale)
         if precision is not None:
             check_precision(precision)
             saved = (self.unet.inference_precision, self.vae.inference_precision)
             self.unet.inference_precision = self.vae.inference_precision = precision
             try:
-                return self.generate(v_in, sampler, num_inference_steps, guidance_scale, target_depth, noise_fn)
+                return self.generate(v_in, sampler, num_inference_steps, guidance_scale, target_depth, noise_fn,
+                                     guidance_rescale=guidance_rescale)
             finally:
                 self.unet.inference_precision, self.vae.inference_precision = saved
         if sampler not in SAMPLERS:
@@ -156,7 +171,8 @@ class VideoToVideoDiffusion(nn.Module):
         if noise_fn is None:
             torch.randn(latent_shape, device=device)  # model.py:303 draws (and discards) one latent
         z_0 = SAMPLERS[sampler](self.diffusion, self.unet, latent_shape, z_cond, num_inference_steps, device,
-                                noise_fn=noise_fn)
+                                noise_fn=noise_fn, guidance_scale=guidance_scale,
+                                guidance_rescale=guidance_rescale)
         with ctx.scope():
             nan_to_num_(ctx, z_0)
         v_out = self.vae.decode(z_0)

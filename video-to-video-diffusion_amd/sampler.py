@@ -66,6 +66,21 @@ def _check_eps(eps, shape):
                         f"{tuple(shape)}, got {type(eps).__name__} {tuple(getattr(eps, 'shape', ()))}")
 
 
+def check_guidance(guidance_scale, guidance_rescale) -> Tuple[float, float]:
+    """Validate the classifier-free guidance arguments (before any launch): a finite scale (0 and negatives included; 0
+    is unconditional sampling, 1 the unguided path) and a rescale phi in [0, 1].  Returns them as floats."""
+    try:
+        s, phi = float(guidance_scale), float(guidance_rescale)
+    except (TypeError, ValueError):
+        raise ValueError(f"guidance_scale / guidance_rescale must be numbers, got {guidance_scale!r}, "
+                         f"{guidance_rescale!r}") from None
+    if not math.isfinite(s):
+        raise ValueError(f"guidance_scale must be finite, got {guidance_scale!r}")
+    if not 0.0 <= phi <= 1.0:     # (a NaN fails both comparisons)
+        raise ValueError(f"guidance_rescale must lie in [0, 1], got {guidance_rescale!r}")
+    return s, phi
+
+
 def _draw_noise(noise_fn, i, shape, dev) -> torch.Tensor:
     return (noise_fn(i, tuple(shape)) if noise_fn is not None
             else torch.randn(tuple(shape), device=dev)).to(dev, torch.float32)
@@ -328,13 +343,16 @@ def _replay(plan: StepPlan, evals, load_noise, launch):
 
 
 def _run_generic(plan: StepPlan, model, shape, conditioning, ctx, z0, *, noise_fn, progress, trajectory,
-                 eps_trajectory):
+                 eps_trajectory, guidance: Optional[Tuple[float, float]] = None):
     """Reverse loop over an ARBITRARY `model(z, t, c) -> eps` callable (the reference's samplers accept any,
     inference/sampler.py:211-219): the network evaluation is the caller's (any torch code on the ROCm device), the
     update with its guards is the engine's `_f32` entry of the plan's kind, once per evaluation.  Not captured: the
     callable is opaque.  The engine's own UNet3D takes the hipGraph path in run_sampler instead.
     The model sees t as plan.t_dtype (Heun's fractional timesteps as fp32, as the reference embeds t) and as z the
-    input the update writes to `zin`: the new state, or after a Heun predictor row the corrector's z' (z keeps zhat)."""
+    input the update writes to `zin`: the new state, or after a Heun predictor row the corrector's z' (z keeps zhat).
+    `guidance` = (s, phi): classifier-free guidance -- two calls per evaluation, model(z, t, c) and model(z, t,
+    zeros_like(c)), combined by ctsi_cfg_combine (the entry of the guided step program); eps_trajectory then holds the
+    guided eps."""
     lib, sptr = ctx.lib, ctx.sptr
     n, L, d, h, w = [int(v) for v in shape]
     evals = len(plan.t)
@@ -343,12 +361,20 @@ def _run_generic(plan: StepPlan, model, shape, conditioning, ctx, z0, *, noise_f
     coef = plan.coef.to(dev, torch.float32).contiguous()
     z_nd = torch.empty((n, d, h, w, L), dtype=torch.float32, device=dev)
     zin_nd = torch.empty_like(z_nd)
-    eps_nd = torch.empty_like(z_nd)
+    eps_nd = torch.empty(((2 if guidance else 1) * n, d, h, w, L), dtype=torch.float32, device=dev)
     hist = torch.zeros_like(z_nd) if SAMPLER_STEPS[plan.kind].hist else None
     step_ptr = torch.zeros(1, dtype=torch.int32, device=dev)
     nonfinite = torch.zeros((evals + 2, 6), dtype=torch.int32, device=dev)
     cond = conditioning.to(dev)
     z = z0.to(dev, torch.float32).contiguous()
+    if guidance:
+        null_cond = torch.zeros_like(cond)
+        cfg_scale = torch.tensor([guidance], dtype=torch.float32, device=dev)
+        cfg_stats = cfg_partials = None
+        if guidance[1] > 0.0:
+            cfg_partials = torch.zeros(n * lib.cfg_stats_blocks(L * d * h * w) * 4, dtype=torch.float64, device=dev)
+            cfg_stats = torch.zeros((n, 4), dtype=torch.float64, device=dev)
+        eps_u_nd = eps_nd[n:]
     with ctx.scope():
         lib.count_nonfinite_f32(_ptr(z), z.numel(), 1, C.c_void_p(nonfinite.data_ptr() + evals * 24), sptr)
         cf = cond.float().contiguous()
@@ -359,13 +385,27 @@ def _run_generic(plan: StepPlan, model, shape, conditioning, ctx, z0, *, noise_f
         eps = model(z, t, cond)
         _check_eps(eps, shape)
         eps = eps.detach().to(torch.float32).contiguous()
-        if eps_trajectory is not None:
+        if guidance:
+            eps_u = model(z, t, null_cond)
+            _check_eps(eps_u, shape)
+            eps_u = eps_u.detach().to(torch.float32).contiguous()
+        elif eps_trajectory is not None:
             eps_trajectory.append(eps.clone())
         noise = None
         if plan.noise_step[e] >= 0:
             noise = _draw_noise(noise_fn, plan.noise_step[e], shape, dev).contiguous()
         with ctx.scope():
             lib.ncdhw_f32_to_ndhwc_f32(_ptr(eps), _ptr(eps_nd), n, L, d, h, w, sptr)
+            if guidance:
+                lib.ncdhw_f32_to_ndhwc_f32(_ptr(eps_u), _ptr(eps_u_nd), n, L, d, h, w, sptr)
+                if cfg_stats is not None:
+                    lib.cfg_stats(_ptr(eps_nd), _ptr(cfg_scale), None, _ptr(cfg_partials), n, L, d, h, w, sptr)
+                    lib.cfg_stats_finalize(_ptr(cfg_partials), _ptr(cfg_stats), n, L, d, h, w, sptr)
+                lib.cfg_combine(_ptr(eps_nd), _ptr(cfg_scale), None, _ptr(cfg_stats), n, L, d, h, w, sptr)
+                if eps_trajectory is not None:
+                    eps_g = torch.empty((n, L, d, h, w), dtype=torch.float32, device=dev)
+                    lib.ndhwc_f32_to_ncdhw_f32(_ptr(eps_nd), _ptr(eps_g), n, L, d, h, w, sptr)
+                    eps_trajectory.append(eps_g)
             step(_ptr(z_nd), _ptr(eps_nd), _ptr(hist), _ptr(noise), _ptr(zin_nd), L, _ptr(coef), _ptr(step_ptr), n, L,
                  d, h, w, _ptr(nonfinite), sptr)
             lib.step_advance(_ptr(step_ptr), sptr)
@@ -438,13 +478,20 @@ def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, 
 def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_desc: Sequence[int],
                 progress: bool, eta: float = 0.0, noise_fn=None, z_init: Optional[torch.Tensor] = None,
                 trajectory: Optional[list] = None, order: int = 2, eps_trajectory: Optional[list] = None,
-                heun: Optional[HeunRows] = None):
+                heun: Optional[HeunRows] = None, guidance_scale: float = 1.0, guidance_rescale: float = 0.0):
     """Shared reverse loop.  kind: 'ddim' | 'ddpm' | 'dpmpp' (DPM-Solver++ of `order` 1 or 2) | 'heun' (EDM of `order` 1
     or 2 on the rows `heun` = heun_coef_rows(...), t_desc = heun.t); t_desc: descending timestep list.
     `eps_trajectory` (unsharded runs only): receives the noise prediction of every U-Net evaluation, fp32 NCDHW.
     'heun': `trajectory` receives the state after every completed step (the VP latent zhat_{i+1}, which already holds
     step i+1's churn; the output last); the initial draw eps becomes zhat_0 = (sigma_0 eps + churn_0 eps_0) / a(sigma_hat_0),
-    eps_0 = noise_fn(0, shape) drawn only when step 0 churns."""
+    eps_0 = noise_fn(0, shape) drawn only when step 0 churns.
+    `guidance_scale` s, `guidance_rescale` phi: classifier-free guidance.  s == 1.0 is the unguided
+    path, untouched.  Any other finite s evaluates the U-Net on the conditioning and on the null conditioning (the
+    all-zero latent) as ONE batch-2n evaluation inside the captured step, and feeds eps = m (eps_u + s (eps_c - eps_u)),
+    m = phi std(eps_c) / std(eps_g) + 1 - phi per sample, to the unchanged update; trajectories and nonfinite counters
+    report on that eps.  Not available with depth sharding (CtsiError)."""
+    s_cfg, phi_cfg = check_guidance(guidance_scale, guidance_rescale)
+    guided = s_cfg != 1.0
     plan = _step_plan(diffusion, kind, t_desc, eta, order, heun)
     if not _is_engine_unet(model) and not callable(model):
         raise CtsiError(f"the samplers need a model(z, t, c) callable; got {type(model).__name__}")
@@ -452,7 +499,13 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
     device = torch.device(device)
     ctx = Ctx.get(device if device.type == "cuda" else conditioning.device)
     n, L, d, h, w = [int(v) for v in shape]
-    max_rows = (diffusion.timesteps + 1) * n
+    nb = 2 * n if guided else n                 # rows of one U-Net evaluation
+    max_rows = (diffusion.timesteps + 1) * nb
+    comm = getattr(unet, "depth_shard_comm", None) if _is_engine_unet(model) else None
+    if guided and comm is not None and comm.world > 1:
+        raise CtsiError("classifier-free guidance (guidance_scale != 1.0) does not support depth sharding "
+                        "(unet.depth_shard_comm): the sharded program holds one volume per rank and the rescale "
+                        "statistics would need a collective; drop the communicator or sample unguided")
     # initial noise is drawn exactly where the reference draws it (on the caller's stream/generator)
     if z_init is not None:
         z0 = z_init
@@ -463,9 +516,9 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
     z0 = plan.initial_state(z0, noise_fn, shape, ctx.device)
     if not _is_engine_unet(model):
         return _run_generic(plan, model, shape, conditioning, ctx, z0, noise_fn=noise_fn, progress=progress,
-                            trajectory=trajectory, eps_trajectory=eps_trajectory)
+                            trajectory=trajectory, eps_trajectory=eps_trajectory,
+                            guidance=(s_cfg, phi_cfg) if guided else None)
     precision = check_precision(getattr(unet, "inference_precision", "bf16"))
-    comm = getattr(unet, "depth_shard_comm", None)
     if comm is not None and comm.world > 1:
         if precision != "bf16":
             raise CtsiError("the fp32 inference mode does not support depth sharding (unet.depth_shard_comm); "
@@ -475,13 +528,16 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
         return run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, kind=kind, t_desc=t_desc, eta=eta,
                                    noise_fn=noise_fn, comm=comm, trajectory=trajectory, order=order, heun=heun)
     with ctx.scope():
-        key = (("sampler", ctx.device.index, n, d, h, w, max_rows) + plan.key + (unet.attention_mode, precision)
-               + plan.key_order)
+        # the unguided key is what it always was; a guided program (with or without the rescale statistics) has its own
+        head = ("sampler-cfg", ctx.device.index, n, d, h, w, max_rows, phi_cfg > 0.0) if guided else (
+            "sampler", ctx.device.index, n, d, h, w, max_rows)
+        key = head + plan.key + (unet.attention_mode, precision) + plan.key_order
         from .engine import cached_program
 
         def build():
             cls = UNetProgramF32 if precision == "fp32" else UNetProgram
-            prog = cls(ctx, unet, n, d, h, w, max_rows, unet.attention_mode)
+            kw = dict(guided=True, rescale=phi_cfg > 0.0) if guided else {}
+            prog = cls(ctx, unet, n, d, h, w, max_rows, unet.attention_mode, **kw)
             prog.add_sampler_step(plan.kind, plan.with_noise)
             return prog
 
@@ -495,7 +551,9 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
         cnd = conditioning.detach().to(ctx.device, torch.float32).contiguous()
         ctx.lib.count_nonfinite_f32(_ptr(cnd), cnd.numel(), 0, C.c_void_p(nf_tail + 24), ctx.sptr)
         cnd.record_stream(ctx.stream)
-        prog.set_schedule([t for t in plan.t for _ in range(n)], plan.coef.to(ctx.device))
+        prog.set_schedule([t for t in plan.t for _ in range(nb)], plan.coef.to(ctx.device))
+        if guided:
+            prog.set_guidance(s_cfg, phi_cfg)     # a device write: the same captured graph serves every scale
         if prog.graph is None:
             # one eager warm-up step is not needed: capture records launches without executing them
             prog.capture()
@@ -544,6 +602,8 @@ class _Sampler:
         """sample_with_stitching on `num_inference_steps` steps (`kw`: more sample() arguments).  Windows are batched
         (up to `window_batch`; None / 0: as many as the device memory holds, see _stitched) only when `batchable`, i.e.
         when the sampler draws no noise after the initial latent."""
+        s_cfg, _ = check_guidance(kw.get("guidance_scale", 1.0), kw.get("guidance_rescale", 0.0))
+
         def sample(shp, cond, z_init=None):
             return self.sample(shp, cond, num_inference_steps, device, progress=False, z_init=z_init, **kw)
 
@@ -551,7 +611,7 @@ class _Sampler:
             window_batch = 0
         return _stitched(self, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress, sample,
                          batched_fn=sample if batchable and window_batch != 1 else None, window_batch=window_batch,
-                         dp_group=dp_group)
+                         dp_group=dp_group, guided=s_cfg != 1.0)
 
 
 class DDPMSampler(_Sampler):
@@ -559,17 +619,21 @@ class DDPMSampler(_Sampler):
 
     @torch.no_grad()
     def sample(self, shape, conditioning, device, progress=True, noise_fn=None, num_steps=None,
-               trajectory=None):
+               trajectory=None, guidance_scale=1.0, guidance_rescale=0.0):
         t_desc = list(reversed(range(self.timesteps)))[:num_steps]
         return run_sampler(self.diffusion, self.model, shape, conditioning, device, kind="ddpm", t_desc=t_desc,
-                           progress=progress, noise_fn=noise_fn, trajectory=trajectory)
+                           progress=progress, noise_fn=noise_fn, trajectory=trajectory,
+                           guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
 
     @torch.no_grad()
     def sample_with_stitching(self, v_thick_full, vae, patch_size=(8, 192, 192),
                               target_patch_size=(48, 192, 192), stride=(4, 96, 96), device='cuda',
-                              progress=True, dp_group=None):
+                              progress=True, dp_group=None, guidance_scale=1.0, guidance_rescale=0.0):
+        check_guidance(guidance_scale, guidance_rescale)
         return _stitched(self, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress,
-                         lambda shp, cond: self.sample(shp, cond, device, progress=False), dp_group=dp_group)
+                         lambda shp, cond: self.sample(shp, cond, device, progress=False,
+                                                       guidance_scale=guidance_scale,
+                                                       guidance_rescale=guidance_rescale), dp_group=dp_group)
 
 
 class DDIMSampler(_Sampler):
@@ -577,15 +641,17 @@ class DDIMSampler(_Sampler):
 
     @torch.no_grad()
     def sample(self, shape, conditioning, num_inference_steps, device, eta=0.0, progress=True, noise_fn=None,
-               trajectory=None, z_init=None):
+               trajectory=None, z_init=None, guidance_scale=1.0, guidance_rescale=0.0):
         t_desc = [int(t) for t in self._get_timesteps(num_inference_steps)]
         return run_sampler(self.diffusion, self.model, shape, conditioning, device, kind="ddim", t_desc=t_desc,
-                           progress=progress, eta=float(eta), noise_fn=noise_fn, trajectory=trajectory, z_init=z_init)
+                           progress=progress, eta=float(eta), noise_fn=noise_fn, trajectory=trajectory, z_init=z_init,
+                           guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
 
     @torch.no_grad()
     def sample_with_stitching(self, v_thick_full, vae, num_inference_steps=20, patch_size=(8, 192, 192),
                               target_patch_size=(48, 192, 192), stride=(4, 96, 96), device='cuda', eta=0.0,
-                              progress=True, window_batch=None, dp_group=None):
+                              progress=True, window_batch=None, dp_group=None, guidance_scale=1.0,
+                              guidance_rescale=0.0):
         """`dp_group` (additive kwarg, default None = every window on this process, as in the reference): a
         torch.distributed process group (or True for the default group) over which the windows are split; every rank
         of the group must make the call with the SAME volume.
@@ -593,9 +659,12 @@ class DDIMSampler(_Sampler):
         that many are encoded / sampled / decoded as one batch -- a single 192x192 patch leaves most of an MI355X
         idle (its coarsest level has 28 conv tiles for 256 CUs).  None / 0 (default): as many as a fifth of the device
         memory holds (13 windows of 48 x 192 x 192 on a 288 GB part); 1: one by one, like the reference.  The initial noise of every window is still drawn
-        with its own `torch.randn` call in window order, exactly as the reference's one-by-one loop draws it."""
+        with its own `torch.randn` call in window order, exactly as the reference's one-by-one loop draws it.
+        `guidance_scale`, `guidance_rescale` (additive kwargs): classifier-free guidance of every window (run_sampler); a
+        guided window counts as two in the automatic `window_batch`."""
         return self._stitch(v_thick_full, vae, num_inference_steps, patch_size, target_patch_size, stride, device,
-                            progress, window_batch, dp_group, float(eta) == 0.0, eta=eta)
+                            progress, window_batch, dp_group, float(eta) == 0.0, eta=eta,
+                            guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
 
 
 class DPMSolverSampler(_Sampler):
@@ -612,20 +681,21 @@ class DPMSolverSampler(_Sampler):
 
     @torch.no_grad()
     def sample(self, shape, conditioning, num_inference_steps, device, progress=True, noise_fn=None, trajectory=None,
-               z_init=None):
+               z_init=None, guidance_scale=1.0, guidance_rescale=0.0):
         t_desc = [int(t) for t in self._get_timesteps(num_inference_steps)]
         return run_sampler(self.diffusion, self.model, shape, conditioning, device, kind="dpmpp", t_desc=t_desc,
                            progress=progress, noise_fn=noise_fn, trajectory=trajectory, z_init=z_init,
-                           order=self.order)
+                           order=self.order, guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
 
     @torch.no_grad()
     def sample_with_stitching(self, v_thick_full, vae, num_inference_steps=20, patch_size=(8, 192, 192),
                               target_patch_size=(48, 192, 192), stride=(4, 96, 96), device='cuda', progress=True,
-                              window_batch=None, dp_group=None):
-        """DDIMSampler.sample_with_stitching without `eta`: the same windows, blend, `window_batch` and `dp_group`
-        behaviour (the solver is deterministic, so windows are always batchable)."""
+                              window_batch=None, dp_group=None, guidance_scale=1.0, guidance_rescale=0.0):
+        """DDIMSampler.sample_with_stitching without `eta`: the same windows, blend, `window_batch`, `dp_group` and
+        guidance behaviour (the solver is deterministic, so windows are always batchable)."""
         return self._stitch(v_thick_full, vae, num_inference_steps, patch_size, target_patch_size, stride, device,
-                            progress, window_batch, dp_group, True)
+                            progress, window_batch, dp_group, True, guidance_scale=guidance_scale,
+                            guidance_rescale=guidance_rescale)
 
 
 class HeunSampler(_Sampler):
@@ -663,22 +733,24 @@ class HeunSampler(_Sampler):
 
     @torch.no_grad()
     def sample(self, shape, conditioning, num_inference_steps, device, progress=True, noise_fn=None, trajectory=None,
-               z_init=None, sigmas=None):
+               z_init=None, sigmas=None, guidance_scale=1.0, guidance_rescale=0.0):
         """`sigmas` (optional): explicit descending noise levels (a trailing 0 is appended when missing); they override
         the schedule and num_inference_steps."""
         rows = self.coef_rows(num_inference_steps, sigmas)
         return run_sampler(self.diffusion, self.model, shape, conditioning, device, kind="heun", t_desc=list(rows.t),
                            progress=progress, noise_fn=noise_fn, trajectory=trajectory, z_init=z_init,
-                           order=self.order, heun=rows)
+                           order=self.order, heun=rows, guidance_scale=guidance_scale,
+                           guidance_rescale=guidance_rescale)
 
     @torch.no_grad()
     def sample_with_stitching(self, v_thick_full, vae, num_inference_steps=20, patch_size=(8, 192, 192),
                               target_patch_size=(48, 192, 192), stride=(4, 96, 96), device='cuda', progress=True,
-                              window_batch=None, dp_group=None):
+                              window_batch=None, dp_group=None, guidance_scale=1.0, guidance_rescale=0.0):
         """DDIMSampler.sample_with_stitching without `eta`: windows are batched when s_churn == 0 and run one by one
         otherwise (each window then draws its own churn noise, as stochastic DDIM does)."""
         return self._stitch(v_thick_full, vae, num_inference_steps, patch_size, target_patch_size, stride, device,
-                            progress, window_batch, dp_group, self.s_churn == 0.0)
+                            progress, window_batch, dp_group, self.s_churn == 0.0, guidance_scale=guidance_scale,
+                            guidance_rescale=guidance_rescale)
 
 
 # generate() / generate_batch() sampler names -> how each samples a latent: (diffusion, model, shape, conditioning,
@@ -724,7 +796,7 @@ def _window_partition(windows, dp_group, sampler):
 
 
 def _stitched(sampler, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress, sample_fn,
-              batched_fn=None, window_batch=1, dp_group=None):
+              batched_fn=None, window_batch=1, dp_group=None, guided=False):
     """Sliding-window inference (sampler.py:63-172, 338-453): per window encode -> sample -> decode on the
     engine, Gaussian-weighted accumulation (ctsi_blend_accumulate) and final normalisation
     (ctsi_blend_normalize) on device.
@@ -777,6 +849,8 @@ def _stitched(sampler, v_thick_full, vae, patch_size, target_patch_size, stride,
             per_window = 2500.0 * b * td * th * tw
             if getattr(vae, "inference_precision", "bf16") == "fp32":
                 per_window *= 2.0         # fp32 activations: twice the bytes per voxel
+            if guided:
+                per_window *= 2.0         # a guided window is two rows of the U-Net's batch
             group = max(1, min(len(mine), int(0.2 * total / per_window)))
     ngroups = max(1, -(-len(mine) // group))            # balanced groups: 25 windows, window_batch 8 -> 7 + 6 + 6 + 6
     bounds = [round(i * len(mine) / ngroups) for i in range(ngroups + 1)]
