@@ -19,7 +19,8 @@ def to_act(prog, x_ncdhw, c_pad=None):
     buf = prog.persistent((n * d * h * w * ct,), torch.bfloat16, zero=True)
     xx = x_ncdhw.to(prog.ctx.device, torch.float32).contiguous()
     prog.lib.ncdhw_f32_to_ndhwc_bf16(_ptr(xx), _ptr(buf), n, c, d, h, w, ct, 0, prog.ctx.sptr)
-    prog.keep.append(xx)
+    # kept alive with the program, but not in `keep`: that list holds the engine's own allocations (tests/poison.py checks them)
+    prog.__dict__.setdefault("_test_inputs", []).append(xx)
     return E.Act(buf, n, ct, d, h, w)
 
 

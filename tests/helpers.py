@@ -59,3 +59,23 @@ def tiny_model_sd(pkg):
     cfg = dict(model_channels=32, num_res_blocks=1, attention_levels=[1], channel_mult=[1, 2], num_heads=4,
                scaling_factor=1.0)
     return model, sd, cfg
+
+
+# production sizes (BASELINE.json configs 1-3): the models behind the `full_model` / `prod_vae` fixtures
+FULL_UNET_CFG = dict(model_channels=128, num_res_blocks=2, attention_levels=[1, 2], channel_mult=[1, 2, 4, 4], num_heads=4,
+                     scaling_factor=1.0)
+FULL_CFG = {'model': {'in_channels': 1, 'latent_dim': 8, 'vae_base_channels': 128, 'vae_scaling_factor': 1.0},
+            'pretrained': {'use_pretrained': True, 'vae': {'enabled': True, 'checkpoint_path': 'unused'}},
+            'noise_schedule': 'cosine', 'diffusion_timesteps': 1000}
+
+
+def build_full_model(pkg, dev):
+    """The full 264.66 M-parameter model (production VAE + U-Net), seeded random weights, in eval mode on `dev`."""
+    torch.manual_seed(0)
+    return pkg.VideoToVideoDiffusion(FULL_CFG).eval().to(dev)
+
+
+def build_prod_vae(pkg, dev):
+    """The production VAE (base 128: 128/256/512 channels), seeded random weights, in eval mode on `dev`."""
+    torch.manual_seed(0)
+    return pkg.VideoVAE(in_channels=1, latent_dim=8, base_channels=128, scaling_factor=1.0).eval().to(dev)

@@ -15,18 +15,12 @@ import torch
 import torch.nn.functional as F
 
 from oracle import ref_ops as R
-from tests.helpers import bf16_round, rel_l2
+from tests.helpers import FULL_CFG, FULL_UNET_CFG as UNET_CFG, bf16_round, build_full_model, build_prod_vae, rel_l2
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 NET_TOL = 3e-2
 CONV_TOL = 3e-3
-UNET_CFG = dict(model_channels=128, num_res_blocks=2, attention_levels=[1, 2], channel_mult=[1, 2, 4, 4], num_heads=4,
-                scaling_factor=1.0)
-FULL_CFG = {'model': {'in_channels': 1, 'latent_dim': 8, 'vae_base_channels': 128, 'vae_scaling_factor': 1.0},
-            'pretrained': {'use_pretrained': True, 'vae': {'enabled': True, 'checkpoint_path': 'unused'}},
-            'noise_schedule': 'cosine', 'diffusion_timesteps': 1000}
-
 
 @pytest.fixture(autouse=True)
 def _convt_as_forward_conv(monkeypatch):
@@ -178,8 +172,7 @@ def test_legacy163_unet_at_512_latent(pkg):
 # --------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def prod_vae(pkg):
-    torch.manual_seed(0)
-    vae = pkg.VideoVAE(in_channels=1, latent_dim=8, base_channels=128, scaling_factor=1.0).eval().to(DEV)
+    vae = build_prod_vae(pkg, DEV)
     sd = {k: v.detach() for k, v in vae.state_dict().items()}
     yield vae, sd
     vae.invalidate_engine_cache()
@@ -226,8 +219,7 @@ def _noise_fn(i, shape):
 
 @pytest.fixture(scope="module")
 def full_model(pkg):
-    torch.manual_seed(0)
-    model = pkg.VideoToVideoDiffusion(FULL_CFG).eval().to(DEV)
+    model = build_full_model(pkg, DEV)
     sd = {k: v.detach() for k, v in model.state_dict().items()}
     yield model, sd
     model.invalidate_engine_cache()

@@ -123,7 +123,28 @@ HALO3_CASES = [
 ]
 
 
-@pytest.mark.parametrize("tile", ["16h", "16h3", "32", "16k", "32k", "32k3", "16k3", "16k3s", "32ks"])
+HALO3_TILES = ["16h", "16h3", "32", "16k", "32k", "32k3", "16k3", "16k3s", "32ks"]
+
+
+def halo3_tile_env(tile):
+    """The overrides that select one tile form of the 3x3x3 halo-tile kernels (also used by tests/test_gpu_poison.py).
+    "16h" / "16h3": 4x4x16 / 3x4x16 tile of the 32x32x16-MFMA kernel (two W-lines per A tile); "32": its 4x2x32 tile; "32k" / "16k": the 512-voxel tile (4x4x32 / 4x8x16) on 16x16x32 MFMAs over tap pairs
+    (conv3_halo_k32.hip); "32k3": its 3x4x32 = 384-voxel tile.  (Measured-slower variants -- round 1's persistent / half-size
+    blocks and 16x16x32 form of the 4x4x16 tile, the 32x32x16 form of the 512-voxel tile -- live under csrc/experiments/.)
+    "16k3": the 3x8x16 = 384-voxel tile; "16k3s": with 2-way split-K (Cin % 128 == 0 cases; the others fall back)
+    "32ks": the 4x4x32 tile with 2-way split-K"""
+    env = {"CTSI_CONV_FORCE_HALO3": "1",
+           "CTSI_CONV_HALO_TILE": "32" if tile == "16k" else tile[:2],   # ("16h3": the 192-voxel tile)
+           "CTSI_CONV_M512W16": "1" if tile == "16k" else "0",
+           "CTSI_CONV_K32_384": "1" if tile == "32k3" else "0",
+           "CTSI_CONV_K32_SPLITK": {"16k3": "plain", "16k3s": "1", "32ks": "512"}.get(tile, "0"),
+           "CTSI_CONV_M512": "1" if tile in ("32k", "16k", "32k3") else "0"}
+    if tile in ("16h", "16h3"):
+        env["CTSI_CONV_H32W16"] = {"16h": "1", "16h3": "2"}[tile]    # 4x4x16 / 3x4x16 tiles
+    return env
+
+
+@pytest.mark.parametrize("tile", HALO3_TILES)
 @pytest.mark.parametrize("name,c1,c2,cout,dims", HALO3_CASES, ids=[c[0] for c in HALO3_CASES])
 def test_conv3_halo_tile_kernel(G, monkeypatch, name, c1, c2, cout, dims, tile):
     """The LDS halo-tile 3x3x3 kernel (conv3_halo.hip) on aligned, ragged, multi-tile and two-source inputs;
@@ -136,19 +157,8 @@ def test_conv3_halo_tile_kernel(G, monkeypatch, name, c1, c2, cout, dims, tile):
     b = formula_input((cout,), 4) * 0.1
     ref = F.conv3d(x, wt, b, padding=1)
     groups = 8
-    monkeypatch.setenv("CTSI_CONV_FORCE_HALO3", "1")
-    # "16h" / "16h3": 4x4x16 / 3x4x16 tile of the 32x32x16-MFMA kernel (two W-lines per A tile); "32": its 4x2x32 tile; "32k" / "16k": the 512-voxel tile (4x4x32 / 4x8x16) on 16x16x32 MFMAs over tap pairs
-    # (conv3_halo_k32.hip); "32k3": its 3x4x32 = 384-voxel tile.  (Measured-slower variants -- round 1's persistent / half-size
-    # blocks and 16x16x32 form of the 4x4x16 tile, the 32x32x16 form of the 512-voxel tile -- live under csrc/experiments/.)
-    monkeypatch.setenv("CTSI_CONV_HALO_TILE", "32" if tile == "16k" else tile[:2])   # ("16h3": the 192-voxel tile)
-    monkeypatch.setenv("CTSI_CONV_M512W16", "1" if tile == "16k" else "0")
-    monkeypatch.setenv("CTSI_CONV_K32_384", "1" if tile == "32k3" else "0")
-    # "16k3": the 3x8x16 = 384-voxel tile; "16k3s": with 2-way split-K (Cin % 128 == 0 cases; the others fall back)
-    # "32ks": the 4x4x32 tile with 2-way split-K
-    monkeypatch.setenv("CTSI_CONV_K32_SPLITK", {"16k3": "plain", "16k3s": "1", "32ks": "512"}.get(tile, "0"))
-    if tile in ("16h", "16h3"):
-        monkeypatch.setenv("CTSI_CONV_H32W16", {"16h": "1", "16h3": "2"}[tile])    # 4x4x16 / 3x4x16 tiles
-    monkeypatch.setenv("CTSI_CONV_M512", "1" if tile in ("32k", "16k", "32k3") else "0")
+    for key, val in halo3_tile_env(tile).items():
+        monkeypatch.setenv(key, val)
     y, sums = G.run_conv(x1, x2, wt, b, want_stats=True, groups=groups)
     assert rel_l2(y, ref) < CONV_TOL, name
     rg = ref.reshape(n, groups, -1).double()
@@ -312,7 +322,16 @@ DOWN_CASES = [
 ]
 
 
-@pytest.mark.parametrize("tile", ["32k", "16k", "32k3", "16k3", "16k3s"])
+DOWN_TILES = ["32k", "16k", "32k3", "16k3", "16k3s"]
+
+
+def down_tile_env(tile):
+    """The overrides that select one tile form of the strided (3,4,4) conv on the k32 halo-tile kernel."""
+    return {"CTSI_CONV_FORCE_HALO3": "1", "CTSI_CONV_M512W16": "1" if tile.startswith("16") else "0",
+            "CTSI_CONV_K32_384": "1" if "k3" in tile else "0", "CTSI_CONV_K32_SPLITK": "1" if tile == "16k3s" else "0"}
+
+
+@pytest.mark.parametrize("tile", DOWN_TILES)
 @pytest.mark.parametrize("name,cin,cout,dims", DOWN_CASES, ids=[c[0] for c in DOWN_CASES])
 def test_downsample_conv_on_halo_tile_kernel(G, monkeypatch, name, cin, cout, dims, tile):
     """Strided Conv3d (3,4,4)/(1,2,2)/pad 1 (models/unet3d.py:204-207, models/vae.py DownsampleBlock) on the k32 halo-tile
@@ -324,10 +343,8 @@ def test_downsample_conv_on_halo_tile_kernel(G, monkeypatch, name, cin, cout, di
     b = formula_input((cout,), 4) * 0.1
     ref = F.conv3d(x, wt, b, stride=(1, 2, 2), padding=(1, 1, 1))
     groups = 8
-    monkeypatch.setenv("CTSI_CONV_FORCE_HALO3", "1")
-    monkeypatch.setenv("CTSI_CONV_M512W16", "1" if tile.startswith("16") else "0")
-    monkeypatch.setenv("CTSI_CONV_K32_384", "1" if "k3" in tile else "0")
-    monkeypatch.setenv("CTSI_CONV_K32_SPLITK", "1" if tile == "16k3s" else "0")
+    for key, val in down_tile_env(tile).items():
+        monkeypatch.setenv(key, val)
     import ctypes as C
     import importlib
     E = importlib.import_module("video-to-video-diffusion_amd.engine")
@@ -493,7 +510,16 @@ CONVT_CASES = [
 ]
 
 
-@pytest.mark.parametrize("tile", ["16", "32", "16x384", "32x384"])
+CONVT_TILES = ["16", "32", "16x384", "32x384"]
+
+
+def convt_tile_env(tile):
+    """The overrides that select one tile form of the ConvTranspose (3,4,4) on the k32 halo-tile kernel."""
+    return {"CTSI_CONV_FORCE_HALO3": "1", "CTSI_CONV_M512W16": "1" if tile.startswith("16") else "0",
+            "CTSI_CONV_K32_384": "1" if tile.endswith("384") else "0"}      # 3x8x16 / 3x4x32 = 384-voxel tiles
+
+
+@pytest.mark.parametrize("tile", CONVT_TILES)
 @pytest.mark.parametrize("name,cin,cout,dims", CONVT_CASES, ids=[c[0] for c in CONVT_CASES])
 def test_conv_transpose_halo_tile_kernel(G, monkeypatch, name, cin, cout, dims, tile):
     """ConvTranspose3d (3,4,4) / (1,2,2) / pad 1 (reference models/unet3d.py:218-221, models/vae.py decoder) on the 12-entry
@@ -505,9 +531,8 @@ def test_conv_transpose_halo_tile_kernel(G, monkeypatch, name, cin, cout, dims, 
     b = formula_input((cout,), 63) * 0.1
     ref = F.conv_transpose3d(x, wt, b, stride=(1, 2, 2), padding=(1, 1, 1))
     groups = 8
-    monkeypatch.setenv("CTSI_CONV_FORCE_HALO3", "1")
-    monkeypatch.setenv("CTSI_CONV_M512W16", "1" if tile.startswith("16") else "0")
-    monkeypatch.setenv("CTSI_CONV_K32_384", "1" if tile.endswith("384") else "0")      # 3x8x16 / 3x4x32 = 384-voxel tiles
+    for key, val in convt_tile_env(tile).items():
+        monkeypatch.setenv(key, val)
     import ctypes as C
     import importlib
     E = importlib.import_module("video-to-video-diffusion_amd.engine")

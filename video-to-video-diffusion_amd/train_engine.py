@@ -437,7 +437,7 @@ class UNetTrainProgram(TrainProgram):
         dev = self.ctx.device
         et = torch.frombuffer(bytearray(b"".join(ents)), dtype=torch.uint8).to(dev)
         bt = torch.frombuffer(bytearray(b"".join(blks)), dtype=torch.uint8).to(dev)
-        self.keep.extend([et, bt])
+        self._lin_tables = (et, bt)      # host-built tables (uploaded whole): kept alive here; `keep` lists the program's own allocations
         lib, sptr, nb = self.lib, self.ctx.sptr, len(blks)
 
         def run():
