@@ -188,7 +188,7 @@ class Program:
         self.op_meta: List[Tuple[str, float, str]] = []
         self.op_bytes: List[float] = []
         self.op_alg_bytes: List[float] = []   # convs: algorithmic HBM bytes (inputs + outputs + weights, each once)
-        self.op_audit: List[Optional[dict]] = []   # per op: what it computes from which buffers (training backward), or None
+        self.op_audit: List[Optional[dict]] = []   # per op: what it computes from which buffers (see _emit), or None
         self.pool = _Pool(ctx.device)
         self.keep: List[object] = []       # tensors / ctypes structs that must outlive the ops
         self.plans: List[C.c_void_p] = []  # conv plan handles (destroyed with the program)
@@ -219,8 +219,10 @@ class Program:
               alg_bytes: float = 0.0, audit: Optional[dict] = None):
         """`nbytes`: algorithmic HBM bytes of an HBM-bound op (what bench.py divides by the launch time for GB/s).
         `audit`: a description of what the op computes -- its kind, the Acts / tensors it reads and writes and the scalars of
-        the formula (references only; it changes nothing about the launch).  The training programs attach one to every
-        backward op so that a test can re-derive each launch's result from its own operands (tests/train_audit.py)."""
+        the formula (references only; it changes nothing about the launch).  Every op that computes something carries one,
+        so that a test can re-derive each launch's result from its own operands (tests/fwd_audit.py for the forward ops,
+        tests/train_audit.py for the training backward).  Buffers that exist only after finalize_layout (`_colsum`,
+        `_gn_sums`) are named through a callable."""
         self.ops.append(fn)
         self.op_meta.append((name, flops, kernel))
         self.op_bytes.append(float(nbytes))
@@ -654,6 +656,14 @@ class Program:
                + (2.0 * x1.n * do * ho * wo * cout if fuse_gn is not None else 0.0))
         if audit is not None:
             audit = dict(audit, out=out_act)
+        else:
+            audit = dict(kind="conv_fwd", x1=x1, x2=x2, weight=weight_fn, bias=bias, transposed=bool(transposed), k=tuple(k),
+                         s=tuple(s), p=tuple(p), cout=cout, cin_w=cin_w, act=act, out=out_act, f32_out=f32_out,
+                         f32_strides=None if f32_out is None else tuple(int(v) for v in f32_strides), stats=stats,
+                         colsum=(lambda: prog._colsum) if want_stats else None, stream_tail=mode.value == 10, fuse_gn=None)
+            if fuse_gn is not None:
+                audit["fuse_gn"] = dict(x=gh, slot=gslot, sums=lambda: prog._gn_sums, gamma=ggamma, beta=gbeta,
+                                        groups=gmod.num_groups, eps=float(gmod.eps), count=int(co.gn_count), silu=bool(gsilu))
         self._emit(run, name, fl, kernel, alg_bytes=alg, audit=audit)
         return out_act, stats
 
@@ -777,7 +787,8 @@ class Program:
                                 C.c_void_p(prog._gn_sums.data_ptr() + slot * 8), n, c, pt["cpad"], groups, pt["tps"],
                                 pt["nclass"], int(i > 0), sptr)
 
-        self._emit(run, "gn.finalize")
+        self._emit(run, "gn.finalize", audit=dict(kind="gn_finalize", colsum=lambda: prog._colsum, sums=lambda: prog._gn_sums,
+                                                  slot=slot, n=n, c=c, groups=groups, parts=parts))
         # depth-sharded programs: the slot holds this slab's sums until `sync_stats_and_halos` (emitted by the consumer:
         # gn_apply / attention / the fused residual tail) all-reduces it together with the tensor's boundary slices
         return slot
@@ -792,7 +803,8 @@ class Program:
         def run():
             lib.gn_colsum(xp, _ptr(prog._colsum), n, c, d, h, w, None, sptr)
 
-        self._emit(run, "gn.colsum", nbytes=2.0 * n * c * d * h * w)
+        self._emit(run, "gn.colsum", nbytes=2.0 * n * c * d * h * w,
+                   audit=dict(kind="gn_colsum", x=x, colsum=lambda: prog._colsum, tps=tps, tile_rows=512))
         return dict(tps=tps, cpad=x.c, nclass=1)
 
     def gn_apply(self, x: Act, slot: int, gn: nn.GroupNorm, *, silu_pre: bool, tbias=None,
@@ -827,7 +839,10 @@ class Program:
             lib.gn_apply(xp, yp, C.c_void_p(prog._gn_sums.data_ptr() + slot * 8), gp, bp, n, c, d, h, w, d_stat,
                          groups, eps, int(silu_pre), tbp, tbias_stride, stp, rp, int(silu_post), sptr)
 
-        self._emit(run, "gn.apply", nbytes=(2 + (residual is not None)) * 2.0 * n * c * d * h * w)
+        self._emit(run, "gn.apply", nbytes=(2 + (residual is not None)) * 2.0 * n * c * d * h * w,
+                   audit=dict(kind="gn_apply", x=x, out=out, sums=lambda: prog._gn_sums, slot=slot, gamma=gamma, beta=beta,
+                              groups=groups, eps=eps, d_stat=d_stat, silu_pre=bool(silu_pre), tbias=tbias, tbias_off=tbias_off,
+                              tbias_stride=tbias_stride, step_ptr=step_ptr, residual=residual, silu_post=bool(silu_post)))
         if fresh:
             self.zero_end_halos(out)
         return out
@@ -890,7 +905,9 @@ class Program:
         def run_ds():
             lib.attn_depthsum(xp, dsp, _ptr(prog._colsum), n, c, d, h, w, sptr)
 
-        self._emit(run_ds, "attn.depthsum", nbytes=2.0 * n * c * d * h * w)
+        self._emit(run_ds, "attn.depthsum", nbytes=2.0 * n * c * d * h * w,
+                   audit=dict(kind="attn_depthsum", x=x, depthsum=depthsum, colsum=lambda: prog._colsum, tps=tps,
+                              tile_pos=256 // (c // 8)))
         slot = self.gn_finalize(x, m.norm.num_groups, dict(tps=tps, cpad=c, nclass=1))
         if self.shard is not None and x.halo:
             # one sync point: GroupNorm statistics (fp64) + the depth sum (fp32) over all ranks
@@ -927,7 +944,9 @@ class Program:
 
             fl_pv = 2.0 * n * h * w * c * c
             self.flops += fl_pv
-            self._emit(run_pv, "attn.pv", fl_pv, "attn_pv_mfma")
+            self._emit(run_pv, "attn.pv", fl_pv, "attn_pv_mfma",
+                       audit=dict(kind="attn_pv", depthsum=depthsum, sums=lambda: prog._gn_sums, slot=slot, gamma=gamma,
+                                  beta=beta, w=wbuf, bias=bias_pv, out=pterm, groups=groups, eps=eps, d=d_all))
             self.pool.put(depthsum)
         else:
             xs = self.act(n, c, 1, h, w, halo=0)
@@ -937,7 +956,9 @@ class Program:
                 lib.attn_normsum(dsp, C.c_void_p(prog._gn_sums.data_ptr() + slot * 8), gp, bp, xsp, n, c, d_all, h, w,
                                  groups, eps, sptr)
 
-            self._emit(run_ns, "attn.normsum")
+            self._emit(run_ns, "attn.normsum",
+                       audit=dict(kind="attn_normsum", depthsum=depthsum, sums=lambda: prog._gn_sums, slot=slot, gamma=gamma,
+                                  beta=beta, out=xs, groups=groups, eps=eps, d=d_all))
             pterm, _ = self.conv("attn.pv", wpv, bpv, xs, None, k=(1, 1, 1), p=(0, 0, 0), cout=c)
             self.pool.put(depthsum)
             self.release(xs)
@@ -956,7 +977,8 @@ class Program:
             def run_rs():
                 lib.attn_softmax_rowsum(qkp, rsp, n, c, d, h, w, heads, sptr)
 
-            self._emit(run_rs, "attn.softmax_rowsum")
+            self._emit(run_rs, "attn.softmax_rowsum",
+                       audit=dict(kind="attn_softmax_rowsum", qk=qk, out=rowsum, heads=heads))
             self.release(qk)
         out = self.act(n, c, d, h, w, halo=x.halo)
         lo, d_ext = self.ext(x)          # x + P over own AND halo slices: P does not depend on depth
@@ -967,7 +989,8 @@ class Program:
         def run_ba():
             lib.attn_broadcast_add(xep, pp, rsp2, heads, op_, n, c, d_ext, h, w, sptr)
 
-        self._emit(run_ba, "attn.broadcast_add", nbytes=4.0 * n * c * d_ext * h * w)
+        self._emit(run_ba, "attn.broadcast_add", nbytes=4.0 * n * c * d_ext * h * w,
+                   audit=dict(kind="attn_broadcast_add", x=x, p=pterm, rowsum=rowsum, heads=heads, out=out))
         self.zero_end_halos(out)
         self.release(pterm)
         if rowsum is not None:
@@ -1293,10 +1316,16 @@ class UNetProgram(Program):
             self.cfg_partials = self.persistent((n * bps * 4,), torch.float64, zero=True)
             self.cfg_stats = self.persistent((n, 4), torch.float64, zero=True)
             pp, stp = _ptr(self.cfg_partials), _ptr(self.cfg_stats)
-            self._emit(lambda: lib.cfg_stats(ep, cs, sp, pp, n, L, d, h, w, sptr), "cfg.stats", nbytes=8.0 * numel)
-            self._emit(lambda: lib.cfg_stats_finalize(pp, stp, n, L, d, h, w, sptr), "cfg.stats_finalize")
+            self._emit(lambda: lib.cfg_stats(ep, cs, sp, pp, n, L, d, h, w, sptr), "cfg.stats", nbytes=8.0 * numel,
+                       audit=dict(kind="cfg_stats", eps=self.eps, scale=self.cfg_scale, step_ptr=self.step_ptr,
+                                  partials=self.cfg_partials, n=n, bps=bps))
+            self._emit(lambda: lib.cfg_stats_finalize(pp, stp, n, L, d, h, w, sptr), "cfg.stats_finalize",
+                       audit=dict(kind="cfg_stats_finalize", partials=self.cfg_partials, stats=self.cfg_stats, n=n, bps=bps,
+                                  count=L * d * h * w))
         stp = _ptr(self.cfg_stats)
-        self._emit(lambda: lib.cfg_combine(ep, cs, sp, stp, n, L, d, h, w, sptr), "cfg.combine", nbytes=12.0 * numel)
+        self._emit(lambda: lib.cfg_combine(ep, cs, sp, stp, n, L, d, h, w, sptr), "cfg.combine", nbytes=12.0 * numel,
+                   audit=dict(kind="cfg_combine", eps=self.eps, scale=self.cfg_scale, step_ptr=self.step_ptr,
+                              stats=self.cfg_stats, n=n))
 
     def _add_guidance_mirror(self):
         """ctsi_cfg_mirror: the z the update wrote into rows [0, n) of the network input, copied to rows [n, 2n)."""
@@ -1305,7 +1334,7 @@ class UNetProgram(Program):
         dst = self._uncond_zin()
         rows, L = self.n * self.d * self.h * self.w, self.L
         self._emit(lambda: lib.cfg_mirror(src, dst, rows, L * nbytes, c_total * nbytes, sptr), "cfg.mirror",
-                   nbytes=2.0 * rows * L * nbytes)
+                   nbytes=2.0 * rows * L * nbytes, audit=dict(kind="cfg_mirror", zin=self.xin, n=self.n, L=L))
 
     def add_sampler_step(self, kind: str, with_noise: bool):
         """Append the update of sampler `kind` (a SAMPLER_STEPS key) and the step-counter increment (done once, before
@@ -1340,10 +1369,13 @@ class UNetProgram(Program):
 
         step_bytes = (4 + 4 + 4 + zin_bytes + (4 if with_noise else 0) + (8 if entry.hist else 0)) * float(
             n * L * d * h * w)
-        self._emit(run_step, "sampler.step", nbytes=step_bytes)
+        self._emit(run_step, "sampler.step", nbytes=step_bytes,
+                   audit=dict(kind="sampler_step", sampler=kind, z=self.z, eps=self.eps, hist=self.hist,
+                              noise=self.noise if with_noise else None, zin=self.xin, coef=self.coef, step_ptr=self.step_ptr,
+                              nonfinite=self.nonfinite if entry.nonfinite else None, n=n, L=L))
         if self.guided:
             self._add_guidance_mirror()
-        self._emit(run_adv, "sampler.advance")
+        self._emit(run_adv, "sampler.advance", audit=dict(kind="sampler_advance", step_ptr=self.step_ptr))
         self.sampler_kind = (kind, with_noise)
 
 

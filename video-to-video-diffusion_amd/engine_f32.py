@@ -147,7 +147,12 @@ class _F32Ops:
         kernel = "conv_f32_mfma_128x%d%s" % (bn, "t" if transposed else ("d" if tuple(s) == (2, 2) else ""))
         alg = (4.0 * x1.n * x1.d * x1.h * x1.w * (x1.c + c2) + float(wbytes) + 4.0 * x1.n * do * ho * wo * cout
                * (2 if residual is not None else 1))
-        self._emit(run, name, fl, kernel, alg_bytes=alg)
+        self._emit(run, name, fl, kernel, alg_bytes=alg,
+                   audit=dict(kind="conv_fwd", f32=True, x1=x1, x2=x2, weight=weight_fn, bias=bias, transposed=bool(transposed),
+                              k=tuple(k), s=tuple(s), p=tuple(p), cout=cout, cin_w=None, act=act, out=out_act, f32_out=f32_out,
+                              f32_strides=None if f32_out is None else tuple(int(v) for v in f32_strides), stats=stats,
+                              colsum=(lambda: prog._colsum) if want_stats else None, stream_tail=False, fuse_gn=None,
+                              residual=residual))
         return out_act, stats
 
     def gn_colsum(self, x: Act) -> dict:
@@ -160,7 +165,8 @@ class _F32Ops:
         def run():
             lib.gn_colsum_f32(xp, _ptr(prog._colsum), n, c, d, h, w, None, sptr)
 
-        self._emit(run, "gn.colsum", nbytes=4.0 * n * c * d * h * w)
+        self._emit(run, "gn.colsum", nbytes=4.0 * n * c * d * h * w,
+                   audit=dict(kind="gn_colsum", f32=True, x=x, colsum=lambda: prog._colsum, tps=tps, tile_rows=512))
         return dict(tps=tps, cpad=x.c, nclass=1)
 
     def gn_apply(self, x: Act, slot: int, gn: nn.GroupNorm, *, silu_pre: bool, tbias=None, tbias_off: int = 0,
@@ -182,7 +188,11 @@ class _F32Ops:
             lib.gn_apply_f32(xp, yp, C.c_void_p(prog._gn_sums.data_ptr() + slot * 8), gp, bp, n, c, d, h, w, d, groups, eps,
                              int(silu_pre), tbp, tbias_stride, stp, rp, int(silu_post), sptr)
 
-        self._emit(run, "gn.apply", nbytes=(2 + (residual is not None)) * 4.0 * n * c * d * h * w)
+        self._emit(run, "gn.apply", nbytes=(2 + (residual is not None)) * 4.0 * n * c * d * h * w,
+                   audit=dict(kind="gn_apply", f32=True, x=x, out=out, sums=lambda: prog._gn_sums, slot=slot, gamma=gamma,
+                              beta=beta, groups=groups, eps=eps, d_stat=d, silu_pre=bool(silu_pre), tbias=tbias,
+                              tbias_off=tbias_off, tbias_stride=tbias_stride, step_ptr=step_ptr, residual=residual,
+                              silu_post=bool(silu_post)))
         return out
 
     def unet_resblock(self, m, x: Act, skip: Optional[Act], tbias: torch.Tensor, tbias_off: int, tbias_stride: int,
@@ -223,7 +233,9 @@ class _F32Ops:
         def run_ds():
             lib.attn_depthsum_f32(xp, dsp, _ptr(prog._colsum), n, c, d, h, w, sptr)
 
-        self._emit(run_ds, "attn.depthsum", nbytes=4.0 * n * c * d * h * w)
+        self._emit(run_ds, "attn.depthsum", nbytes=4.0 * n * c * d * h * w,
+                   audit=dict(kind="attn_depthsum", f32=True, x=x, depthsum=depthsum, colsum=lambda: prog._colsum, tps=tps,
+                              tile_pos=64))
         slot = self.gn_finalize(x, m.norm.num_groups, dict(tps=tps, cpad=c, nclass=1))
         gamma = self.dev_f32(lambda: m.norm.weight)
         beta = self.dev_f32(lambda: m.norm.bias)
@@ -236,7 +248,9 @@ class _F32Ops:
             lib.attn_normsum_f32(dsp, C.c_void_p(prog._gn_sums.data_ptr() + slot * 8), gp, bp, xsp, n, c, d, h, w, groups,
                                  eps, sptr)
 
-        self._emit(run_ns, "attn.normsum")
+        self._emit(run_ns, "attn.normsum",
+                   audit=dict(kind="attn_normsum", f32=True, depthsum=depthsum, sums=lambda: prog._gn_sums, slot=slot,
+                              gamma=gamma, beta=beta, out=xs, groups=groups, eps=eps, d=d))
 
         # fold proj_out . V-projection in fp64, round once:  P = (Wp Wv) xs + (D Wp bv + bp)
         def wpv():
@@ -256,7 +270,8 @@ class _F32Ops:
         def run_ba():
             lib.attn_broadcast_add_f32(xp, pp, op_, n, c, d, h, w, sptr)
 
-        self._emit(run_ba, "attn.broadcast_add", nbytes=12.0 * n * c * d * h * w)
+        self._emit(run_ba, "attn.broadcast_add", nbytes=12.0 * n * c * d * h * w,
+                   audit=dict(kind="attn_broadcast_add", f32=True, x=x, p=pterm, rowsum=None, heads=m.num_heads, out=out))
         self.release(pterm)
         return out
 

@@ -363,7 +363,11 @@ class UNetTrainProgram(TrainProgram):
                                      _ptr(prog.w2), _ptr(prog.b2), _ptr(prog.w_all), _ptr(prog.b_all), prog.total_out,
                                      _ptr(prog.te_scratch), _ptr(prog.tbias), sptr)
 
-        self._emit(run_inputs, "train.inputs")
+        self._emit(run_inputs, "train.inputs", audit=dict(
+            kind="train.inputs", z0=self.z0, noise=self.noise, cond=self.cond, t_rows=self.t_rows,
+            sqrt_ac=lambda: prog.sqrt_ac, sqrt_1mac=lambda: prog.sqrt_1mac, xin=self.xin, L=L, dim=self.dim,
+            time_dim=self.time_dim, w1=self.w1, b1=self.b1, w2=self.w2, b2=self.b2, w_all=self.w_all, b_all=self.b_all,
+            te_scratch=self.te_scratch, tbias=self.tbias))
         self.zero_gn_op()
 
         # ---- forward network (same wiring as engine.UNetProgram) -------------------------------------------------
@@ -399,7 +403,9 @@ class UNetTrainProgram(TrainProgram):
             lib.mse_loss_fwd(_ptr(prog.eps), _ptr(prog.noise), _ptr(prog.mask) if prog.use_mask else None,
                              _ptr(prog.norm), n, L, d, h, w, _ptr(prog.loss_ws), _ptr(prog.loss_out), sptr)
 
-        self._emit(run_loss, "loss.fwd")
+        self._emit(run_loss, "loss.fwd", audit=dict(
+            kind="loss.fwd", pred=self.eps, noise=self.noise, mask=lambda: prog.mask if prog.use_mask else None,
+            norm=self.norm, out=self.loss_out))
         self.n_fwd = len(self.ops)
         self.generation = 0   # bumped by every run_forward (see there)
 
@@ -490,7 +496,8 @@ class UNetTrainProgram(TrainProgram):
         def run_ds():
             lib.attn_depthsum(xp, dsp, _ptr(prog._colsum), n, c, d, h, w, sptr)
 
-        self._emit(run_ds, "attn.depthsum")
+        self._emit(run_ds, "attn.depthsum", audit=dict(kind="attn_depthsum", x=x, depthsum=depthsum,
+                                                       colsum=lambda: prog._colsum, tps=tps, tile_pos=256 // (c // 8)))
         slot = self.gn_finalize(x, m.norm.num_groups, dict(tps=tps, cpad=c, nclass=1))
         gamma = self.dev_f32(lambda: m.norm.weight)
         beta = self.dev_f32(lambda: m.norm.bias)
@@ -502,7 +509,8 @@ class UNetTrainProgram(TrainProgram):
             lib.attn_normsum(dsp, C.c_void_p(prog._gn_sums.data_ptr() + slot * 8), gp, bp, xsp, n, c, d, h, w, groups,
                              eps, sptr)
 
-        self._emit(run_ns, "attn.normsum")
+        self._emit(run_ns, "attn.normsum", audit=dict(kind="attn_normsum", depthsum=depthsum, sums=lambda: prog._gn_sums,
+                                                      slot=slot, gamma=gamma, beta=beta, out=xs, groups=groups, eps=eps, d=d))
         wv = lambda: m.qkv.weight[2 * c:3 * c]
         def bv():                      # the V bias is added once per depth slice of the sum
             return float(d) * m.qkv.bias[2 * c:3 * c]
@@ -517,7 +525,8 @@ class UNetTrainProgram(TrainProgram):
         def run_ba():
             lib.attn_broadcast_add(xp, pp, None, m.num_heads, op_, n, c, d, h, w, sptr)
 
-        self._emit(run_ba, "attn.broadcast_add")
+        self._emit(run_ba, "attn.broadcast_add", audit=dict(kind="attn_broadcast_add", x=x, p=pterm, rowsum=None,
+                                                            heads=m.num_heads, out=out))
 
         def bwd():
             gy = out.grad

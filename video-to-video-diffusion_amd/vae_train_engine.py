@@ -109,7 +109,7 @@ class VAETrainProgram(TrainProgram):
         def run_seam():
             lib.ncdhw_f32_to_ndhwc_bf16(_ptr(prog.z), zp, n, L, d, hl, wl, L, 0, sptr)
 
-        self._emit(run_seam, "seam.z_to_bf16")
+        self._emit(run_seam, "seam.z_to_bf16", audit=dict(kind="seam.z_to_bf16", z=self.z, out=self.zin))
 
         def seam_bwd():       # runs after post_quant's backward wrote zin.grad = W_p^T du = sf * (its share of dL/dz)
             zg = prog.zin.grad
