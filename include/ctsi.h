@@ -138,6 +138,10 @@ double ctsi_conv_plan_flops(const ctsi_conv_plan* plan);
 /* which kernel variant the plan launches: MFMA tile (bm x bn) and staging mode
  * (0: general gather, 1: small-cin tap-packed K, 2: buffer-addressed whole-chunk gather)      */
 int ctsi_conv_plan_config(const ctsi_conv_plan* plan, int* bm, int* bn, int* mode);
+/* what ctsi_conv_plan_config cannot tell apart (host-only; tests and tools/conv_plan_sweep.py): out[0..2] the tile TD, TH, TW
+ * (linear-row gather plans: TD = depth slices a tile can touch), out[3] the split-K factor (ksplit of a k32 plan, gsplit of a
+ * gather plan, else 0), out[4] flag bits 1 linear, 2 fast, 4 head2, 8 ds; out[5..7] are reserved (0).                   */
+int ctsi_conv_plan_form(const ctsi_conv_plan* plan, int out[8]);
 /* which packed-weight image ctsi_conv_plan_pack_weights writes for this plan, as far as the descriptor's channel / kernel
  * fields, ctsi_conv_plan_cout_pad and the weight cin (ctsi_conv_plan_set_weight_cin) do not already say: bits 0-3 the
  * kernel family (CTSI_PACK_*); k32 plans add their form << 4 (0 Conv3d 3x3x3, 1 ConvTranspose3d, 2 strided Conv3d), the

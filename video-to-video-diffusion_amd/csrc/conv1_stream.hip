@@ -194,6 +194,12 @@ __global__ void conv1_stream_pack_kernel(const float* __restrict__ w, bf16_t* __
 
 // n-tile width (in 16-cout tiles) for a layer, 0 = not served: K in whole 128-channel chunks from each source, the n-tile's
 // weight image within 128 KB of LDS
+// CTSI_CONV1_STREAM (tuning / test aid, read per plan): 0 keeps every plan on the gather kernel, 2 also takes the deep-K forms
+extern "C" int ctsi_conv1_stream_switch() {
+    const char* e = getenv("CTSI_CONV1_STREAM");
+    return e ? atoi(e) : -1;
+}
+
 extern "C" int ctsi_conv1_stream_nt(int c1, int c2, int cout) {
     if (c1 <= 0 || c1 % 128 != 0 || c2 % 128 != 0) return 0;
     const int nch = (c1 + c2) / 128;
@@ -204,8 +210,7 @@ extern "C" int ctsi_conv1_stream_nt(int c1, int c2, int cout) {
         // deep K: the weight image only fits LDS in 64-cout n-tiles, every voxel row is then fetched cout / 64 times through the
         // L2 -> CU path and the pass is no faster than the gather kernel's (768 -> 256 @48x64^2: 160 vs 153 us, 1024 -> 512
         // @48x32^2: 103 vs 91 us; profiles/r04_tail_bench.log).  Parity-tested, selected only on request (CTSI_CONV1_STREAM=2)
-        const char* e = getenv("CTSI_CONV1_STREAM");
-        if (!(e && atoi(e) == 2)) return 0;
+        if (ctsi_conv1_stream_switch() != 2) return 0;
         nt = 4;
     } else return 0;
     const char* fnt = getenv("CTSI_CONV1_STREAM_NT");              // tuning / test aid (read per plan): force a narrower n-tile

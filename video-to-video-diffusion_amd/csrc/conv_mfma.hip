@@ -20,12 +20,11 @@
 // (sum, sum of squares) for the GroupNorm that follows every large conv on this path.
 #include <type_traits>
 #include "conv3_halo_common.h"
+#include "conv_plan.h"
 #include <string.h>
 #include <stdlib.h>
 #include <math.h>
 
-#define CTSI_MAX_TAPS 48
-#define CTSI_BK 64
 
 __device__ __attribute__((aligned(256))) uint32_t g_ctsi_zero_page[64];  // 256 B of zeros
 
@@ -720,690 +719,17 @@ __global__ void conv_pack_weights_kernel(const PackParams q) {
     }
 }
 
-// ---- host side --------------------------------------------------------------------------------------
-struct ctsi_conv_plan {
-    ctsi_conv_desc d;
-    int Cin, CinW;
-    int Do, Ho, Wo;
-    int Dr, Hr, Wr, sH, sW, uH, uW;
-    int nclass, T;
-    int small, lcpt, kc_per_tap, ksteps, Ktot;
-    int BM, BN, CoutPad, ntiles_n;
-    int lTH, lTW, TD, TH, TW, tilesD, tilesH, tilesW, tps, mtiles;
-    int linear;   // gather kernel: tiles are runs of BM consecutive row-grid voxels
-    int tapk[CTSI_MAX_TAPS];
-    int tapdelta[CTSI_MAX_TAPS];
-    int8_t od[CTSI_MAX_TAPS], oh[CTSI_MAX_TAPS], ow[CTSI_MAX_TAPS];
-    int NA, NB, NC;
-    int ad[4][4], bh[4][4], cw[4][4];
-    int8_t pH[4], pW[4];
-    int tap_margin[4], ad_min[4];
-    int fast, dshift;
-    int h32_w16;    // halo3 == 2 only: 1 = 4x4x16 tile (two W-lines of 16 per A tile), 2 = 3x4x16 tile, instead of 4x2x32
-    int m512_w16;   // halo3 == 7 only: tile of the k32 kernel: 0 = 4x4x32, 2 = 4x8x16, 3 = 3x4x32, 5 = 3x8x16, 6 = 4x4x24, 7 = 8x4x12 (384 voxels)
-    int gsplit;     // gather kernel (halo3 == 0): S-way split-K for launches of a few dozen blocks with a deep K loop (needs a workspace)
-    int ds;         // halo3 == 7: the strided (3,4,4)/(1,2,2) Downsample form of the k32 kernel (conv3_halo_k32.hip, DS)
-    int head2;      // halo3 == 6: conv3_head2_kernel (taps as the GEMM's N dimension) serves the launches that ask for no column sums
-    int ksplit;     // halo3 == 7, tile 5: 2 = two blocks per (tile, n-tile), each half of the input-channel chunks (needs a workspace)
-    int stem;       // 1: conv3_stem_kernel (conv3_stem.hip: 3x3x3 conv of a one-channel volume stored with 8 channels); chosen by
-                    // ctsi_conv_plan_set_weight_cin(plan, 1)
-    int stream1;    // > 0: conv1_stream_kernel (conv1_stream.hip: 1x1x1 conv + fused GroupNorm tail as a streaming pass), value = 16-cout
-                    // tiles per n-tile; chosen by ctsi_conv_plan_set_stream_tail, never by ctsi_conv_plan_create
-    int halo3;  // 3x3x3 halo-tile kernels: 2 = conv3_halo32_kernel (conv3_halo.hip: 4x2x32 / 4x4x16 / 3x4x16 tiles), 6 = few-cout
-                // heads (conv3_head.hip), 7 = conv3_halo_k32_kernel (conv3_halo_k32.hip: 512- / 384-voxel tiles, ConvTranspose).
-                // 1 (16x16x32 form of the 4x4x16 tile), 3 / 4 (persistent and half-size blocks) and 5 (32x32x16 form of the
-                // 512-voxel tile) were measured slower and live under csrc/experiments/, outside libctsi.so.
-    double flops;
-};
-
-static int ilog2(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-
-// pick the power-of-two (TD,TH,TW) with TD*TH*TW == bm that covers the row grid with the fewest
-// padded rows; ties go to the most cube-like tile (smallest halo for the L2).
-static void choose_tile(int bm, int Dr, int Hr, int Wr, int* TD, int* TH, int* TW) {
-    long long best = -1;
-    int bsurf = 0;
-    const int lb = ilog2(bm);
-    for (int lw = 0; lw <= lb; ++lw)
-        for (int lh = 0; lh + lw <= lb; ++lh) {
-            const int tw = 1 << lw, th = 1 << lh, td = bm >> (lw + lh);
-            const long long tiles = (long long)ceil_div(Dr, td) * ceil_div(Hr, th) * ceil_div(Wr, tw);
-            const int surf = (td + 2) * (th + 2) * (tw + 2);
-            if (best < 0 || tiles < best || (tiles == best && surf < bsurf)) {
-                best = tiles;
-                bsurf = surf;
-                *TD = td;
-                *TH = th;
-                *TW = tw;
-            }
-        }
-}
-
-extern "C" int ctsi_conv_plan_create(ctsi_conv_plan** out, const ctsi_conv_desc* desc) {
-    CTSI_CHECK_ARG(out && desc, "ctsi_conv_plan_create: null argument");
-    const ctsi_conv_desc& d = *desc;
-    CTSI_CHECK_ARG(d.n > 0 && d.c1 > 0 && d.c2 >= 0 && d.cout > 0 && d.di > 0 && d.hi > 0 && d.wi > 0,
-                   "ctsi_conv_plan_create: bad sizes n=%d c1=%d c2=%d cout=%d in=%dx%dx%d", d.n, d.c1,
-                   d.c2, d.cout, d.di, d.hi, d.wi);
-    CTSI_CHECK_ARG(d.c1 % 8 == 0 && d.c2 % 8 == 0,
-                   "ctsi_conv_plan_create: source channel counts must be multiples of 8 (got %d, %d); "
-                   "pad the tensor at the layout boundary", d.c1, d.c2);
-    CTSI_CHECK_ARG(d.kd >= 1 && d.kh >= 1 && d.kw >= 1 && d.sh >= 1 && d.sw >= 1,
-                   "ctsi_conv_plan_create: bad kernel/stride");
-    ctsi_conv_plan* p = (ctsi_conv_plan*)calloc(1, sizeof(ctsi_conv_plan));
-    if (!p) {
-        ctsi_set_error("ctsi_conv_plan_create: out of host memory");
-        return CTSI_ERR_INVALID;
-    }
-    p->d = d;
-    p->dshift = d.halo_d ? 1 : 0;
-    const int di_own = d.di - 2 * p->dshift;   // depth of the slab the rows cover
-    if (d.halo_d && (d.kd != 3 || d.pd != 1 || di_own < 1)) {
-        free(p);
-        ctsi_set_error("ctsi_conv_plan_create: halo_d needs kd=3, pd=1 and di >= 3");
-        return CTSI_ERR_UNSUPPORTED;
-    }
-    p->Cin = d.c1 + d.c2;
-    p->CinW = p->Cin;
-    const int KK = d.kd * d.kh * d.kw;
-    if (!d.transposed) {
-        p->Do = di_own + 2 * d.pd - d.kd + 1;
-        p->Ho = (d.hi + 2 * d.ph - d.kh) / d.sh + 1;
-        p->Wo = (d.wi + 2 * d.pw - d.kw) / d.sw + 1;
-        if (KK > CTSI_MAX_TAPS || p->Do <= 0 || p->Ho <= 0 || p->Wo <= 0) {
-            free(p);
-            ctsi_set_error("ctsi_conv_plan_create: unsupported Conv3d geometry k=(%d,%d,%d)", d.kd, d.kh, d.kw);
-            return CTSI_ERR_UNSUPPORTED;
-        }
-        p->nclass = 1;
-        p->T = KK;
-        p->Dr = p->Do; p->Hr = p->Ho; p->Wr = p->Wo;
-        p->sH = d.sh; p->sW = d.sw; p->uH = 1; p->uW = 1;
-        p->pH[0] = 0; p->pW[0] = 0;
-        p->NA = d.kd; p->NB = d.kh; p->NC = d.kw;
-        if (d.kd > 3 || d.kh > 4 || d.kw > 4) {
-            free(p);
-            ctsi_set_error("ctsi_conv_plan_create: unsupported Conv3d geometry k=(%d,%d,%d)", d.kd, d.kh, d.kw);
-            return CTSI_ERR_UNSUPPORTED;
-        }
-        for (int a = 0; a < d.kd; ++a) p->ad[0][a] = a - d.pd;
-        for (int b = 0; b < d.kh; ++b) p->bh[0][b] = b - d.ph;
-        for (int c = 0; c < d.kw; ++c) p->cw[0][c] = c - d.pw;
-        int t = 0;
-        for (int a = 0; a < d.kd; ++a)
-            for (int b = 0; b < d.kh; ++b)
-                for (int c = 0; c < d.kw; ++c, ++t) {
-                    p->od[t] = (int8_t)(a - d.pd);
-                    p->oh[t] = (int8_t)(b - d.ph);
-                    p->ow[t] = (int8_t)(c - d.pw);
-                    p->tapk[t] = (a * d.kh + b) * d.kw + c;
-                }
-    } else {
-        // ConvTranspose3d, depth stride 1: o_d = i_d - pd + k_d; o_h = i_h*sh - ph + k_h.
-        // One parity class per (o_h % sh, o_w % sw); each class is a stride-1 gather conv on the
-        // input grid with kd * (kh/sh) * (kw/sw) taps.
-        const bool ok = d.sh == 2 && d.sw == 2 && d.kh == 4 && d.kw == 4 && d.ph == 1 && d.pw == 1 &&
-                        d.kd == 3 && d.pd == 1;
-        if (!ok) {
-            free(p);
-            ctsi_set_error("ctsi_conv_plan_create: ConvTranspose3d supports k=(3,4,4) s=(1,2,2) p=1 only");
-            return CTSI_ERR_UNSUPPORTED;
-        }
-        p->Do = di_own; p->Ho = d.hi * 2; p->Wo = d.wi * 2;
-        p->nclass = 4;
-        p->T = 12;
-        p->Dr = di_own; p->Hr = d.hi; p->Wr = d.wi;
-        p->sH = 1; p->sW = 1; p->uH = 2; p->uW = 2;
-        for (int cls = 0; cls < 4; ++cls) {
-            const int py = cls >> 1, px = cls & 1;
-            p->pH[cls] = (int8_t)py;
-            p->pW[cls] = (int8_t)px;
-            // output o = 2m+py receives (k, i): py=0 -> (1,m),(3,m-1); py=1 -> (2,m),(0,m+1)
-            const int ky[2] = {py == 0 ? 1 : 2, py == 0 ? 3 : 0};
-            const int oy[2] = {0, py == 0 ? -1 : 1};
-            const int kx[2] = {px == 0 ? 1 : 2, px == 0 ? 3 : 0};
-            const int ox[2] = {0, px == 0 ? -1 : 1};
-            p->NA = 3; p->NB = 2; p->NC = 2;
-            for (int a = 0; a < 3; ++a) p->ad[cls][a] = 1 - a;
-            for (int b = 0; b < 2; ++b) { p->bh[cls][b] = oy[b]; p->cw[cls][b] = ox[b]; }
-            int t = cls * 12;
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 2; ++b)
-                    for (int c = 0; c < 2; ++c, ++t) {
-                        p->od[t] = (int8_t)(1 - a);  // i_d = o_d + pd - k_d
-                        p->oh[t] = (int8_t)oy[b];
-                        p->ow[t] = (int8_t)ox[c];
-                        p->tapk[t] = (a * 4 + ky[b]) * 4 + kx[c];
-                    }
-        }
-    }
-    for (int t = 0; t < p->nclass * p->T; ++t)
-        p->tapdelta[t] = (p->od[t] * d.hi + p->oh[t]) * d.wi + p->ow[t];
-    for (int c = 0; c < p->nclass; ++c) {
-        int mn = 0, dmin = 0;
-        for (int t = 0; t < p->T; ++t) {
-            if (p->tapdelta[c * p->T + t] < mn) mn = p->tapdelta[c * p->T + t];
-            if (p->od[c * p->T + t] < dmin) dmin = p->od[c * p->T + t];
-        }
-        p->tap_margin[c] = -mn;
-        p->ad_min[c] = dmin;
-    }
-
-    // K walk
-    if (p->Cin <= 32 && (p->Cin & (p->Cin - 1)) == 0) {
-        p->small = 1;
-        p->lcpt = ilog2(p->Cin / 8);
-        const int chunks = p->T << p->lcpt;
-        p->ksteps = ceil_div(chunks, 8);
-        p->kc_per_tap = 0;
-    } else {
-        p->small = 0;
-        p->kc_per_tap = ceil_div(p->Cin, 64);
-        p->ksteps = p->T * p->kc_per_tap;
-    }
-    p->Ktot = p->ksteps * CTSI_BK;
-    // tile selection: the bigger the tile the fewer L2->LDS bytes per flop (128x128: 64 flop/B,
-    // 256x128: 85, 256x256: 128), but the grid must still fill 256 CUs about twice over.
-    {
-        const long long rows = (long long)d.n * p->Dr * p->Hr * p->Wr * p->nclass;
-        const char* force = getenv("CTSI_CONV_TILE");  // "128x128" | "256x128" | "256x256" (tuning aid)
-        p->BM = 128;
-        p->BN = d.cout <= 32 ? 32 : 128;
-        if (d.cout > 32) {
-            const long long wg_256x256 = (rows / 256) * ceil_div(d.cout, 256);
-            const long long wg_256x128 = (rows / 256) * ceil_div(d.cout, 128);
-            if (d.cout >= 256 && d.cout % 256 == 0 && wg_256x256 >= 640) {
-                p->BM = 256; p->BN = 256;
-            } else if (wg_256x128 >= 640) {
-                p->BM = 256; p->BN = 128;
-            }
-            if (force) {
-                if (!strcmp(force, "128x128")) { p->BM = 128; p->BN = 128; }
-                if (!strcmp(force, "256x128")) { p->BM = 256; p->BN = 128; }
-                if (!strcmp(force, "256x256") && d.cout % 256 == 0) { p->BM = 256; p->BN = 256; }
-            }
-        }
-    }
-    {   // 3x3x3 / stride 1 / pad 1 with whole 32-channel chunks per source: LDS halo-tile kernel, provided its
-        // fixed 4x4x16 tile does not waste more than ~30 % of the rows and the per-tile halo fits 2^31 bytes
-        const bool k3 = !d.transposed && d.kd == 3 && d.kh == 3 && d.kw == 3 && d.sh == 1 && d.sw == 1 &&
-                        d.pd == 1 && d.ph == 1 && d.pw == 1;
-        const long long rows = (long long)p->Dr * p->Hr * p->Wr;
-        const long long padded = (long long)ceil_div(p->Dr, 4) * ceil_div(p->Hr, 4) * ceil_div(p->Wr, 16) * 256;
-        const int cmax = d.c1 > d.c2 ? d.c1 : d.c2;
-        const double extent = 8.0 * d.hi * d.wi * cmax * 2.0;
-        // whole 32-channel chunks per source for the 4x4x16 / 4x2x32 kernels; the 512-voxel kernel walks 16-channel chunks,
-        // so sources of 16 channels (the U-Net stem: [z | cond] = 2 x latent_dim = 16) can use it too
-        const bool c32 = !p->small && d.c1 % 32 == 0 && d.c2 % 32 == 0;
-        const bool c16 = d.c1 % 16 == 0 && d.c2 % 16 == 0 && !getenv("CTSI_CONV_NO_C16");
-        p->halo3 = k3 && (c32 || c16) && d.cout >= 64 && d.cout % 8 == 0 &&
-                   p->CinW == p->Cin && (rows * 10 >= padded * 7 || getenv("CTSI_CONV_FORCE_HALO3")) && extent < 2.0e9 &&
-                   !getenv("CTSI_CONV_NO_HALO3");
-        if (p->halo3) {
-            p->BM = 256;
-            p->BN = 128;
-            // Which of the three halo-tile kernels: score = useful fraction of the tile rows x fill of the 256 CUs (blocks /
-            // whole rounds) x the kernel's measured relative efficiency on full grids (16-wide 0.85, 4x2x32 1.0, 4x4x32 / 512
-            // voxels 1.1).  Reproduces every interleaved A/B measurement of profiles/r01_notes.md: 48x128^2 and 48x64^2 -> 512-voxel
-            // tile, 48x32^2 x 512 couts -> 4x2x32 (384 big blocks would idle a quarter of the CUs), 48x16^2 and 48x48^2 ->
-            // 16-wide, a lone 48x24^2 level (144 blocks either way) -> 512-voxel tile.
-            auto score = [&](int td, int th, int tw, double eff) {
-                const long long t = (long long)d.n * ceil_div(p->Dr, td) * ceil_div(p->Hr, th) * ceil_div(p->Wr, tw);
-                const long long b = t * ceil_div(d.cout, 128);
-                const double useful = (double)rows * d.n / ((double)t * td * th * tw);
-                return useful * (double)b / (double)(((b + 255) / 256) * 256) * eff;
-            };
-            const double s16 = score(4, 4, 16, 0.85), s32 = score(4, 2, 32, 1.0), s512 = score(4, 4, 32, 1.1);
-            const char* w16 = getenv("CTSI_CONV_M512W16");    // "0" | "1": the 4x8x16 form of the 512-voxel kernel
-            const double s512w = (w16 && !strcmp(w16, "0")) ? 0.0 : score(4, 8, 16, 1.0);
-            int pick = s16 >= s32 && s16 >= s512 ? 1 : (s32 >= s512 ? 2 : 5);
-            bool use_w16 = s512w > s16 && s512w > s32 && s512w > s512;
-            if (w16 && !strcmp(w16, "1")) use_w16 = true;
-            const char* hv = getenv("CTSI_CONV_HALO_TILE");   // "16" | "32" (tuning aids)
-            const char* m5 = getenv("CTSI_CONV_M512");        // "0" | "1"
-            if (hv && !strcmp(hv, "16")) pick = 1;
-            if (hv && !strcmp(hv, "32") && pick == 1) pick = s32 >= s512 ? 2 : 5;
-            if (m5 && !strcmp(m5, "0") && pick == 5) pick = 2;
-            if (m5 && !strcmp(m5, "1") && pick != 1) pick = 5;
-            if (!c32 && pick != 5) {   // 16-channel sources: only the 512-voxel kernel applies
-                pick = 5;
-                use_w16 = s512w > s512;
-            }
-            if (use_w16 && (!c32 || (!(hv && !strcmp(hv, "16")) && !(m5 && !strcmp(m5, "0"))))) {
-                pick = 5;
-                p->m512_w16 = 2;
-            }
-            {   // 16-wide levels: tile 4x4x16 (256 voxels; an A tile of 32 rows = two W-lines of 16) or 3x4x16 (192 voxels; 3x1
-                // MFMA tiles per wave: 0.95 of the 2x2 form's efficiency) of conv3_halo32_kernel -- whichever fills the 256
-                // CUs better (48x16x16 x 512 couts: 192 vs 256 blocks)
-                const char* hw = getenv("CTSI_CONV_H32W16");   // "1" | "2" (tuning / test aid)
-                if (pick == 1) {
-                    pick = 2;
-                    p->h32_w16 = score(3, 4, 16, 0.95) > score(4, 4, 16, 1.0) ? 2 : 1;
-                    if (hw && !strcmp(hw, "1")) p->h32_w16 = 1;
-                    if (hw && !strcmp(hw, "2")) p->h32_w16 = 2;
-                    if (p->h32_w16 == 2) p->BM = 192;
-                }
-            }
-            p->halo3 = pick;
-            if (pick == 5) {
-                p->BM = 512;
-                // the 512-voxel tile runs on v_mfma_f32_16x16x32_bf16 over tap pairs (conv3_halo_k32.hip: +10-12 % on real data
-                // over the 32x32x16 form conv3_halo32m_kernel, which -- with its normalise-on-load experiment -- now lives
-                // under csrc/experiments/, outside libctsi.so; profiles/r02_notes.md)
-                p->halo3 = 7;
-            }
-            {   // 384-voxel tile (3x4x32, 48 voxels per wave) of the k32 kernel where 512-voxel tiles fill the CUs badly: the
-                // 48x32x32 x 512-cout layers are 384 blocks of 512 x 128 (1.5 rounds of the 256 CUs) or 512 blocks of 384 x 128
-                // (2 rounds).  Relative efficiencies on full grids: 4x2x32 / 32x32x16 MFMAs 1.0, k32 512-voxel 1.15, k32 384-voxel 1.1
-                const char* t384 = getenv("CTSI_CONV_K32_384");   // "0" | "1" (tuning / test aid)
-                const double cur = p->halo3 == 7 ? (p->m512_w16 == 2 ? score(4, 8, 16, 1.15) : score(4, 4, 32, 1.15))
-                                   : p->halo3 == 2 ? (p->h32_w16 == 2 ? score(3, 4, 16, 0.95) : p->h32_w16 == 1 ? score(4, 4, 16, 1.0) : s32)
-                                                   : s16;
-                bool use384 = score(3, 4, 32, 1.1) > cur;
-                if (t384 && !strcmp(t384, "0")) use384 = false;
-                if (t384 && !strcmp(t384, "1")) use384 = true;
-                if (use384) {
-                    p->halo3 = 7;
-                    p->BM = 384;
-                    p->h32_w16 = 0;
-                    p->m512_w16 = 3;
-                }
-                // 16-wide levels with deep K and few voxels (48x16x16, 512 -> 512: 192 / 256 / 128 blocks with 512- / 192- / 384-
-                // voxel tiles): 3x8x16 = 384 voxels with 2-way split-K = 256 blocks of half the channel chunks each (one round,
-                // half the weight bytes per block).  Measured 0.141 ms per half-K block against 0.18 ms for the 192-voxel tile.
-                const char* sk = getenv("CTSI_CONV_K32_SPLITK");   // "0" | "1" | "plain" (tuning / test aid)
-                auto score_sk = [&]() {
-                    const long long t = (long long)d.n * ceil_div(p->Dr, 3) * ceil_div(p->Hr, 8) * ceil_div(p->Wr, 16);
-                    const long long b = 2 * t * ceil_div(d.cout, 128);
-                    const double useful = (double)rows * d.n / ((double)t * 384);
-                    return useful * (double)b / (double)(((b + 255) / 256) * 256) * 1.1;
-                };
-                // (round 4: not below 256 input channels -- a half-K block of a 128-channel layer walks 4 chunks, and its prologue,
-                //  hand-off and epilogue cost more than the better fill returns: config-3 128 -> 128 @ 4 x 48^3 0.408 ms as
-                //  2304 half-K blocks of 3x8x16, 0.331 ms as 864 blocks of 4x8x16; 256 -> 256 equal either way; profiles/r04_notes.md.
-                //  CTSI_CONV_K32_SK384_MIN: that threshold, for A/B timing)
-                const char* skc = getenv("CTSI_CONV_K32_SK384_MIN");
-                const bool sk_ok = p->Cin % 128 == 0 && d.c1 % 16 == 0 && d.c2 % 16 == 0;
-                const bool sk_deep = p->Cin >= (skc ? atoi(skc) : 256);
-                const double cur2 = use384 ? score(3, 4, 32, 1.1) : cur;
-                bool use_sk = sk_ok && sk_deep && score_sk() > cur2;
-                if (sk && !strcmp(sk, "0")) use_sk = false;
-                if (sk && !strcmp(sk, "1") && sk_ok) use_sk = true;
-                // 2-way split-K on the 4x4x32 tile: pays where the 512-voxel grid fills the CUs badly AND K is deep enough to
-                // amortise the parked accumulators (256 KB per tile): 1024 -> 512 @48x32x32 1325 -> 1400 TFLOP/s against the
-                // 384-voxel tile, 512 -> 512 +0.5 %, 256 -> 512 -7 % (profiles/r02_notes.md).  Round 4: with the direct-store
-                // epilogue (which the split-K form takes and the plain 384-voxel tile does not) 512 -> 512 is +5.6 % (1260 ->
-                // 1330 TFLOP/s, profiles/r04_notes.md), 256 -> 512 still -3 %: the threshold is 512 input channels now
-                auto fill = [&](long long b) { return (double)b / (double)(((b + 255) / 256) * 256); };
-                const long long b512 = (long long)d.n * ceil_div(p->Dr, 4) * ceil_div(p->Hr, 4) * ceil_div(p->Wr, 32) * ceil_div(d.cout, 128);
-                const char* skm = getenv("CTSI_CONV_K32_SK512_MIN");   // tuning aid: least input channels for this form (A/B timing)
-                const bool sk512 = sk_ok && p->Cin >= (skm ? atoi(skm) : 512) && p->Wr % 32 == 0 && p->Hr % 4 == 0 && p->Dr % 4 == 0 &&
-                                   fill(b512) < 0.8 && fill(2 * b512) >= 0.95 && !(sk && !strcmp(sk, "0"));
-                if ((sk && !strcmp(sk, "512") && sk_ok) || (sk512 && !(sk && (!strcmp(sk, "1") || !strcmp(sk, "plain"))))) {
-                    p->halo3 = 7;
-                    p->BM = 512;
-                    p->h32_w16 = 0;
-                    p->m512_w16 = 0;
-                    p->ksplit = 2;
-                } else
-                if (use_sk || (sk && !strcmp(sk, "plain"))) {
-                    p->halo3 = 7;
-                    p->BM = 384;
-                    p->h32_w16 = 0;
-                    p->m512_w16 = 5;
-                    p->ksplit = use_sk ? 2 : 1;
-                }
-            }
-        }
-        if (k3 && (c32 || c16) && d.cout >= 64 && d.cout % 8 == 0 && p->CinW == p->Cin && extent < 2.0e9 && !getenv("CTSI_CONV_NO_HALO3")) {
-            // 24- and 12-wide planes (the 48 x 24^2 / 48 x 12^2 levels of 192^2 patches: config 1, config 3, stitching windows): 16- and
-            // 32-wide tiles cover them at 75 %.  The k32 kernel's 384-voxel tiles 4x4x24 / 8x4x12 (A tiles that straddle W-lines,
-            // conv3_halo_k32.hip) cover them whole.  Same score as above (useful rows x fill of the 256 CUs x relative efficiency);
-            // taken only when clearly ahead: 25 stitching windows at once 113 -> 101 ms per U-Net evaluation (L1 + L2 convs 57.9 ->
-            // 46.2 ms), while at B = 4 (config 3) the fewer, larger tiles fill the CUs worse (L2: 288 blocks = 1.1 rounds) and
-            // the 16-wide tiles stay (measured equal / slower: profiles/r04_notes.md).  CTSI_CONV_K32_NARROW = 0 / 1: never /
-            // wherever the plane divides.
-            auto sc = [&](int td, int th, int tw, double eff, int kmul) {
-                const long long t = (long long)d.n * ceil_div(p->Dr, td) * ceil_div(p->Hr, th) * ceil_div(p->Wr, tw);
-                const long long b = t * ceil_div(d.cout, 128) * kmul;
-                const double useful = (double)rows * d.n / ((double)t * td * th * tw);
-                return useful * (double)b / (double)(((b + 255) / 256) * 256) * eff;
-            };
-            double cur;
-            if (p->halo3 == 7) {
-                const int km = p->ksplit == 2 ? 2 : 1;
-                cur = p->m512_w16 == 5 ? sc(3, 8, 16, 1.1, km) : p->m512_w16 == 3 ? sc(3, 4, 32, 1.1, 1)
-                      : p->m512_w16 == 2 ? sc(4, 8, 16, 1.15, 1) : sc(4, 4, 32, 1.15, km);
-            } else if (p->halo3 == 2) {
-                cur = p->h32_w16 == 2 ? sc(3, 4, 16, 0.95, 1) : p->h32_w16 == 1 ? sc(4, 4, 16, 1.0, 1) : sc(4, 2, 32, 1.0, 1);
-            } else {
-                cur = 0.6;      // the gather kernel (halo tiles wasted > 30 % of their rows)
-            }
-            const char* nw = getenv("CTSI_CONV_K32_NARROW");
-            const bool off = nw && !strcmp(nw, "0"), force = nw && !strcmp(nw, "1");
-            struct { int td, th, tw, code; } cand[2] = {{4, 4, 24, 6}, {8, 4, 12, 7}};
-            // 2-way split-K on these tiles where it fills the CUs better (B = 4, 48 x 24^2 x 256 couts: 576 blocks = 2.25 rounds ->
-            // 1152 = 4.5; 48 x 12^2 x 512 couts: 288 -> 576); CTSI_CONV_K32_NARROW_SK = 0 / 1: never / wherever K allows
-            const char* nsk = getenv("CTSI_CONV_K32_NARROW_SK");
-            const char* skc = getenv("CTSI_CONV_K32_SK384_MIN");
-            const bool nsk_ok = p->Cin % 128 == 0 && d.c1 % 16 == 0 && d.c2 % 16 == 0 && !(nsk && !strcmp(nsk, "0"));
-            const bool nsk_deep = p->Cin >= (skc ? atoi(skc) : 256);
-            for (auto& c : cand) {
-                if (off || p->halo3 == 6 || p->Wr % c.tw != 0 || p->Wr % 16 == 0) continue;
-                const double s1 = sc(c.td, c.th, c.tw, 1.07, 1), s2 = nsk_ok ? sc(c.td, c.th, c.tw, 1.07, 2) : 0.0;
-                const bool sk2 = nsk_ok && ((nsk && !strcmp(nsk, "1")) || (nsk_deep && s2 > 1.1 * s1));
-                if (force || (sk2 ? s2 : s1) > 1.05 * cur) {
-                    p->halo3 = 7;
-                    p->BM = 384;
-                    p->BN = 128;
-                    p->h32_w16 = 0;
-                    p->m512_w16 = c.code;
-                    p->ksplit = sk2 ? 2 : 0;
-                    break;
-                }
-            }
-        }
-        // ConvTranspose3d (3,4,4) / (1,2,2) on the k32 kernel: each parity class is a 12-tap convolution on the input grid with
-        // the 3x3x3 conv's halo tile (conv3_halo_k32.hip, TR = true); CTSI_CONV_K32T=0 keeps the gather kernel (A/B timing)
-        if (d.transposed && d.c2 == 0 && d.c1 % 16 == 0 && d.cout >= 64 && d.cout % 8 == 0 && p->CinW == p->Cin &&
-            extent < 2.0e9) {
-            // tile: useful fraction of the tile rows x fill of the 256 CUs (4 classes x n-tiles blocks per input tile) x relative
-            // efficiency (384-voxel tiles 0.96)
-            // (4x4x24 / 8x4x12: the straddling 384-voxel tiles for 24- / 12-wide input planes, only where the plane divides:
-            //  25 stitching windows at once, Upsample + Downsample layers 12.4 -> 11.1 ms; CTSI_CONV_K32_NARROW=0: never)
-            const bool narrow_off = getenv("CTSI_CONV_K32_NARROW") && !strcmp(getenv("CTSI_CONV_K32_NARROW"), "0");
-            struct { int td, th, tw, code; double eff; } cand[6] = {{4, 4, 32, 0, 1.0}, {4, 8, 16, 2, 1.0}, {3, 4, 32, 3, 0.96},
-                                                                    {3, 8, 16, 5, 0.96}, {4, 4, 24, 6, 0.96}, {8, 4, 12, 7, 0.96}};
-            double best = -1.0, best_useful = 0.0;
-            int best_code = 0;
-            for (auto& c : cand) {
-                if (c.code >= 6 && (p->Wr % c.tw != 0 || p->Wr % 16 == 0 || narrow_off)) continue;
-                const long long t = (long long)d.n * ceil_div(p->Dr, c.td) * ceil_div(p->Hr, c.th) * ceil_div(p->Wr, c.tw);
-                const long long b = t * 4 * ceil_div(d.cout, 128);
-                const double useful = (double)rows * d.n / ((double)t * c.td * c.th * c.tw);
-                const double sc = useful * (double)b / (double)(((b + 255) / 256) * 256) * c.eff;
-                if (sc > best) {
-                    best = sc;
-                    best_code = c.code;
-                    best_useful = useful;
-                }
-            }
-            const char* kt = getenv("CTSI_CONV_K32T");
-            const bool force = getenv("CTSI_CONV_FORCE_HALO3") != nullptr;
-            if ((best_useful >= 0.7 || force) && !(kt && !strcmp(kt, "0")) && !getenv("CTSI_CONV_NO_HALO3")) {
-                p->halo3 = 7;
-                p->BN = 128;
-                p->m512_w16 = best_code;
-                const char* w16 = getenv("CTSI_CONV_M512W16");    // "0" | "1" (tuning / test aid: 4x4x32 / 4x8x16)
-                if (w16 && !strcmp(w16, "1")) p->m512_w16 = 2;
-                if (w16 && !strcmp(w16, "0")) p->m512_w16 = 0;
-                const char* t384 = getenv("CTSI_CONV_K32_384");   // "1": a 384-voxel tile of that width (test aid)
-                if (t384 && !strcmp(t384, "1")) p->m512_w16 = (p->m512_w16 == 2 || p->m512_w16 == 5) ? 5 : 3;
-                if (t384 && !strcmp(t384, "0")) p->m512_w16 = (p->m512_w16 == 2 || p->m512_w16 == 5) ? 2 : 0;
-                p->BM = (p->m512_w16 == 3 || p->m512_w16 >= 5) ? 384 : 512;
-            }
-        }
-        // Strided Conv3d (3,4,4) / (1,2,2) / pad 1 (Downsample3D, the VAE encoder's DownsampleBlock) on the k32 kernel: the four
-        // input-parity sub-grids are 3x2x2-tap stride-1 convolutions on the OUTPUT grid's halo tile (conv3_halo_k32.hip, DS =
-        // true).  CTSI_CONV_K32D=0 keeps the gather kernel (A/B timing).  Tile by the same score as the ConvTranspose form;
-        // levels whose grid stays below one round of the 256 CUs with deep K take the 2-way split-K form of the 3x8x16 tile.
-        if (!d.transposed && d.kd == 3 && d.kh == 4 && d.kw == 4 && d.sh == 2 && d.sw == 2 && d.pd == 1 && d.ph == 1 && d.pw == 1 &&
-            d.c2 == 0 && d.c1 % 16 == 0 && d.cout >= 64 && d.cout % 8 == 0 && p->CinW == p->Cin && d.hi % 2 == 0 && d.wi % 2 == 0 &&
-            extent < 2.0e9) {
-            struct { int td, th, tw, code; double eff; } cand[6] = {{4, 4, 32, 0, 1.0}, {4, 8, 16, 2, 1.0}, {3, 4, 32, 3, 0.96},
-                                                                    {3, 8, 16, 5, 0.96}, {4, 4, 24, 6, 0.96}, {8, 4, 12, 7, 0.96}};
-            const bool narrow_off = getenv("CTSI_CONV_K32_NARROW") && !strcmp(getenv("CTSI_CONV_K32_NARROW"), "0");
-            double best = -1.0, best_useful = 0.0;
-            int best_code = 0;
-            long long best_blocks = 0;
-            for (auto& c : cand) {
-                if (c.code >= 6 && (p->Wr % c.tw != 0 || p->Wr % 16 == 0 || narrow_off)) continue;
-                const long long t = (long long)d.n * ceil_div(p->Dr, c.td) * ceil_div(p->Hr, c.th) * ceil_div(p->Wr, c.tw);
-                const long long b = t * ceil_div(d.cout, 128);
-                const double useful = (double)rows * d.n / ((double)t * c.td * c.th * c.tw);
-                const double sc = useful * (double)b / (double)(((b + 255) / 256) * 256) * c.eff;
-                if (useful < 0.7 && !getenv("CTSI_CONV_FORCE_HALO3")) continue;   // (a 32-wide tile on a 16-wide plane)
-                if (sc > best) {
-                    best = sc;
-                    best_code = c.code;
-                    best_useful = useful;
-                    best_blocks = b;
-                }
-            }
-            const char* kd_ = getenv("CTSI_CONV_K32D");       // "0": gather kernel (tuning / test aid)
-            const bool force = getenv("CTSI_CONV_FORCE_HALO3") != nullptr;
-            if ((best_useful >= 0.7 || force) && !(kd_ && !strcmp(kd_, "0")) && !getenv("CTSI_CONV_NO_HALO3")) {
-                p->halo3 = 7;
-                p->ds = 1;
-                p->BN = 128;
-                p->m512_w16 = best_code;
-                const char* w16 = getenv("CTSI_CONV_M512W16");    // "0" | "1" (tuning / test aid: 4x4x32 / 4x8x16)
-                if (w16 && !strcmp(w16, "1")) p->m512_w16 = 2;
-                if (w16 && !strcmp(w16, "0")) p->m512_w16 = 0;
-                const char* t384 = getenv("CTSI_CONV_K32_384");   // "1": a 384-voxel tile of that width (test aid)
-                if (t384 && !strcmp(t384, "1")) p->m512_w16 = (p->m512_w16 == 2 || p->m512_w16 == 5) ? 5 : 3;
-                if (t384 && !strcmp(t384, "0")) p->m512_w16 = (p->m512_w16 == 2 || p->m512_w16 == 5) ? 2 : 0;
-                // split-K: 3x8x16 tiles, two blocks per (tile, n-tile) -- when even the best tile leaves the grid at <= half a
-                // round of the CUs (48x16x16 x 512 couts: 128 blocks) and K is deep (48 taps x Cin)
-                const char* sk = getenv("CTSI_CONV_K32_SPLITK");  // "0" | "1" (tuning / test aid)
-                const long long t5 = (long long)d.n * ceil_div(p->Dr, 3) * ceil_div(p->Hr, 8) * ceil_div(p->Wr, 16) * ceil_div(d.cout, 128);
-                bool use_sk = p->Cin % 32 == 0 && p->Cin >= 256 && best_blocks <= 160 && 2 * t5 <= 512;
-                if (sk && !strcmp(sk, "0")) use_sk = false;
-                if (sk && !strcmp(sk, "1") && p->Cin % 32 == 0) use_sk = true;
-                if (use_sk) {
-                    p->m512_w16 = 5;
-                    p->ksplit = 2;
-                }
-                p->BM = (p->m512_w16 == 3 || p->m512_w16 >= 5) ? 384 : 512;
-            }
-        }
-        // few output channels (network heads: 128 -> 8, 128 -> 1): halo tile 4x2x16 x 16 couts, see conv3_head.hip
-        const long long padded_h = (long long)ceil_div(p->Dr, 4) * ceil_div(p->Hr, 2) * ceil_div(p->Wr, 16) * 128;
-        if (!p->halo3 && k3 && !p->small && d.c2 == 0 && d.c1 % 32 == 0 && d.cout <= 16 && (rows * 10 >= padded_h * 7 || getenv("CTSI_CONV_FORCE_HALO3")) &&
-            extent < 2.0e9 && !getenv("CTSI_CONV_NO_HEAD3")) {
-            p->halo3 = 6;
-            p->BM = 128;
-            p->BN = 16;
-            p->head2 = ctsi_conv3_head2_supported(p->Cin, d.cout) && p->CinW == p->Cin && !getenv("CTSI_CONV_NO_HEAD2");
-        }
-    }
-    p->CoutPad = ceil_div(d.cout, p->BN) * p->BN;
-    p->ntiles_n = p->CoutPad / p->BN;
-    if (p->halo3 == 7 && p->m512_w16 == 6) {
-        p->TD = 4; p->TH = 4; p->TW = 24;
-    } else if (p->halo3 == 7 && p->m512_w16 == 7) {
-        p->TD = 8; p->TH = 4; p->TW = 12;
-    } else if (p->halo3 == 7 && p->m512_w16 == 5) {
-        p->TD = 3; p->TH = 8; p->TW = 16;
-    } else if (p->halo3 == 7 && p->m512_w16 == 3) {
-        p->TD = 3; p->TH = 4; p->TW = 32;
-    } else if (p->halo3 == 7 && p->m512_w16 == 2) {
-        p->TD = 4; p->TH = 8; p->TW = 16;
-    } else if (p->halo3 == 7) {
-        p->TD = 4; p->TH = 4; p->TW = 32;
-    } else if (p->halo3 == 2) {
-        p->TD = p->h32_w16 == 2 ? 3 : 4; p->TH = p->h32_w16 ? 4 : 2; p->TW = p->h32_w16 ? 16 : 32;
-    } else if (p->halo3 == 6) {
-        p->TD = 4; p->TH = 2; p->TW = 16;
-    } else {
-        choose_tile(p->BM, p->Dr, p->Hr, p->Wr, &p->TD, &p->TH, &p->TW);
-    }
-    p->lTH = ilog2(p->TH);
-    p->lTW = ilog2(p->TW);
-    p->tilesD = ceil_div(p->Dr, p->TD);
-    p->tilesH = ceil_div(p->Hr, p->TH);
-    p->tilesW = ceil_div(p->Wr, p->TW);
-    p->tps = p->tilesD * p->tilesH * p->tilesW;
-    if (!p->halo3) {
-        // gather kernel on small planes: a power-of-two box tile over e.g. a 6 x 6 plane is 44 % padding rows; runs of
-        // BM consecutive voxels have none (only the last tile of a sample is ragged)
-        const long long rows = (long long)p->Dr * p->Hr * p->Wr;
-        const long long boxed = (long long)p->tps * p->BM;
-        const char* lin = getenv("CTSI_CONV_LINEAR");   // "0" | "1" (tuning aid)
-        if ((boxed * 100 > rows * 115 && !(lin && !strcmp(lin, "0"))) || (lin && !strcmp(lin, "1"))) {
-            p->linear = 1;
-            p->tps = (int)((rows + p->BM - 1) / p->BM);
-            p->TD = (int)(p->BM / ((long long)p->Hr * p->Wr)) + 2;   // depth slices one tile can touch (fast-path extent)
-        }
-    }
-    p->mtiles = d.n * p->tps;
-    {   // buffer-addressed fast path: whole 64-channel chunks per source and a tile halo that fits 2^31 bytes
-        const int cmax = d.c1 > d.c2 ? d.c1 : d.c2;
-        const double extent = ((double)(p->TD + 4) * d.hi * d.wi + 2.0 * d.wi + 8) * cmax * 2.0 * (p->sH > 1 ? 1 : 1);
-        p->fast = !p->small && d.c1 % 64 == 0 && d.c2 % 64 == 0 && extent < 2.0e9 && !getenv("CTSI_CONV_NO_FAST");
-    }
-    p->gsplit = 0;
-    if (!p->halo3 && !p->small && p->BM == 128 && p->BN == 128) {
-        // S-way split-K on the gather kernel: a layer that is a few dozen blocks (the 6 x 6 level of ONE 192^2 patch: 14 m-tiles
-        // x 4 n-tiles = 56 blocks on 256 CUs) with hundreds of sequential K-steps is bound by its K-step latency; S blocks
-        // per tile walk 1 / S of the steps each (csrc/conv_mfma.hip, hand-off by ticket).  CTSI_CONV_GSPLIT = 0 | 2..8 overrides.
-        const long long blocks = (long long)p->nclass * p->mtiles * p->ntiles_n;
-        int S = 0;
-        if (blocks * 2 <= 256 && p->ksteps >= 32) {
-            S = (int)(256 / blocks);
-            if (S > 4) S = 4;
-            while (S > 1 && p->ksteps / S < 16) --S;
-        } else if (blocks <= 256 && p->ksteps >= 64) {
-            S = 2;     // 129-256 blocks: the grid doubles past the ring mode's one-block-per-CU limit, so the two half-K blocks of
-        }              // a tile share a CU in the 2-stage mode: 560 -> 700 TFLOP/s on the 6 x 6 level of config 3 (B = 4)
-        const char* gs = getenv("CTSI_CONV_GSPLIT");
-        if (gs) S = atoi(gs) >= 2 && atoi(gs) <= 8 && p->ksteps >= atoi(gs) ? atoi(gs) : 0;
-        p->gsplit = S >= 2 ? S : 0;
-    }
-    if (!d.transposed)
-        p->flops = 2.0 * d.n * (double)p->Do * p->Ho * p->Wo * p->Cin * d.cout * KK;
-    else
-        p->flops = 2.0 * d.n * (double)di_own * d.hi * d.wi * p->Cin * d.cout * KK;
-    *out = p;
-    return CTSI_OK;
-}
-
-extern "C" void ctsi_conv_plan_destroy(ctsi_conv_plan* plan) { free(plan); }
-
-// few-cout heads (halo3 == 6): the packed buffer holds conv3_head_kernel's image, padded to 256 B, then conv3_head2_kernel's
-static size_t head1_bytes(const ctsi_conv_plan* p) {
-    return ((size_t)p->Cin * 27 * (p->d.cout <= 8 ? 8 : 16) * 2 + 1024 + 255) / 256 * 256;
-}
-
-extern "C" int ctsi_conv_plan_out_dims(const ctsi_conv_plan* p, int* d, int* h, int* w) {
-    CTSI_CHECK_ARG(p, "ctsi_conv_plan_out_dims: null plan");
-    if (d) *d = p->Do;
-    if (h) *h = p->Ho;
-    if (w) *w = p->Wo;
-    return CTSI_OK;
-}
-extern "C" size_t ctsi_conv_plan_weight_bytes(const ctsi_conv_plan* p) {
-    if (!p) return 0;
-    if (p->stem) return ctsi_conv3_stem_weight_bytes(p->CoutPad);
-    if (p->stream1) return (size_t)p->d.cout * p->Cin * 2;
-    if (p->halo3 == 6)   // head kernels: conv3_head's image (8 weight rows when cout <= 8; + 1 KB: its last DMA piece is read whole),
-        return head1_bytes(p) + (ctsi_conv3_head2_supported(p->Cin, p->d.cout) ? ctsi_conv3_head2_weight_bytes(p->d.cout) : 0);   // then conv3_head2's
-    if (p->halo3 == 7) return ctsi_conv3_halo_k32_weight_bytes(p->Cin, p->CoutPad, p->BN, p->ds ? 2 : p->d.transposed);   // entries padded to whole steps
-    if (p->halo3) return (size_t)p->Cin * 27 * p->CoutPad * 2;   // [chunk][27][cout_pad][32 | 16 ch] bf16
-    return (size_t)p->nclass * p->CoutPad * p->Ktot * 2;
-}
-extern "C" int ctsi_conv_plan_tiles(const ctsi_conv_plan* p) { return p ? p->nclass * p->mtiles : 0; }
-extern "C" int ctsi_conv_plan_tiles_per_sample(const ctsi_conv_plan* p) { return p ? p->tps : 0; }
-extern "C" int ctsi_conv_plan_cout_pad(const ctsi_conv_plan* p) { return p ? p->CoutPad : 0; }
-extern "C" double ctsi_conv_plan_flops(const ctsi_conv_plan* p) { return p ? p->flops : 0.0; }
-extern "C" size_t ctsi_conv_plan_workspace_bytes(const ctsi_conv_plan* p) {
-    // split-K plans: tickets / flags + fp32 partial accumulators (ctsi_conv_out.workspace; zero the first 8 * tiles bytes once)
-    if (p && !p->halo3 && p->gsplit >= 2) {   // gather kernel: [tile] tickets (padded to 256 B) + [tile][split][128 x 128] fp32
-        const size_t tiles = (size_t)p->nclass * p->mtiles * p->ntiles_n;
-        return (tiles * 4 + 255) / 256 * 256 + tiles * p->gsplit * (size_t)(128 * 128) * sizeof(float);
-    }
-    if (!p || p->ksplit != 2) return 0;
-    return ctsi_conv3_halo_k32_splitk_bytes(p->mtiles * p->ntiles_n);
-}
-extern "C" int ctsi_conv_plan_config(const ctsi_conv_plan* p, int* bm, int* bn, int* mode) {
-    CTSI_CHECK_ARG(p, "ctsi_conv_plan_config: null plan");
-    if (bm) *bm = p->BM;
-    if (bn) *bn = p->BN;
-    if (mode) *mode = p->stem ? 11 : p->stream1 ? 10 : (p->halo3 ? 2 + p->halo3 : (p->small ? 1 : (p->fast ? 2 : 0)));
-    if (p->stream1) {
-        if (bm) *bm = 16;
-        if (bn) *bn = p->stream1 * 16;
-    }
-    return CTSI_OK;
-}
-
-// The packed-image layout ctsi_conv_plan_pack_weights writes, beyond the descriptor's channel / kernel fields, the cout
-// padding and the weight's cin (see ctsi.h): the kernel family, and for the k32 kernel its form and whether the image is
-// cout-permuted for the direct-store epilogue.  Mirrors the branches of ctsi_conv_plan_pack_weights below.
-extern "C" int ctsi_conv_plan_pack_layout(const ctsi_conv_plan* p) {
-    if (!p) return 0;
-    if (p->stem) return CTSI_PACK_STEM;
-    if (p->stream1) return CTSI_PACK_STREAM_TAIL | (p->stream1 << 8);
-    if (p->halo3 == 7) {
-        const int form = p->ds ? 2 : p->d.transposed;
-        const int direct = ctsi_conv3_halo_k32_direct(p->m512_w16, p->ksplit, p->ds);
-        return CTSI_PACK_K32 | (form << 4) | (direct << 6) | ((p->BN / 16) << 8);
-    }
-    if (p->halo3 == 6) return CTSI_PACK_HEAD | (ctsi_conv3_head2_supported(p->Cin, p->d.cout) ? 1 << 4 : 0);
-    if (p->halo3) return CTSI_PACK_HALO;
-    return p->small ? CTSI_PACK_GATHER_SMALL : CTSI_PACK_GATHER;
-}
-
-// A 1x1x1 stride-1 conv that will run with the fused GroupNorm tail (ctsi_conv_out.gn_x) or as a plain bf16 conv + bias may
-// take the streaming kernel of conv1_stream.hip (another packed-weight layout: call this BEFORE ctsi_conv_plan_weight_bytes /
-// _pack_weights).  on = 1 selects it where the layer qualifies (whole 128-channel chunks per source, cout in whole n-tiles)
-// and is a no-op otherwise -- ctsi_conv_plan_config reports mode 10 when it is active; on = 0 returns to the gather kernel.
-// CTSI_CONV1_STREAM=0 (tuning / test aid) keeps every plan on the gather kernel.
-extern "C" int ctsi_conv_plan_set_stream_tail(ctsi_conv_plan* p, int on) {
-    CTSI_CHECK_ARG(p, "ctsi_conv_plan_set_stream_tail: null plan");
-    p->stream1 = 0;
-    const char* e = getenv("CTSI_CONV1_STREAM");
-    if (!on || (e && atoi(e) == 0)) return CTSI_OK;
-    const ctsi_conv_desc& d = p->d;
-    if (d.transposed || d.kd != 1 || d.kh != 1 || d.kw != 1 || d.sh != 1 || d.sw != 1 || d.pd || d.ph || d.pw || p->dshift)
-        return CTSI_OK;
-    p->stream1 = ctsi_conv1_stream_nt(d.c1, d.c2, d.cout);
-    return CTSI_OK;
-}
-
-// The weight tensor may carry fewer input channels than the (padded) activation tensor: the
-// VAE encoder's first conv sees a 1-channel volume stored as 8 channels (7 zero).
-extern "C" int ctsi_conv_plan_set_weight_cin(ctsi_conv_plan* p, int cin_w) {
-    CTSI_CHECK_ARG(p && cin_w > 0 && cin_w <= p->Cin, "ctsi_conv_plan_set_weight_cin: bad cin %d", cin_w);
-    p->CinW = cin_w;
-    // a 3x3x3 stride-1 conv of a ONE-channel volume (the VAE encoder's first layer: the CT volume is stored with 8 channels,
-    // 7 of them padding) with >= 64 couts: the 27 taps become the K of one MFMA (conv3_stem.hip); CTSI_CONV_NO_STEM keeps the
-    // gather kernel's small-Cin form (A/B timing, tests)
-    const ctsi_conv_desc& d = p->d;
-    if (cin_w == 1 && !d.transposed && d.kd == 3 && d.kh == 3 && d.kw == 3 && d.sh == 1 && d.sw == 1 && d.pd == 1 && d.ph == 1 &&
-        d.pw == 1 && d.c2 == 0 && d.c1 == 8 && d.cout >= 64 && d.cout % 8 == 0 && !p->dshift && !getenv("CTSI_CONV_NO_STEM")) {
-        p->stem = 1;
-        p->halo3 = 0;
-        p->gsplit = 0;
-        p->linear = 0;
-        p->BM = 512;
-        p->BN = 128;
-        ctsi_conv3_stem_tile(&p->TD, &p->TH, &p->TW);
-        p->tilesD = ceil_div(p->Dr, p->TD);
-        p->tilesH = ceil_div(p->Hr, p->TH);
-        p->tilesW = ceil_div(p->Wr, p->TW);
-        p->tps = p->tilesD * p->tilesH * p->tilesW;
-        p->mtiles = d.n * p->tps;
-        p->CoutPad = ceil_div(d.cout, 128) * 128;
-        p->ntiles_n = p->CoutPad / 128;
-    }
-    return CTSI_OK;
-}
-
+// ---- host side: packing and launches (the plan itself: conv_plan.hip) ----------------------------------------
 extern "C" int ctsi_conv_plan_pack_weights(const ctsi_conv_plan* p, const float* w, void* packed,
                                            void* stream) {
     CTSI_CHECK_ARG(p && w && packed, "ctsi_conv_plan_pack_weights: null argument");
     if (p->stem) return ctsi_conv3_stem_pack(w, packed, p->d.cout, p->CoutPad, p->CinW, stream);
     if (p->stream1) return ctsi_conv1_stream_pack(w, packed, p->d.cout, p->Cin, p->CinW, p->stream1, stream);
-    if (p->halo3 == 7)
-        return ctsi_conv3_halo_k32_pack(w, packed, p->d.cout, p->CoutPad, p->Cin, p->CinW, p->BN, p->ds ? 2 : p->d.transposed,
-                                        ctsi_conv3_halo_k32_direct(p->m512_w16, p->ksplit, p->ds), stream);
-    if (p->halo3 == 6) {
+    const ConvFamily family = conv_family(p);
+    if (family == CONV_K32)
+        return ctsi_conv3_halo_k32_pack(w, packed, p->d.cout, p->CoutPad, p->Cin, p->CinW, p->BN, conv_k32_image(p),
+                                        conv_k32_direct(p), stream);
+    if (family == CONV_HEAD) {
         hipMemsetAsync((char*)packed + head1_bytes(p) - 1280, 0, 1280, (hipStream_t)stream);
         if (ctsi_conv3_head2_supported(p->Cin, p->d.cout)) {
             const int rc = ctsi_conv3_head2_pack(w, (char*)packed + head1_bytes(p), p->d.cout, p->Cin, p->CinW, stream);
@@ -1411,7 +737,7 @@ extern "C" int ctsi_conv_plan_pack_weights(const ctsi_conv_plan* p, const float*
         }
         return ctsi_conv3_halo_pack(w, packed, p->d.cout, p->d.cout <= 8 ? 8 : 16, p->Cin, p->CinW, stream);
     }
-    if (p->halo3) return ctsi_conv3_halo_pack(w, packed, p->d.cout, p->CoutPad, p->Cin, p->CinW, stream);
+    if (family == CONV_HALO32) return ctsi_conv3_halo_pack(w, packed, p->d.cout, p->CoutPad, p->Cin, p->CinW, stream);
     PackParams q;
     memset(&q, 0, sizeof(q));
     q.w = w;
@@ -1484,6 +810,7 @@ extern "C" int ctsi_conv_fwd(const ctsi_conv_plan* p, const void* x1, const void
                        "ctsi_conv_fwd: bf16 output needs cout, cout_stride, c_off multiples of 8 "
                        "(cout=%d stride=%d off=%d)", p->d.cout, o->cout_stride, o->c_off);
     }
+    const ConvFamily family = conv_family(p);
     if (p->stem && o->mode == 0 && o->act == 0 && o->gn_x == nullptr) {
         StemParams q;
         memset(&q, 0, sizeof(q));
@@ -1529,13 +856,13 @@ extern "C" int ctsi_conv_fwd(const ctsi_conv_plan* p, const void* x1, const void
         return ctsi_conv1_stream_launch(&q, p->d.n, p->stream1, stream);
     }
     if (o->gn_x != nullptr) {
-        CTSI_CHECK_ARG(!p->halo3 && o->mode == 0 && o->act == 0 && o->colsum == nullptr && p->nclass == 1,
+        CTSI_CHECK_ARG(!p->form && o->mode == 0 && o->act == 0 && o->colsum == nullptr && p->nclass == 1,
                        "ctsi_conv_fwd: the fused GroupNorm tail needs a gather-kernel plan, bf16 output, no act / colsum");
         CTSI_CHECK_ARG(o->gn_sums && o->gn_gamma && o->gn_beta && o->gn_groups > 0 && p->d.cout % o->gn_groups == 0 &&
                            o->gn_count > 0,
                        "ctsi_conv_fwd: bad fused GroupNorm arguments (groups=%d, cout=%d)", o->gn_groups, p->d.cout);
     }
-    if (p->halo3 && (p->halo3 == 6 || (o->mode == 0 && o->act == 0))) {
+    if (p->form && (family == CONV_HEAD || (o->mode == 0 && o->act == 0))) {
         Conv3HaloParams h;
         memset(&h, 0, sizeof(h));
         h.x1 = (const bf16_t*)x1;
@@ -1550,7 +877,7 @@ extern "C" int ctsi_conv_fwd(const ctsi_conv_plan* p, const void* x1, const void
         h.dshift = p->dshift;
         h.tilesD = p->tilesD; h.tilesH = p->tilesH; h.tilesW = p->tilesW; h.tps = p->tps; h.mtiles = p->mtiles;
         h.ntiles_n = p->ntiles_n;
-        h.nchunks = p->Cin / (p->halo3 == 7 ? 16 : 32) * (p->ds ? 4 : 1);   // (Downsample form: 4 virtual chunks per 16 channels)
+        h.nchunks = p->Cin / (family == CONV_K32 ? 16 : 32) * (p->ds ? 4 : 1);   // (Downsample form: 4 virtual chunks per 16 channels)
         h.ds = p->ds;
         h.Cout = p->d.cout; h.CoutPad = p->CoutPad;
         h.cout_stride = o->cout_stride; h.c_off = o->c_off;
@@ -1584,7 +911,7 @@ extern "C" int ctsi_conv_fwd(const ctsi_conv_plan* p, const void* x1, const void
             const char* eb = getenv("CTSI_CONV_EPI_BARRIER");   // "1": A/B timing of the barrier the direct epilogue drops (read per launch)
             h.dbg_epi_barrier = eb ? atoi(eb) : 0;
         }
-        if (p->halo3 == 6) {
+        if (family == CONV_HEAD) {
             // second form (taps as the GEMM's N dimension, input read once straight into the MFMA layout: conv3_head2.hip) for the
             // layers it covers; conv3_head_kernel keeps the others and the GroupNorm column sums.  CTSI_CONV_NO_HEAD2: A/B timing
             if (p->head2 && o->colsum == nullptr)
@@ -1593,17 +920,17 @@ extern "C" int ctsi_conv_fwd(const ctsi_conv_plan* p, const void* x1, const void
             return ctsi_conv3_head_launch(&h, p->d.cout <= 8 ? 8 : 16, o->mode, o->act, o->sn, o->sc, o->sd, o->sh, o->sw, stream);
         }
         h.tr = p->d.transposed;
-        if (p->halo3 == 7 && p->ksplit == 2) {
+        if (family == CONV_K32 && p->ksplit == 2) {
             CTSI_CHECK_ARG(o->workspace, "ctsi_conv_fwd: this plan needs ctsi_conv_out.workspace (ctsi_conv_plan_workspace_bytes)");
             const int tiles = p->mtiles * p->ntiles_n;
             h.ksplit = 2;
             h.sk_sync = (int*)o->workspace;
             h.sk_ws = (float*)((char*)o->workspace + ((size_t)tiles * 8 + 255) / 256 * 256);
         }
-        if (p->halo3 == 7) return ctsi_conv3_halo_k32_launch(&h, p->m512_w16, p->BN, stream);
-        return ctsi_conv3_halo_launch(&h, p->h32_w16 == 2 ? 4 : (p->h32_w16 ? 3 : 1), stream);
+        if (family == CONV_K32) return ctsi_conv3_halo_k32_launch(&h, p->form->code, p->BN, stream);
+        return ctsi_conv3_halo_launch(&h, p->form->code, stream);
     }
-    CTSI_CHECK_ARG(!p->halo3, "ctsi_conv_fwd: the 3x3x3 halo-tile plan supports bf16 NDHWC output without activation");
+    CTSI_CHECK_ARG(!p->form, "ctsi_conv_fwd: the 3x3x3 halo-tile plan supports bf16 NDHWC output without activation");
     ConvKParams k;
     memset(&k, 0, sizeof(k));
     k.x1 = (const bf16_t*)x1;

@@ -207,6 +207,7 @@ struct Conv1StreamParams {
     int tiles;                // 16-voxel tiles per sample
     int P;                    // blocks per (sample, n-tile)
 };
+extern "C" int ctsi_conv1_stream_switch();   // CTSI_CONV1_STREAM, -1: unset
 extern "C" int ctsi_conv1_stream_nt(int c1, int c2, int cout);
 extern "C" int ctsi_conv1_stream_pack(const float* w, void* packed, int cout, int cin, int cin_w, int nt, void* stream);
 extern "C" int ctsi_conv1_stream_launch(Conv1StreamParams* q, int n, int nt, void* stream);
