@@ -561,6 +561,24 @@ int ctsi_cfg_stats(const float* eps, const float* scale, const int* step_ptr, do
 int ctsi_cfg_stats_finalize(const double* partials, double* stats, int n, int c, int d, int h, int w, void* stream);
 int ctsi_cfg_mirror(const void* src, void* dst, long long rows, int row_bytes, int stride_bytes, void* stream);
 
+/* v-prediction (csrc/prediction.hip): the network predicts v = sqrt(abar) eps - sqrt(1 - abar) z_0.
+ * ctsi_pred_to_eps: the model output becomes eps in place, fp32, elementwise over n rows of per_sample contiguous floats
+ *   (any layout: the NDHWC step buffers and the NCDHW single-step tensors alike):
+ *     out[b, i] <- a out[b, i] + b0 z[b % z_rows, i] + b1 hist[b % z_rows, i]
+ *   {a, b0, b1, 0} = rows[(*step_ptr * rows_per_step + b % rows_per_step) * 4 ..], a device table (*step_ptr = 0 when
+ *   step_ptr is NULL), so a captured graph serves every step.  z is loaded only by rows with b0 != 0, hist only by rows
+ *   with b1 != 0; hist may be NULL (the caller then builds no row with b1 != 0).  z_rows <= n: a guided batch of 2n rows
+ *   reads the n rows of z twice.  One product and one fma per term; 16-byte accesses when per_sample % 4 == 0 and every
+ *   pointer is 16-byte aligned.
+ * ctsi_q_sample_v: ctsi_q_sample (the same bf16 NDHWC z_t slice, the same bits) that also writes the training target
+ *   v_target = sqrt_ac[t_b] noise - sqrt_1mac[t_b] z0 (fp32 NCDHW) in the same pass.
+ * Null pointers / non-positive sizes / rows_per_step or z_rows outside [1, n] return CTSI_ERR_INVALID before any launch.
+ * Capture-safe: no allocation, no synchronisation. */
+int ctsi_pred_to_eps(float* out, const float* z, const float* hist, const float* rows, const int* step_ptr,
+                     int rows_per_step, int n, int z_rows, long long per_sample, void* stream);
+int ctsi_q_sample_v(const float* z0, const float* noise, const float* sqrt_ac, const float* sqrt_1mac, const int* t,
+                    void* dst, float* v_target, int n, int c, int d, int h, int w, int c_total, int c_off, void* stream);
+
 /* hipGraph helpers (one captured graph per denoising step) -------------------------------- */
 typedef struct ctsi_graph ctsi_graph;
 int ctsi_graph_begin_capture(void* stream);

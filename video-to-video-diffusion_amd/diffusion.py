@@ -19,8 +19,14 @@ from .lib import CtsiError
 
 
 class GaussianDiffusion(nn.Module):
-    def __init__(self, noise_schedule='cosine', timesteps=1000, beta_start=0.0001, beta_end=0.02):
+    def __init__(self, noise_schedule='cosine', timesteps=1000, beta_start=0.0001, beta_end=0.02,
+                 prediction_type='epsilon'):
+        """`prediction_type` (additive): what the U-Net's output means -- 'epsilon' (default, the reference) or
+        'v_prediction', v = sqrt(abar) eps - sqrt(1 - abar) z_0 (Salimans & Ho 2022).  A plain attribute:
+        no buffer is registered for it, the coefficients come from `alphas_cumprod`."""
         super().__init__()
+        from .prediction import check_prediction_type
+        self.prediction_type = check_prediction_type(prediction_type)
         self.timesteps = timesteps
         self.noise_schedule = noise_schedule
         if noise_schedule == 'linear':
@@ -69,6 +75,60 @@ class GaussianDiffusion(nn.Module):
         z_t = (self._extract(self.sqrt_alphas_cumprod, t, z_0.shape) * z_0 +
                self._extract(self.sqrt_one_minus_alphas_cumprod, t, z_0.shape) * noise)
         return z_t, noise
+
+    # ---- v-prediction ---------------------------------------------------------------------------
+    def v_target(self, z_0, t, noise):
+        """The training target of 'v_prediction': v = sqrt(abar_t) noise - sqrt(1 - abar_t) z_0 (elementwise torch ops on
+        whatever device the tensors live, from the two buffers q_sample reads; the training step forms it in
+        ctsi_q_sample_v from the same buffers)."""
+        return (self._extract(self.sqrt_alphas_cumprod, t, z_0.shape) * noise -
+                self._extract(self.sqrt_one_minus_alphas_cumprod, t, z_0.shape) * z_0)
+
+    def pred_to_eps_rows(self, t_desc, dtype=torch.float32):
+        """Rows {sqrt(abar_t), sqrt(1 - abar_t), 0, 0} of ctsi_pred_to_eps for the integer timesteps `t_desc`: eps =
+        sqrt(abar) v + sqrt(1 - abar) z_t.  float64 from `alphas_cumprod`, rounded once to `dtype`."""
+        idx = torch.as_tensor([int(v) for v in t_desc], dtype=torch.long)
+        ab = self.alphas_cumprod.detach().double().cpu()[idx]
+        rows = torch.zeros(len(idx), 4, dtype=torch.float64)
+        rows[:, 0] = torch.sqrt(ab)
+        rows[:, 1] = torch.sqrt(1.0 - ab)
+        return rows.to(dtype)
+
+    @torch.no_grad()
+    def model_output_to_eps(self, z_t, t, out):
+        """The noise prediction a model output stands for, per-sample t: `out` itself under 'epsilon'; under
+        'v_prediction' eps = sqrt(abar_t) out + sqrt(1 - abar_t) z_t -- one ctsi_pred_to_eps launch with one row per sample
+        on ROCm tensors (fp32 result), the same formula in torch on host tensors (their dtype)."""
+        return out if self.prediction_type == "epsilon" else self._from_v(z_t, t, out, False)
+
+    @torch.no_grad()
+    def _predict_z_0_from_v(self, z_t, t, v):
+        """z_0 = sqrt(abar_t) z_t - sqrt(1 - abar_t) v, per-sample t: no division, so it stays exact where abar_t is tiny.
+        The same launch as model_output_to_eps with the rows {-sqrt(1 - abar), sqrt(abar), 0}."""
+        return self._from_v(z_t, t, v, True)
+
+    def _from_v(self, z_t, t, v, want_z0):
+        """a v + b z_t per sample: (a, b) = (sqrt(abar), sqrt(1 - abar)) for eps, (-sqrt(1 - abar), sqrt(abar)) for z_0."""
+        if tuple(v.shape) != tuple(z_t.shape) or t.reshape(-1).shape[0] != z_t.shape[0]:
+            raise ValueError(f"expected a model output of shape {tuple(z_t.shape)} and one timestep per sample, got "
+                             f"{tuple(v.shape)} and t of shape {tuple(t.shape)}")
+        rows = self.pred_to_eps_rows(t.reshape(-1).tolist(), torch.float64)
+        if want_z0:
+            rows = torch.stack([-rows[:, 1], rows[:, 0], rows[:, 2], rows[:, 3]], dim=1)
+        if not (z_t.is_cuda and v.is_cuda):
+            a, b = (rows[:, k].to(v.dtype).reshape(-1, *((1,) * (v.dim() - 1))) for k in (0, 1))
+            return a * v + b * z_t
+        from .engine import Ctx, _ptr
+        ctx = Ctx.get(z_t.device)
+        n = int(z_t.shape[0])
+        z = z_t.detach().to(torch.float32).contiguous()
+        out = v.detach().to(torch.float32).clone(memory_format=torch.contiguous_format)
+        rows = rows.to(ctx.device, torch.float32).contiguous()
+        with ctx.scope():
+            ctx.lib.pred_to_eps(_ptr(out), _ptr(z), None, _ptr(rows), None, n, n, n, z.numel() // n, ctx.sptr)
+            for tns in (z, out, rows):
+                tns.record_stream(ctx.stream)
+        return out
 
     # ---- DDPM reverse process on the HIP engine -------------------------------------------------------
     def ddpm_coef_rows(self, t_desc):
@@ -138,8 +198,8 @@ class GaussianDiffusion(nn.Module):
         """(mean, variance, log_variance) of q(z_{t-1} | z_t, z_0_pred) (diffusion.py:270-308).  `model` is any
         `model(z, t, c) -> eps` callable on the ROCm device (the engine's UNet3D evaluates per-sample timesteps); the
         posterior mean is one ctsi_ddpm_posterior launch.  variance / log_variance are the (B,1,1,1,1) buffer gathers
-        the reference returns."""
-        noise_pred = model(z_t, t, c)
+        the reference returns.  Under 'v_prediction' the model returns v (model_output_to_eps converts it)."""
+        noise_pred = self.model_output_to_eps(z_t, t, model(z_t, t, c))
         _, mean = self._posterior(z_t, t, noise_pred, None, clip_denoised, False, True)
         variance = self._extract(self.posterior_variance, t, z_t.shape)
         log_variance = self._extract(self.posterior_log_variance_clipped, t, z_t.shape)
@@ -156,14 +216,15 @@ class GaussianDiffusion(nn.Module):
         if len(set(tv)) == 1 and clip_denoised and noise is None and _is_engine_unet(model):
             return run_sampler(self, model, tuple(z_t.shape), c, z_t.device, kind="ddpm", t_desc=[tv[0]],
                                progress=False, z_init=z_t)
-        noise_pred = model(z_t, t, c)
+        noise_pred = self.model_output_to_eps(z_t, t, model(z_t, t, c))
         if noise is None:
             noise = torch.randn_like(z_t)
         return self._posterior(z_t, t, noise_pred, noise, clip_denoised, False, True)[1]
 
     def training_loss(self, model, z_0, c, mask=None, vae=None, v_gt=None, use_ssim=False, ssim_weight=0.0,
                       t=None, noise=None, cond_drop_prob=0.0, cond_keep=None):
-        """Min-SNR-5 weighted epsilon-prediction loss (diffusion.py:108-247) with forward AND backward on the HIP
+        """Min-SNR-5 weighted epsilon-prediction loss (diffusion.py:108-247; under prediction_type='v_prediction' the
+        target is v and the weight min(snr, 5) / (snr + 1), everything else unchanged) with forward AND backward on the HIP
         engine: the returned scalar carries an autograd node whose backward launches the engine's gradient kernels
         and feeds the U-Net parameters' .grad.
 
@@ -203,7 +264,9 @@ class GaussianDiffusion(nn.Module):
             keep = keep.to(device)
             c = c * keep.to(c.dtype)[:, None, None, None, None]
         snr = self.alphas_cumprod[t] / (1 - self.alphas_cumprod[t] + 1e-8)
-        snr_weight = torch.clamp(snr, max=5.0) / (snr + 1e-8)
+        v_pred = self.prediction_type == "v_prediction"
+        # Min-SNR-5 (Hang et al. 2023): min(snr, 5) / snr on an eps target, min(snr, 5) / (snr + 1) on a v target
+        snr_weight = torch.clamp(snr, max=5.0) / (snr + 1.0 if v_pred else snr + 1e-8)
         if mask is not None:
             m = mask.to(device=device, dtype=torch.float32)
             if m.dim() != 3 or m.shape[0] != B or m.shape[2] != d or m.shape[1] not in (1, L):
@@ -220,8 +283,10 @@ class GaussianDiffusion(nn.Module):
             norm = snr_weight / float(B * L * d * h * w)
         ctx = Ctx.get(device)
         with ctx.scope():
-            prog = cached_program(model, ("unet-train", ctx.device.index, B, d, h, w),
-                                  lambda: UNetTrainProgram(ctx, model, B, d, h, w))
+            # the epsilon key is what it always was; a v program (q_sample_v, a target buffer) has its own
+            key = ("unet-train", ctx.device.index, B, d, h, w) + ((self.prediction_type,) if v_pred else ())
+            kw = dict(prediction=self.prediction_type) if v_pred else {}
+            prog = cached_program(model, key, lambda: UNetTrainProgram(ctx, model, B, d, h, w, **kw))
             prog.set_diffusion(self)
         loss = train_step(prog, z_0.detach().float(), c.detach().float(), t, noise.float(), norm, m)
         loss_dict = {'mse': loss.item()}
@@ -243,7 +308,7 @@ class GaussianDiffusion(nn.Module):
                     with ctx.scope():
                         ctx.lib.ndhwc_f32_to_ncdhw_f32(C.c_void_p(prog.eps.data_ptr()), C.c_void_p(eps.data_ptr()), B, L, d, h,
                                                        w, ctx.sptr)
-                    z0_pred = self._predict_z_0_from_noise(z_t, t, eps)
+                    z0_pred = (self._predict_z_0_from_v if v_pred else self._predict_z_0_from_noise)(z_t, t, eps)
                     # training keeps the bf16 programs whatever `vae.inference_precision` says
                     v_pred = vae._decode(z0_pred, "bf16") if hasattr(vae, "_decode") else vae.decode(z0_pred)
                     terms = []

@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from .lib import ConvDesc, ConvOut, CtsiError, get_lib
+from .prediction import add_pred_to_eps, check_prediction_type
 
 _CTX: Dict[int, "Ctx"] = {}
 
@@ -1107,10 +1108,14 @@ class UNetProgram(Program):
     conditioning, rows [n, 2n) on the null conditioning, the all-zero latent -- and add_sampler_step puts ctsi_cfg_combine
     between the network and the update and ctsi_cfg_mirror behind it.  z, hist, noise, the nonfinite table and
     z_ncdhw() / eps_ncdhw() stay n-sized; timestep rows are per (evaluation, network row): 2n per evaluation.
-    `rescale` adds the statistics pass of the guidance rescale (phi > 0)."""
+    `rescale` adds the statistics pass of the guidance rescale (phi > 0).
+
+    `prediction`: 'epsilon' (default: the program is what it always was) or 'v_prediction' -- the network
+    output is v, and add_sampler_step puts one ctsi_pred_to_eps launch over all network rows between the network and
+    everything that reads eps (guidance, update, counters, eps_ncdhw()); its rows sit in `pred_rows`, one per evaluation."""
 
     def __init__(self, ctx: Ctx, unet, n: int, d: int, h: int, w: int, max_rows: int, attention_mode="fast",
-                 shard=None, guided: bool = False, rescale: bool = False):
+                 shard=None, guided: bool = False, rescale: bool = False, prediction: str = "epsilon"):
         """`d` is the depth this program owns: the whole volume on one GPU, or the rank's slab of
         `shard.depth_total // shard.world` slices when `shard` (parallel.ShardSpec) is given."""
         super().__init__(ctx)
@@ -1122,6 +1127,7 @@ class UNetProgram(Program):
                             "volume per rank and the rescale statistics would need a collective")
         self.unet = unet
         self.guided, self.rescale = bool(guided), bool(guided and rescale)
+        self.prediction = check_prediction_type(prediction)
         self.n, self.d, self.h, self.w = n, d, h, w
         n = self.nb = 2 * n if guided else n        # the network's batch; self.n stays the number of samples
         L = unet.latent_dim
@@ -1253,11 +1259,12 @@ class UNetProgram(Program):
         row = torch.tensor([float(scale), float(rescale)], dtype=torch.float32)
         self.cfg_scale.copy_(row.expand(self.cfg_scale.shape[0], 2))
 
-    def set_schedule(self, t_rows: Sequence[float], coef_rows: Optional[torch.Tensor] = None):
+    def set_schedule(self, t_rows: Sequence[float], coef_rows: Optional[torch.Tensor] = None,
+                     pred_rows: Optional[torch.Tensor] = None):
         """Upload the timestep of every (step, network row) row -- n per evaluation, 2n in a guided program -- embed all
         of them in one go and rewind the device-side step counter.  Integer-valued rows take the int32 entry
         (ctsi_time_embed_fwd); a schedule with any fractional timestep is embedded from fp32 rows
-        (ctsi_time_embed_fwd_tf)."""
+        (ctsi_time_embed_fwd_tf).  `pred_rows`: the (E, 4) conversion rows of a v-prediction program (StepPlan.pred)."""
         rows = len(t_rows)
         if rows > self.max_rows:
             raise CtsiError(f"schedule needs {rows} rows but the program was built for {self.max_rows}")
@@ -1271,6 +1278,15 @@ class UNetProgram(Program):
             self.t_rows[:rows].copy_(torch.tensor([int(v) for v in vals], dtype=torch.int32), non_blocking=False)
         if coef_rows is not None:
             self.coef[:coef_rows.shape[0]].copy_(coef_rows.to(torch.float32))
+        if self.prediction != "epsilon" and getattr(self, "pred_rows", None) is not None:
+            if pred_rows is None:
+                raise CtsiError("internal: a v-prediction step program needs the schedule's conversion rows")
+            if pred_rows.shape[0] > self.pred_rows.shape[0]:
+                raise CtsiError(f"schedule needs {pred_rows.shape[0]} conversion rows but the program holds "
+                                f"{self.pred_rows.shape[0]}")
+            if self.hist is None and bool((pred_rows[:, 2] != 0).any()):
+                raise CtsiError("internal: a conversion row reads the history buffer but the sampler kind has none")
+            self.pred_rows[:pred_rows.shape[0]].copy_(pred_rows.to(torch.float32))
         self.step_ptr.zero_()
         embed, tp = (lib.time_embed_fwd_tf, self.t_rows_f) if fractional else (lib.time_embed_fwd, self.t_rows)
         embed(_ptr(tp), rows, self.dim, self.time_dim, _ptr(self.w1), _ptr(self.b1), _ptr(self.w2), _ptr(self.b2),
@@ -1338,10 +1354,16 @@ class UNetProgram(Program):
 
     def add_sampler_step(self, kind: str, with_noise: bool):
         """Append the update of sampler `kind` (a SAMPLER_STEPS key) and the step-counter increment (done once, before
-        capture).  'heun': one update per U-Net evaluation (predictor, corrector or final row); `with_noise` = churn on."""
+        capture).  'heun': one update per U-Net evaluation (predictor, corrector or final row); `with_noise` = churn on.
+        A v-prediction program converts the network output first (prediction.add_pred_to_eps), ahead of the guidance."""
         lib, sptr = self.lib, self.ctx.sptr
         n, L, d, h, w = self.n, self.L, self.d, self.h, self.w
         entry = SAMPLER_STEPS[kind]
+        self.hist = None
+        if self.prediction != "epsilon":
+            if entry.hist:      # (the conversion of a Heun corrector row reads the history)
+                self.hist = self.persistent((n, d, h, w, L), torch.float32, zero=True)
+            add_pred_to_eps(self)
         if self.guided:
             self._add_guidance_combine()
         if with_noise and self.noise is None:
@@ -1355,7 +1377,8 @@ class UNetProgram(Program):
         self.nonfinite = self.persistent((self.max_rows + 2, 6), torch.int32, zero=True)
         nfp = _ptr(self.nonfinite)
         # the kind's history (fp32 NDHWC, zeroed: the update only ever stores finite values in it)
-        self.hist = self.persistent((n, d, h, w, L), torch.float32, zero=True) if entry.hist else None
+        if self.hist is None and entry.hist:
+            self.hist = self.persistent((n, d, h, w, L), torch.float32, zero=True)
         hp = _ptr(self.hist)
         xin = self.xin
 

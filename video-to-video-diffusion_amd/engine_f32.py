@@ -284,13 +284,14 @@ class UNetProgramF32(_F32Ops, UNetProgram):
     a concatenated pair (never materialised)."""
 
     def __init__(self, ctx: Ctx, unet, n: int, d: int, h: int, w: int, max_rows: int, attention_mode="fast", shard=None,
-                 guided: bool = False, rescale: bool = False):
+                 guided: bool = False, rescale: bool = False, prediction: str = "epsilon"):
         if shard is not None:
             raise CtsiError("the fp32 inference mode does not support depth sharding")
         if attention_mode != "fast":
             raise CtsiError("the fp32 inference mode supports attention_mode='fast' only (the exact mode evaluates the "
                             "same mathematics, DESIGN section 3.2)")
-        super().__init__(ctx, unet, n, d, h, w, max_rows, attention_mode, shard=None, guided=guided, rescale=rescale)
+        super().__init__(ctx, unet, n, d, h, w, max_rows, attention_mode, shard=None, guided=guided, rescale=rescale,
+                         prediction=prediction)
 
     def _input_acts(self, n, d, h, w, halo) -> Tuple[Act, Optional[Act]]:
         L = self.L

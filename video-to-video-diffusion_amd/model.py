@@ -62,7 +62,9 @@ class VideoToVideoDiffusion(nn.Module):
         self.diffusion = GaussianDiffusion(noise_schedule=config.get('noise_schedule', 'cosine'),
                                            timesteps=config.get('diffusion_timesteps', 1000),
                                            beta_start=config.get('beta_start', 0.0001),
-                                           beta_end=config.get('beta_end', 0.02))
+                                           beta_end=config.get('beta_end', 0.02),
+                                           # additive key, top level like `noise_schedule`: 'epsilon' | 'v_prediction'
+                                           prediction_type=config.get('prediction_type', 'epsilon'))
         self.config = config
         self.use_pretrained = use_pretrained
         # additive key, top level like every U-Net / diffusion key: the conditioning-dropout probability of `forward`

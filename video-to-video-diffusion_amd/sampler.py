@@ -273,6 +273,33 @@ def heun_coef_rows(alphas_cumprod: torch.Tensor, sigmas: Sequence[float], order:
                     init=(sig[0] / A0, churn[0] / A0))
 
 
+def heun_pred_rows(heun: HeunRows, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """ctsi_pred_to_eps rows {a, b0, b1, 0} for the evaluations of an EDM run under v-prediction.  At
+    the noise level sigma = sigma_eval[e] the VP coefficients are alpha = 1 / sqrt(1 + sigma^2), beta = sigma alpha, and
+    eps = alpha v + beta zin with zin the network's input.  A predictor, Euler or final row evaluates the network on the state
+    zhat itself: {alpha, beta, 0}.  A corrector row evaluates it on z' = c4 zhat + c5 D1 (c4 = p / a', c5 = q / a' of the
+    preceding predictor row), which the engine recomputes instead of storing: {alpha, beta c4, beta c5} with the D1 buffer
+    as `hist`.  float64, rounded once to `dtype`."""
+    E = len(heun.sigma_eval)
+    rows = np.zeros((E, 4), dtype=np.float64)
+    a = lambda v: math.sqrt(1.0 + v * v)
+    step = 0
+    for e in range(E):
+        sg = float(heun.sigma_eval[e])
+        alpha = 1.0 / a(sg)
+        beta = sg * alpha
+        if e > 0 and not heun.closes[e - 1]:            # the corrector of step `step`: sigma_eval[e] = sigma_{step+1}
+            s_hat, s1 = float(heun.sigma_hat[step]), float(heun.sigmas[step + 1])
+            c4 = a(s_hat) * s1 / s_hat / a(s1)
+            c5 = (1.0 - s1 / s_hat) / a(s1)
+            rows[e] = (alpha, beta * c4, beta * c5, 0.0)
+        else:
+            rows[e] = (alpha, beta, 0.0, 0.0)
+        if heun.closes[e]:
+            step += 1
+    return torch.from_numpy(rows).to(dtype)
+
+
 class StepPlan(NamedTuple):
     """One sampling run as data, per U-Net evaluation e (E = len(t)).  run_sampler, run_sampler_sharded and the
     generic-callable loop read it and never test the sampler kind; only _step_plan builds one."""
@@ -288,6 +315,7 @@ class StepPlan(NamedTuple):
     key_order: tuple                # ... and their last element: (order,) for dpmpp / heun, else ()
     init: Optional[Tuple[float, float]] = None     # z_0 = init[0] eps + init[1] eps_0; None: z_0 = eps
     init_noise: bool = False                       # eps_0 = noise_fn(0, shape) is drawn (step 0 churns)
+    pred: Optional[torch.Tensor] = None            # (E, 4) ctsi_pred_to_eps rows under 'v_prediction'; None: the output is eps
 
     def initial_state(self, z0: torch.Tensor, noise_fn, shape, dev) -> torch.Tensor:
         """The loop's start from the initial draw eps = z0 (Heun's zhat_0 is formed in float64)."""
@@ -303,13 +331,16 @@ def _step_plan(diffusion, kind: str, t_desc: Sequence, eta: float, order: int, h
     """The only place that branches on the sampler kind.  A new sampler adds one branch here and one row to
     engine.SAMPLER_STEPS (its update entry and operands).  'heun' takes the rows `heun` (t_desc = heun.t)."""
     E = len(t_desc)
+    # v-prediction: the conversion rows, and the prediction type in the program cache keys (the epsilon keys stay as they are)
+    v_pred = getattr(diffusion, "prediction_type", "epsilon") == "v_prediction"
+    vkey = ("v_prediction",) if v_pred else ()
     if kind == "heun":
         if heun is None or len(heun.t) != E:
             raise ValueError("kind='heun' needs the rows of heun_coef_rows(...) (heun=) and t_desc = heun.t")
         with_noise = bool((heun.gammas > 0).any())        # churn on
         return StepPlan(kind, heun.rows, tuple(float(t) for t in t_desc), torch.float32, tuple(heun.noise_step),
-                        tuple(heun.closes), with_noise, True, (kind, with_noise), (order,), init=heun.init,
-                        init_noise=bool(heun.gammas[0] > 0))
+                        tuple(heun.closes), with_noise, True, (kind, with_noise) + vkey, (order,), init=heun.init,
+                        init_noise=bool(heun.gammas[0] > 0), pred=heun_pred_rows(heun) if v_pred else None)
     if kind == "ddim":
         coef = ddim_coef_rows(diffusion.alphas_cumprod, t_desc, eta)
     elif kind == "ddpm":
@@ -321,7 +352,8 @@ def _step_plan(diffusion, kind: str, t_desc: Sequence, eta: float, order: int, h
     with_noise = kind == "ddpm" or eta > 0
     return StepPlan(kind, coef, tuple(int(t) for t in t_desc), torch.long,
                     tuple(range(E)) if with_noise else (-1,) * E, (True,) * E, with_noise, kind != "ddpm",
-                    (kind, with_noise), (order,) if kind == "dpmpp" else ())
+                    (kind, with_noise) + vkey, (order,) if kind == "dpmpp" else (),
+                    pred=diffusion.pred_to_eps_rows(t_desc) if v_pred else None)
 
 
 def _progress(plan: StepPlan, progress: bool):
@@ -350,6 +382,8 @@ def _run_generic(plan: StepPlan, model, shape, conditioning, ctx, z0, *, noise_f
     callable is opaque.  The engine's own UNet3D takes the hipGraph path in run_sampler instead.
     The model sees t as plan.t_dtype (Heun's fractional timesteps as fp32, as the reference embeds t) and as z the
     input the update writes to `zin`: the new state, or after a Heun predictor row the corrector's z' (z keeps zhat).
+    Under 'v_prediction' (plan.pred) the callable returns v: ctsi_pred_to_eps turns the evaluation's rows into eps before
+    the guidance and the update, as in the step programs; eps_trajectory holds that eps.
     `guidance` = (s, phi): classifier-free guidance -- two calls per evaluation, model(z, t, c) and model(z, t,
     zeros_like(c)), combined by ctsi_cfg_combine (the entry of the guided step program); eps_trajectory then holds the
     guided eps."""
@@ -363,6 +397,11 @@ def _run_generic(plan: StepPlan, model, shape, conditioning, ctx, z0, *, noise_f
     zin_nd = torch.empty_like(z_nd)
     eps_nd = torch.empty(((2 if guidance else 1) * n, d, h, w, L), dtype=torch.float32, device=dev)
     hist = torch.zeros_like(z_nd) if SAMPLER_STEPS[plan.kind].hist else None
+    pred = None
+    if plan.pred is not None:
+        if hist is None and bool((plan.pred[:, 2] != 0).any()):
+            raise CtsiError("internal: a conversion row reads the history buffer but the sampler kind has none")
+        pred = plan.pred.to(dev, torch.float32).contiguous()
     step_ptr = torch.zeros(1, dtype=torch.int32, device=dev)
     nonfinite = torch.zeros((evals + 2, 6), dtype=torch.int32, device=dev)
     cond = conditioning.to(dev)
@@ -389,7 +428,7 @@ def _run_generic(plan: StepPlan, model, shape, conditioning, ctx, z0, *, noise_f
             eps_u = model(z, t, null_cond)
             _check_eps(eps_u, shape)
             eps_u = eps_u.detach().to(torch.float32).contiguous()
-        elif eps_trajectory is not None:
+        elif eps_trajectory is not None and pred is None:
             eps_trajectory.append(eps.clone())
         noise = None
         if plan.noise_step[e] >= 0:
@@ -398,6 +437,14 @@ def _run_generic(plan: StepPlan, model, shape, conditioning, ctx, z0, *, noise_f
             lib.ncdhw_f32_to_ndhwc_f32(_ptr(eps), _ptr(eps_nd), n, L, d, h, w, sptr)
             if guidance:
                 lib.ncdhw_f32_to_ndhwc_f32(_ptr(eps_u), _ptr(eps_u_nd), n, L, d, h, w, sptr)
+            if pred is not None:
+                lib.pred_to_eps(_ptr(eps_nd), _ptr(z_nd), _ptr(hist), _ptr(pred), _ptr(step_ptr), 1, eps_nd.shape[0], n,
+                                L * d * h * w, sptr)
+                if not guidance and eps_trajectory is not None:
+                    eps_c = torch.empty((n, L, d, h, w), dtype=torch.float32, device=dev)
+                    lib.ndhwc_f32_to_ncdhw_f32(_ptr(eps_nd), _ptr(eps_c), n, L, d, h, w, sptr)
+                    eps_trajectory.append(eps_c)
+            if guidance:
                 if cfg_stats is not None:
                     lib.cfg_stats(_ptr(eps_nd), _ptr(cfg_scale), None, _ptr(cfg_partials), n, L, d, h, w, sptr)
                     lib.cfg_stats_finalize(_ptr(cfg_partials), _ptr(cfg_stats), n, L, d, h, w, sptr)
@@ -443,7 +490,8 @@ def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, 
         key = ("sampler-shard", ctx.device.index, 1, d, h, w, comm.rank, comm.world) + plan.key + plan.key_order
 
         def build():
-            prog = UNetProgram(ctx, unet, 1, dl, h, w, diffusion.timesteps + 1, "fast", shard=spec)
+            kw = dict(prediction="v_prediction") if plan.pred is not None else {}   # elementwise on the rank's slab
+            prog = UNetProgram(ctx, unet, 1, dl, h, w, diffusion.timesteps + 1, "fast", shard=spec, **kw)
             prog.add_sampler_step(plan.kind, plan.with_noise)
             return prog
 
@@ -457,7 +505,7 @@ def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, 
                 prog.noise.copy_(noises[i][b:b + 1, :, lo:lo + dl].to(ctx.device, torch.float32))
 
             prog.load_latents(z0[b:b + 1], conditioning[b:b + 1])
-            prog.set_schedule(list(plan.t), plan.coef.to(ctx.device))
+            prog.set_schedule(list(plan.t), plan.coef.to(ctx.device), plan.pred)
             if capture and prog.graph is None:
                 prog.capture()
                 prog.step_ptr.zero_()
@@ -489,7 +537,9 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
     path, untouched.  Any other finite s evaluates the U-Net on the conditioning and on the null conditioning (the
     all-zero latent) as ONE batch-2n evaluation inside the captured step, and feeds eps = m (eps_u + s (eps_c - eps_u)),
     m = phi std(eps_c) / std(eps_g) + 1 - phi per sample, to the unchanged update; trajectories and nonfinite counters
-    report on that eps.  Not available with depth sharding (CtsiError)."""
+    report on that eps.  Not available with depth sharding (CtsiError).
+    `diffusion.prediction_type == 'v_prediction'`: the model's output is v; one ctsi_pred_to_eps launch
+    per evaluation turns it into eps ahead of the guidance and the update, so everything above holds as written."""
     s_cfg, phi_cfg = check_guidance(guidance_scale, guidance_rescale)
     guided = s_cfg != 1.0
     plan = _step_plan(diffusion, kind, t_desc, eta, order, heun)
@@ -537,6 +587,8 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
         def build():
             cls = UNetProgramF32 if precision == "fp32" else UNetProgram
             kw = dict(guided=True, rescale=phi_cfg > 0.0) if guided else {}
+            if plan.pred is not None:
+                kw["prediction"] = "v_prediction"
             prog = cls(ctx, unet, n, d, h, w, max_rows, unet.attention_mode, **kw)
             prog.add_sampler_step(plan.kind, plan.with_noise)
             return prog
@@ -551,7 +603,7 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
         cnd = conditioning.detach().to(ctx.device, torch.float32).contiguous()
         ctx.lib.count_nonfinite_f32(_ptr(cnd), cnd.numel(), 0, C.c_void_p(nf_tail + 24), ctx.sptr)
         cnd.record_stream(ctx.stream)
-        prog.set_schedule([t for t in plan.t for _ in range(nb)], plan.coef.to(ctx.device))
+        prog.set_schedule([t for t in plan.t for _ in range(nb)], plan.coef.to(ctx.device), plan.pred)
         if guided:
             prog.set_guidance(s_cfg, phi_cfg)     # a device write: the same captured graph serves every scale
         if prog.graph is None:

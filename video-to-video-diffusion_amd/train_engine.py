@@ -28,6 +28,7 @@ import torch.nn as nn
 
 from .engine import Act, Ctx, Program, _ptr
 from .lib import CtsiError, WgradDesc
+from .prediction import check_prediction_type
 
 
 class TrainProgram(Program):
@@ -282,8 +283,11 @@ class TrainProgram(Program):
 
 
 class UNetTrainProgram(TrainProgram):
-    def __init__(self, ctx: Ctx, unet, n: int, d: int, h: int, w: int):
+    def __init__(self, ctx: Ctx, unet, n: int, d: int, h: int, w: int, prediction: str = "epsilon"):
+        """`prediction` = 'v_prediction' (DESIGN section 18): the inputs come from ctsi_q_sample_v, which also writes the
+        target v into `v_target`, and both loss launches read that buffer where the epsilon program reads the noise."""
         super().__init__(ctx)
+        self.prediction = check_prediction_type(prediction)
         self.weight_cache = False    # weights change every optimizer step: private images, repacked in place
         if unet.attention_mode != "fast":
             raise CtsiError("training supports attention_mode='fast' only")
@@ -313,6 +317,9 @@ class UNetTrainProgram(TrainProgram):
         self.xin = Act(self.persistent((n * vox * 2 * L,), torch.bfloat16, zero=True), n, 2 * L, d, h, w, 0)
         self.z0 = self.persistent((n, L, d, h, w), torch.float32, zero=True)
         self.noise = self.persistent((n, L, d, h, w), torch.float32, zero=True)
+        v_pred = self.prediction == "v_prediction"
+        self.v_target = self.persistent((n, L, d, h, w), torch.float32, zero=True) if v_pred else None
+        self.target = self.v_target if v_pred else self.noise      # what the prediction is compared with
         self.cond = self.persistent((n, L, d, h, w), torch.float32, zero=True)
         self.t_rows = self.persistent((n,), torch.int32, zero=True)
         self.norm = self.persistent((n,), torch.float32, zero=True)
@@ -356,8 +363,12 @@ class UNetTrainProgram(TrainProgram):
         prog = self
 
         def run_inputs():
-            lib.q_sample(_ptr(prog.z0), _ptr(prog.noise), _ptr(prog.sqrt_ac), _ptr(prog.sqrt_1mac), _ptr(prog.t_rows),
-                         prog.xin.ip, n, L, d, h, w, 2 * L, 0, sptr)
+            if v_pred:
+                lib.q_sample_v(_ptr(prog.z0), _ptr(prog.noise), _ptr(prog.sqrt_ac), _ptr(prog.sqrt_1mac),
+                               _ptr(prog.t_rows), prog.xin.ip, _ptr(prog.v_target), n, L, d, h, w, 2 * L, 0, sptr)
+            else:
+                lib.q_sample(_ptr(prog.z0), _ptr(prog.noise), _ptr(prog.sqrt_ac), _ptr(prog.sqrt_1mac),
+                             _ptr(prog.t_rows), prog.xin.ip, n, L, d, h, w, 2 * L, 0, sptr)
             lib.ncdhw_f32_to_ndhwc_bf16(_ptr(prog.cond), prog.xin.ip, n, L, d, h, w, 2 * L, L, sptr)
             lib.time_embed_train_fwd(_ptr(prog.t_rows), n, prog.dim, prog.time_dim, _ptr(prog.w1), _ptr(prog.b1),
                                      _ptr(prog.w2), _ptr(prog.b2), _ptr(prog.w_all), _ptr(prog.b_all), prog.total_out,
@@ -367,7 +378,8 @@ class UNetTrainProgram(TrainProgram):
             kind="train.inputs", z0=self.z0, noise=self.noise, cond=self.cond, t_rows=self.t_rows,
             sqrt_ac=lambda: prog.sqrt_ac, sqrt_1mac=lambda: prog.sqrt_1mac, xin=self.xin, L=L, dim=self.dim,
             time_dim=self.time_dim, w1=self.w1, b1=self.b1, w2=self.w2, b2=self.b2, w_all=self.w_all, b_all=self.b_all,
-            te_scratch=self.te_scratch, tbias=self.tbias))
+            te_scratch=self.te_scratch, tbias=self.tbias,
+            **(dict(kernel="q_sample_v", v_target=self.v_target) if v_pred else {})))
         self.zero_gn_op()
 
         # ---- forward network (same wiring as engine.UNetProgram) -------------------------------------------------
@@ -400,22 +412,22 @@ class UNetTrainProgram(TrainProgram):
                     gy=self.d_eps)
 
         def run_loss():
-            lib.mse_loss_fwd(_ptr(prog.eps), _ptr(prog.noise), _ptr(prog.mask) if prog.use_mask else None,
+            lib.mse_loss_fwd(_ptr(prog.eps), _ptr(prog.target), _ptr(prog.mask) if prog.use_mask else None,
                              _ptr(prog.norm), n, L, d, h, w, _ptr(prog.loss_ws), _ptr(prog.loss_out), sptr)
 
         self._emit(run_loss, "loss.fwd", audit=dict(
-            kind="loss.fwd", pred=self.eps, noise=self.noise, mask=lambda: prog.mask if prog.use_mask else None,
+            kind="loss.fwd", pred=self.eps, noise=self.target, mask=lambda: prog.mask if prog.use_mask else None,
             norm=self.norm, out=self.loss_out))
         self.n_fwd = len(self.ops)
         self.generation = 0   # bumped by every run_forward (see there)
 
         # ---- backward: loss, then the tape in reverse, then the time embedding ---------------------------------
         def run_loss_bwd():
-            lib.mse_loss_bwd(_ptr(prog.eps), _ptr(prog.noise), _ptr(prog.mask) if prog.use_mask else None,
+            lib.mse_loss_bwd(_ptr(prog.eps), _ptr(prog.target), _ptr(prog.mask) if prog.use_mask else None,
                              _ptr(prog.norm), _ptr(prog.gscale), n, L, d, h, w, prog.d_eps.ip, prog.Lp, sptr)
 
         self._emit(run_loss_bwd, "loss.bwd", audit=dict(
-            kind="loss_bwd", pred=self.eps, noise=self.noise, mask=lambda: prog.mask if prog.use_mask else None, norm=self.norm,
+            kind="loss_bwd", pred=self.eps, noise=self.target, mask=lambda: prog.mask if prog.use_mask else None, norm=self.norm,
             gscale=self.gscale, out=self.d_eps))
         for fn in reversed(self.tape):
             fn()
