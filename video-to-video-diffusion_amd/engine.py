@@ -33,7 +33,8 @@ _CTX: Dict[int, "Ctx"] = {}
 # the fp32 weight tensor the layer's weight_fn returns).  Every program built from the same weights -- the sampler program, the
 # plain forward, other latent shapes, window batches, the depth-sharded variants: 265 M parameters = 0.53 GB of packed
 # bf16 per program otherwise -- shares ONE image and packs it once.  Entries are immutable and die with their last user
-# (weak values); a program whose weights changed looks up / packs new images and drops its captured graph.
+# (weak values); a program whose weights changed looks up / packs new images and drops its captured graph.  Both precisions
+# read and fill it in one place, Program._weight_image.
 _PACKED: Dict[int, "weakref.WeakValueDictionary"] = {}
 # every live program (weak): check_device_errors re-zeroes their split-K hand-off workspaces after a reported device error
 _LIVE_PROGRAMS: "weakref.WeakSet" = weakref.WeakSet()
@@ -179,6 +180,29 @@ class Act:
         return C.c_void_p(self.t.data_ptr())
 
 
+class _ConvPlan(NamedTuple):
+    """One bf16 conv layer as Program._conv_setup leaves it: the plan and everything the emitters read of it."""
+    plan: C.c_void_p
+    desc: ConvDesc
+    out_dims: Tuple[int, int, int]      # (d, h, w) of the output
+    wbytes: int                         # size of the packed weight image
+    mode: int                           # the plan's kernel family (ctsi_conv_plan_config)
+    kernel: str                         # the launch's label (_conv_label)
+    flops: float
+    tiles: int
+    tps: int                            # tiles per sample
+    cpad: int                           # cout padded to the kernel's tile
+    workspace: int                      # split-K hand-off workspace (device address), 0: the plan has none
+    holder: List[Optional[torch.Tensor]]    # [the packed weight image] (Program._weight_image)
+
+
+def _conv_label(bm: int, bn: int, mode: int, desc: ConvDesc, split_k: bool) -> str:
+    """conv_mfma_<bm>x<bn>_m<mode>[t|d][s] -- t: ConvTranspose form, d: Downsample form (both of the k32 family, mode 9),
+    s: split-K form."""
+    form = "t" if desc.transposed else ("d" if (desc.sh, desc.sw) == (2, 2) else "")
+    return "conv_mfma_%dx%d_m%d%s%s" % (bm, bn, mode, form if mode == 9 else "", "s" if split_k else "")
+
+
 class Program:
     """A flat list of libctsi launches plus the buffers they touch."""
 
@@ -203,6 +227,9 @@ class Program:
         self._gn_need: List[Tuple[int, int]] = []
         self.graph = None
         self._params: List[torch.Tensor] = []
+        self._param_storages: set = set()    # storage addresses of the tracked parameters (_build_fast)
+        self._track_module: Optional[nn.Module] = None
+        self._events: List[C.c_void_p] = []  # fork / join events of overlapped convs (destroyed with the program)
         self._versions: Tuple[int, ...] = ()
         self.shard = None  # parallel.ShardSpec for depth-sharded programs
         self.weight_cache = True    # share packed weight images between programs (training programs repack in place)
@@ -211,7 +238,7 @@ class Program:
         # fast re-pack (see fast_repack): what every pack function reads and writes, so that the launches can be replayed from
         # prebuilt pointer tables without touching torch
         self._f32_meta: List[dict] = []     # dev_f32 buffers: dict(buf, make, parts, scale, fn)
-        self._pack_meta: List[dict] = []    # conv weight images: dict(plan, weight_fn, holder, fn)
+        self._pack_meta: List[dict] = []    # conv weight images: dict(plan (None: an fp32 image), weight_fn, holder, fn)
         self._fast = None
         self._sk_workspaces: List[torch.Tensor] = []   # split-K hand-off workspaces (tickets / flags + parked partial sums)
         _LIVE_PROGRAMS.add(self)
@@ -396,7 +423,7 @@ class Program:
         for ent in self._pack_meta:
             holder, plan, wfn = ent["holder"], ent["plan"], ent["weight_fn"]
             fast = getattr(wfn, "fast_layout", None)
-            if holder[0] is None:
+            if holder[0] is None or plan is None:     # (an fp32 image is packed from its descriptor: no plan to replay)
                 slow.append(ent["fn"])
                 continue
             dst = C.c_void_p(holder[0].data_ptr())
@@ -417,8 +444,8 @@ class Program:
                 packs.append((lib.conv_plan_pack_weights, (plan, C.c_void_p(wt.data_ptr()), dst, sptr)))
             else:
                 slow.append(ent["fn"])
-        # refresh functions registered outside the two tables (an attention block's folded matrix, the packs of an overlapped
-        # depth-sharded conv) have no fast form: they run as they are, and keep the step out of the recorded graph
+        # refresh functions registered outside the two tables (an attention block's folded matrix) have no fast form: they
+        # run as they are, and keep the step out of the recorded graph
         known = {id(ent["fn"]) for ent in self._f32_meta} | {id(ent["fn"]) for ent in self._pack_meta}
         slow.extend(fn for fn in self.pack_fns if id(fn) not in known and fn not in slow)
         seg_bytes = b"".join(struct.pack("<QQqfi", s_, d_, n_, sc, 0) for (s_, d_, n_, sc) in segs)
@@ -472,9 +499,8 @@ class Program:
         replaced `module.weight` are all seen.  Writes through `p.data` / raw pointers bump nothing torch can
         observe: call `model.invalidate_engine_cache()` after those."""
         fp = [(p._version, p.data_ptr()) for p in self._params]
-        mod = getattr(self, "_track_module", None)
-        if mod is not None:
-            fp.extend((id(p), p._version, p.data_ptr()) for p in mod.parameters())
+        if self._track_module is not None:
+            fp.extend((id(p), p._version, p.data_ptr()) for p in self._track_module.parameters())
         return tuple(fp)
 
     def track_module(self, module: nn.Module):
@@ -502,21 +528,154 @@ class Program:
         return False
 
     # ---- conv ----------------------------------------------------------------------------------------------
+    # One emitter for every conv of every program.  What both precisions need -- the weight image, the `norm_in` pre-pass,
+    # the bias buffer, the column-sum slab, the ConvOut target, the flops count -- is a method of its own below:
+    # conv() / _conv_overlapped put them around a conv plan, engine_f32._F32Ops.conv around ctsi_conv_f32_fwd.
+    def _weight_image(self, weight_fn, sig: tuple, wbytes: int, pack_call, plan=None) -> List[Optional[torch.Tensor]]:
+        """Register the packed kernel-layout image of a conv's weights and return its holder, a one-element list that
+        repack() fills and the launch reads.  `sig` is the layout half of the cache key (_pack_sig / _f32_pack_sig);
+        `pack_call(src, dst)` lays the fp32 weights out: ctsi_conv_plan_pack_weights on `plan`, or
+        ctsi_conv_f32_pack_weights on a descriptor (`plan` None).  A program that shares images (`weight_cache`) looks the
+        image up in _PACKED by (sig, content) and packs on a miss only; the others own a private image, repacked in place."""
+        prog, dev = self, self.ctx.device
+        holder: List[Optional[torch.Tensor]] = [None]
+
+        def pack():
+            wt = weight_fn().detach().to(device=dev, dtype=torch.float32).contiguous()
+            if prog.weight_cache:
+                cache = _PACKED.setdefault(dev.index, weakref.WeakValueDictionary())
+                key = (sig, _content_key(wt))
+                t = cache.get(key)
+                if t is None:
+                    t = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+                    pack_call(_ptr(wt), _ptr(t))
+                    cache[key] = t
+                    prog.pack_stats["packed"] += 1
+                else:
+                    prog.pack_stats["shared"] += 1
+            else:
+                t = holder[0] if holder[0] is not None else torch.empty(wbytes, dtype=torch.uint8, device=dev)
+                pack_call(_ptr(wt), _ptr(t))
+            wt.record_stream(prog.ctx.stream)
+            if holder[0] is not t:
+                prog._weights_moved = prog._weights_moved or holder[0] is not None
+                holder[0] = t
+
+        self.pack_fns.append(pack)
+        self._pack_meta.append(dict(plan=plan, weight_fn=weight_fn, holder=holder, fn=pack))
+        return holder
+
+    def _norm_in_pass(self, x1: Act, norm_in, synced: bool = False):
+        """The `norm_in` of conv(): x1 <- silu?(gn(x1)) + tbias in place, as a pass of its own ahead of the conv."""
+        slot, gn, silu, tb = norm_in
+        kw_tb = {} if tb is None else dict(tbias=tb[0], tbias_off=tb[1], tbias_stride=tb[2], step_ptr=tb[3])
+        self.gn_apply(x1, slot, gn, silu_pre=silu, out=x1, synced=synced, **kw_tb)
+
+    def _conv_bias(self, bias_fn) -> Optional[torch.Tensor]:
+        if bias_fn is None:
+            return None
+        return self.dev_f32(bias_fn, parts=getattr(bias_fn, "parts", None), scale=getattr(bias_fn, "scale", 1.0))
+
+    def _count_conv(self, name: str, fl: float):
+        self.flops += fl
+        self.conv_flops.append((name, fl))
+
+    def _conv_stats(self, tiles: int, tps: int, cpad: int, nclass: int, off: int = 0) -> dict:
+        """The handle gn_finalize takes for the column sums a `want_stats` conv of `tiles` tiles writes, `off` floats into
+        the program's column-sum buffer."""
+        self._colsum_need = max(self._colsum_need, off + 2 * tiles * cpad)
+        return dict(tps=tps, cpad=cpad, nclass=nclass)
+
+    def _conv_target(self, co: ConvOut, x1: Act, cout: int, dims, out: Optional[Act], f32_out, f32_strides,
+                     ext_lo: int = 0) -> Optional[Act]:
+        """Point `co` at the conv's output: the fp32 tensor `f32_out` with element strides (n, c, d, h, w), or an Act --
+        `out`, or a new one of `dims` = (d, h, w) -- written from `ext_lo` slices below its own ones.  Returns the Act."""
+        if f32_out is not None:
+            co.y = f32_out.data_ptr()
+            co.mode = 1
+            co.sn, co.sc, co.sd, co.sh, co.sw = [int(v) for v in f32_strides]
+            return None
+        if out is None:
+            out = self.act(x1.n, cout, *dims, halo=x1.halo)
+        co.y = self.ext_ptr(out, ext_lo).value
+        co.mode = 0
+        co.cout_stride = out.c
+        co.c_off = 0
+        return out
+
+    def _conv_setup(self, name: str, desc: ConvDesc, weight_fn, cin_w: Optional[int],
+                    stream_tail: bool = False) -> _ConvPlan:
+        """Everything one launch of ctsi_conv_fwd needs besides its operands: the plan of `desc`, what the emitters read
+        of it, its split-K workspace and its weight image; counts the layer's flops under `name`."""
+        lib, sptr = self.lib, self.ctx.sptr
+        plan = C.c_void_p()
+        lib.conv_plan_create(C.byref(plan), C.byref(desc))
+        self.plans.append(plan)
+        if cin_w is not None:
+            lib.conv_plan_set_weight_cin(plan, cin_w)
+        if stream_tail:
+            lib.conv_plan_set_stream_tail(plan, 1)
+        do, ho, wo, bm, bn, mode = (C.c_int() for _ in range(6))
+        lib.conv_plan_out_dims(plan, C.byref(do), C.byref(ho), C.byref(wo))
+        lib.conv_plan_config(plan, C.byref(bm), C.byref(bn), C.byref(mode))
+        wbytes = lib.conv_plan_weight_bytes(plan)
+        sig = _pack_sig(lib, plan, desc.transposed, (desc.kd, desc.kh, desc.kw), (desc.sh, desc.sw), desc.c1, desc.c2,
+                        desc.cout, cin_w)
+        holder = self._weight_image(weight_fn, sig, wbytes, lambda w, t: lib.conv_plan_pack_weights(plan, w, t, sptr), plan)
+        fl = lib.conv_plan_flops(plan)
+        self._count_conv(name, fl)
+        workspace = self._conv_workspace(plan)
+        return _ConvPlan(plan, desc, (do.value, ho.value, wo.value), wbytes, mode.value,
+                         _conv_label(bm.value, bn.value, mode.value, desc, bool(workspace)), fl, lib.conv_plan_tiles(plan),
+                         lib.conv_plan_tiles_per_sample(plan), lib.conv_plan_cout_pad(plan), workspace, holder)
+
+    def _conv_launch(self, name: str, cp: _ConvPlan, x1p, x2p, bias, co: ConvOut, *, colsum_off: Optional[int] = None,
+                     gn_slot: Optional[int] = None, audit: Optional[dict] = None):
+        """Emit ctsi_conv_fwd of the layer set up as `cp` on the input views `x1p` / `x2p`, into the target `co` describes.
+        `colsum_off`: where its column sums go (floats into the column-sum buffer; None: it writes none); `gn_slot`: the
+        statistics the fused GroupNorm tail of `co` reads."""
+        lib, sptr, prog, plan, holder, desc = self.lib, self.ctx.sptr, self, cp.plan, cp.holder, cp.desc
+        co.workspace = cp.workspace
+        self.keep.append(co)
+        bp = _ptr(bias)
+
+        def run():
+            co.colsum = 0 if colsum_off is None else prog._colsum.data_ptr() + colsum_off * 4
+            if gn_slot is not None:
+                co.gn_sums = prog._gn_sums.data_ptr() + gn_slot * 8
+            lib.conv_fwd(plan, x1p, x2p, _ptr(holder[0]), bp, C.byref(co), sptr)
+
+        # algorithmic HBM bytes: inputs + weights + output (+ the tensor a fused GroupNorm tail reads), each once
+        do, ho, wo = cp.out_dims
+        out_elems = float(desc.n * do * ho * wo * desc.cout)
+        alg = (2.0 * desc.n * desc.di * desc.hi * desc.wi * (desc.c1 + desc.c2) + float(cp.wbytes)
+               + (4.0 if co.mode == 1 else 2.0) * out_elems + (2.0 * out_elems if co.gn_x else 0.0))
+        self._emit(run, name, cp.flops, cp.kernel, alg_bytes=alg, audit=audit)
+
     def conv(self, name: str, weight_fn, bias_fn, x1: Act, x2: Optional[Act], *, transposed=False,
              k=(3, 3, 3), s=(1, 1), p=(1, 1, 1), cout: int, cin_w: Optional[int] = None,
              out: Optional[Act] = None, want_stats=False, f32_out: Optional[torch.Tensor] = None,
              f32_strides: Optional[Sequence[int]] = None, act: int = 0, fuse_gn=None, ext_out: bool = False,
              norm_in=None, audit: Optional[dict] = None):
-        """Emit one convolution.  weight_fn/bias_fn return the *current* fp32 parameter tensors
-        (possibly derived, e.g. scaled or pre-multiplied).  Returns (out_act, stats_handle).
-        `fuse_gn` = (h: Act, slot, gn: nn.GroupNorm, silu: bool): the epilogue stores silu?(gn(h) + conv result)
-        instead of the conv result (ctsi_conv_out.gn_x; h may be the output buffer itself).
+        """Emit one convolution of [x1 | x2] (x2: the second half of a channel concatenation, never materialised).
+        Returns (out_act, stats_handle).  The parameters both precisions take (engine_f32._F32Ops.conv is the fp32 form):
+        `weight_fn` / `bias_fn` return the *current* fp32 parameter tensors (possibly derived, e.g. scaled or
+            pre-multiplied; bias_fn may be None); `cin_w`: input channels the weights carry when the activation is padded.
+        `transposed`, `k`, `s` (h, w), `p`, `cout`: the layer's geometry.
+        `out`: write into this Act instead of a new one.  `f32_out` + `f32_strides` (element strides n, c, d, h, w): store
+            fp32 into that tensor instead (out_act is None).  `act`: the epilogue's activation (1 = tanh).
+        `want_stats`: also write per-tile column sums; the stats handle is what gn_finalize takes.
         `norm_in` = (slot, gn: nn.GroupNorm, silu: bool, tb) with tb = None or (tbias, tbias_off, tbias_stride, step_ptr):
-        x1 is the RAW output of the previous conv and this conv's input is silu?(gn(x1)) + tbias: the normalisation is
-        emitted as its own in-place pass first (depth-sharded: its statistics travel with the raw boundary slices in one
-        sync point), so x1 must not be used raw afterwards.  (A normalise-on-load variant of the 512-voxel kernel that
-        applied it to the staged tile in LDS was bit-identical but slower: csrc/experiments/conv3_halo_m512.hip.)"""
-        lib = self.lib
+            x1 is the RAW output of the previous conv and this conv's input is silu?(gn(x1)) + tbias: the normalisation is
+            emitted as its own in-place pass first (depth-sharded: its statistics travel with the raw boundary slices in
+            one sync point), so x1 must not be used raw afterwards.  (A normalise-on-load variant of the 512-voxel kernel
+            that applied it to the staged tile in LDS was bit-identical but slower: csrc/experiments/conv3_halo_m512.hip.)
+        bf16 only (the fp32 form rejects them):
+        `fuse_gn` = (h: Act, slot, gn: nn.GroupNorm, silu: bool): the epilogue stores silu?(gn(h) + conv result) instead of
+            the conv result (ctsi_conv_out.gn_x; h may be the output buffer itself).
+        `ext_out`: a pointwise conv over inputs with valid halo slices covers them too.
+        `audit`: replaces the op's audit record (the training programs' data-gradient convs).
+        fp32 only: `residual` (an fp32 Act of the output's shape), added in the epilogue."""
         nin_synced = False
         if norm_in is not None and self.shard is not None and x1.halo:
             # depth-sharded: statistics + RAW boundary slices in one sync point, whichever way the normalisation happens
@@ -542,90 +701,25 @@ class Program:
             if deep or x1.dirty or (x2 is not None and x2.dirty):
                 raise CtsiError("internal: ext_out needs a pointwise conv over inputs with valid halo slices")
             ext_lo, ext_d = self.ext(x1)
-        di = x1.d + 2 if deep else ext_d
-        desc = ConvDesc(int(transposed), k[0], k[1], k[2], s[0], s[1], p[0], p[1], p[2], x1.n, x1.c,
-                        0 if x2 is None else x2.c, cout, di, x1.h, x1.w, 1 if deep else 0)
-        plan = C.c_void_p()
-        lib.conv_plan_create(C.byref(plan), C.byref(desc))
-        self.plans.append(plan)
-        if cin_w is not None:
-            lib.conv_plan_set_weight_cin(plan, cin_w)
-        if fuse_gn is not None and tuple(k) == (1, 1, 1) and f32_out is None and not want_stats and act == 0:
-            # the ResBlock tails are HBM-bound passes: the streaming kernel where the layer qualifies (csrc/conv1_stream.hip)
-            lib.conv_plan_set_stream_tail(plan, 1)
         if norm_in is not None:
-            nslot, ngn, nsilu, ntb = norm_in      # normalise in place, then a plain conv
-            kw_tb = {} if ntb is None else dict(tbias=ntb[0], tbias_off=ntb[1], tbias_stride=ntb[2], step_ptr=ntb[3])
-            self.gn_apply(x1, nslot, ngn, silu_pre=nsilu, out=x1, synced=nin_synced, **kw_tb)
-            norm_in = None
-        do, ho, wo = C.c_int(), C.c_int(), C.c_int()
-        lib.conv_plan_out_dims(plan, C.byref(do), C.byref(ho), C.byref(wo))
-        do, ho, wo = do.value, ho.value, wo.value
-        wbytes = lib.conv_plan_weight_bytes(plan)
-        bias = (self.dev_f32(bias_fn, parts=getattr(bias_fn, "parts", None), scale=getattr(bias_fn, "scale", 1.0))
-                if bias_fn is not None else None)
-        sptr = self.ctx.sptr
-        bm, bn, mode = C.c_int(), C.c_int(), C.c_int()
-        lib.conv_plan_config(plan, C.byref(bm), C.byref(bn), C.byref(mode))
-        sig = _pack_sig(lib, plan, transposed, k, s, x1.c, 0 if x2 is None else x2.c, cout, cin_w)
-        holder: List[Optional[torch.Tensor]] = [None]
-        prog = self
-
-        def pack():
-            wt = weight_fn().detach().to(device=prog.ctx.device, dtype=torch.float32).contiguous()
-            if prog.weight_cache:
-                cache = _PACKED.setdefault(prog.ctx.device.index, weakref.WeakValueDictionary())
-                key = (sig, _content_key(wt))
-                t = cache.get(key)
-                if t is None:
-                    t = torch.empty(wbytes, dtype=torch.uint8, device=prog.ctx.device)
-                    lib.conv_plan_pack_weights(plan, _ptr(wt), _ptr(t), sptr)
-                    cache[key] = t
-                    prog.pack_stats["packed"] += 1
-                else:
-                    prog.pack_stats["shared"] += 1
-            else:
-                t = holder[0] if holder[0] is not None else torch.empty(wbytes, dtype=torch.uint8, device=prog.ctx.device)
-                lib.conv_plan_pack_weights(plan, _ptr(wt), _ptr(t), sptr)
-            wt.record_stream(prog.ctx.stream)
-            if holder[0] is not t:
-                prog._weights_moved = prog._weights_moved or holder[0] is not None
-                holder[0] = t
-
-        self.pack_fns.append(pack)
-        self._pack_meta.append(dict(plan=plan, weight_fn=weight_fn, holder=holder, fn=pack))
-        fl = lib.conv_plan_flops(plan)
-        self.flops += fl
-        self.conv_flops.append((name, fl))
-
-        stats = None
-        colsum_ptr = 0
-        if want_stats:
-            tiles = lib.conv_plan_tiles(plan)
-            cpad = lib.conv_plan_cout_pad(plan)
-            self._colsum_need = max(self._colsum_need, 2 * tiles * cpad)
-            stats = dict(tps=lib.conv_plan_tiles_per_sample(plan), cpad=cpad,
-                         nclass=4 if transposed else 1)
+            self._norm_in_pass(x1, norm_in, nin_synced)
+        bias = self._conv_bias(bias_fn)
+        desc = ConvDesc(int(transposed), k[0], k[1], k[2], s[0], s[1], p[0], p[1], p[2], x1.n, x1.c,
+                        0 if x2 is None else x2.c, cout, x1.d + 2 if deep else ext_d, x1.h, x1.w, 1 if deep else 0)
+        # the ResBlock tails are HBM-bound passes: the streaming kernel where the layer qualifies (csrc/conv1_stream.hip)
+        tail = fuse_gn is not None and tuple(k) == (1, 1, 1) and f32_out is None and not want_stats and act == 0
+        cp = self._conv_setup(name, desc, weight_fn, cin_w, stream_tail=tail)
+        do, ho, wo = cp.out_dims
+        stats = self._conv_stats(cp.tiles, cp.tps, cp.cpad, 4 if transposed else 1) if want_stats else None
         co = ConvOut()
-        co.workspace = self._conv_workspace(plan)
-        if f32_out is not None:
-            co.y = f32_out.data_ptr()
-            co.mode = 1
-            co.sn, co.sc, co.sd, co.sh, co.sw = [int(v) for v in f32_strides]
-            out_act = None
-        else:
-            if out is None:
-                out = self.act(x1.n, cout, do - (ext_d - x1.d), ho, wo, halo=x1.halo)
-            out.dirty = not ext_out
-            co.y = self.ext_ptr(out, ext_lo).value
-            co.mode = 0
-            co.cout_stride = out.c
-            co.c_off = 0
-            out_act = out
+        out_act = self._conv_target(co, x1, cout, (do - (ext_d - x1.d), ho, wo), out, f32_out, f32_strides, ext_lo)
+        if out_act is not None:
+            out_act.dirty = not ext_out
         co.act = act
+        prog = self
         if fuse_gn is not None:
             gh, gslot, gmod, gsilu = fuse_gn
-            if f32_out is not None or want_stats or (gh.n, gh.c, gh.d, gh.h, gh.w) != (x1.n, cout, out.d, ho, wo):
+            if f32_out is not None or want_stats or (gh.n, gh.c, gh.d, gh.h, gh.w) != (x1.n, cout, out_act.d, ho, wo):
                 raise CtsiError("internal: fused GroupNorm tail needs a bf16 output of the normalised tensor's shape")
             ggamma = self.dev_f32(lambda: gmod.weight)
             gbeta = self.dev_f32(lambda: gmod.bias)
@@ -635,37 +729,20 @@ class Program:
             co.gn_groups, co.gn_eps = gmod.num_groups, float(gmod.eps)
             co.gn_count = (cout // gmod.num_groups) * d_stat * gh.h * gh.w
             co.gn_silu = int(gsilu)
-        self.keep.append(co)
-        x1p = x1.fp if deep else self.ext_ptr(x1, ext_lo)
-        x2p = C.c_void_p(0) if x2 is None else (x2.fp if deep else self.ext_ptr(x2, ext_lo))
-        bp = _ptr(bias)
-
-        gn_slot = fuse_gn[1] if fuse_gn is not None else None
-
-        def run():
-            co.colsum = prog._colsum.data_ptr() if want_stats else 0
-            if gn_slot is not None:
-                co.gn_sums = prog._gn_sums.data_ptr() + gn_slot * 8
-            lib.conv_fwd(plan, x1p, x2p, _ptr(holder[0]), bp, C.byref(co), sptr)
-
-        form = "t" if transposed else ("d" if tuple(s) == (2, 2) else "")        # t: ConvTranspose form, d: Downsample form,
-        kernel = "conv_mfma_%dx%d_m%d%s%s" % (bm.value, bn.value, mode.value, form if mode.value == 9 else "",
-                                              "s" if co.workspace else "")      # s: split-K form
-        cin_all = x1.c + (0 if x2 is None else x2.c)
-        alg = (2.0 * x1.n * di * x1.h * x1.w * cin_all + float(wbytes)
-               + (4.0 if f32_out is not None else 2.0) * x1.n * do * ho * wo * cout
-               + (2.0 * x1.n * do * ho * wo * cout if fuse_gn is not None else 0.0))
         if audit is not None:
             audit = dict(audit, out=out_act)
         else:
             audit = dict(kind="conv_fwd", x1=x1, x2=x2, weight=weight_fn, bias=bias, transposed=bool(transposed), k=tuple(k),
                          s=tuple(s), p=tuple(p), cout=cout, cin_w=cin_w, act=act, out=out_act, f32_out=f32_out,
                          f32_strides=None if f32_out is None else tuple(int(v) for v in f32_strides), stats=stats,
-                         colsum=(lambda: prog._colsum) if want_stats else None, stream_tail=mode.value == 10, fuse_gn=None)
+                         colsum=(lambda: prog._colsum) if want_stats else None, stream_tail=cp.mode == 10, fuse_gn=None)
             if fuse_gn is not None:
                 audit["fuse_gn"] = dict(x=gh, slot=gslot, sums=lambda: prog._gn_sums, gamma=ggamma, beta=gbeta,
                                         groups=gmod.num_groups, eps=float(gmod.eps), count=int(co.gn_count), silu=bool(gsilu))
-        self._emit(run, name, fl, kernel, alg_bytes=alg, audit=audit)
+        x1p = x1.fp if deep else self.ext_ptr(x1, ext_lo)
+        x2p = C.c_void_p(0) if x2 is None else (x2.fp if deep else self.ext_ptr(x2, ext_lo))
+        self._conv_launch(name, cp, x1p, x2p, bias, co, colsum_off=0 if want_stats else None,
+                          gn_slot=fuse_gn[1] if fuse_gn is not None else None, audit=audit)
         return out_act, stats
 
     def _conv_overlapped(self, name, weight_fn, bias_fn, x1: Act, x2: Optional[Act], k, p, cout, cin_w, want_stats):
@@ -676,13 +753,13 @@ class Program:
             interior  input = the d own slices taken as a halo'd tensor   -> output slices 1 .. d-2
             lower     input = [lo halo, own 0, own 1]                     -> output slice 0
             upper     input = [own d-2, own d-1, hi halo]                 -> output slice d-1"""
-        lib, sptr, prog, ctx = self.lib, self.ctx.sptr, self, self.ctx
+        lib, sptr = self.lib, self.ctx.sptr
         spec = self.shard
-        cs = ctx.comm_stream_ptr()
+        cs = self.ctx.comm_stream_ptr()
         ev_fork, ev_join = C.c_void_p(), C.c_void_p()
         lib.event_create(C.byref(ev_fork))
         lib.event_create(C.byref(ev_join))
-        self._events = getattr(self, "_events", []) + [ev_fork, ev_join]     # destroyed with the program
+        self._events += [ev_fork, ev_join]
         todo = [a for a in (x1, x2) if a is not None and a.halo and a.dirty]
         sl = [self._slices(a) for a in todo]
         for a in todo:
@@ -695,76 +772,33 @@ class Program:
                 spec.comm.exchange(spec.rank, lo_own, hi_own, lo_halo, hi_halo, sptr=cs)
             lib.event_record(ev_join, cs)
 
+        def run_join():
+            lib.stream_wait_event(sptr, ev_join)            # halos have landed: the boundary slices may be computed
+
         self._emit(run_fork, "halo.exchange.async", 0.0, "comm")
         d, se_in1 = x1.d, x1.slice_elems * 2
-        se_in2 = 0 if x2 is None else x2.slice_elems * 2
+        c2, se_in2 = (0, 0) if x2 is None else (x2.c, x2.slice_elems * 2)
         out = self.act(x1.n, cout, d, x1.h, x1.w, halo=x1.halo)
         out.dirty = True
         se_out = out.slice_elems * 2
-        bias = (self.dev_f32(bias_fn, parts=getattr(bias_fn, "parts", None), scale=getattr(bias_fn, "scale", 1.0))
-                if bias_fn is not None else None)
+        bias = self._conv_bias(bias_fn)
         parts, col_off = [], 0
         views = [("interior", d, x1.ip.value, 0 if x2 is None else x2.ip.value, out.ip.value + se_out),
                  ("lower", 3, x1.fp.value, 0 if x2 is None else x2.fp.value, out.ip.value),
                  ("upper", 3, x1.ip.value + (d - 2) * se_in1, 0 if x2 is None else x2.ip.value + (d - 2) * se_in2,
                   out.ip.value + (d - 1) * se_out)]
-        for vi, (tag, di, p1, p2, py) in enumerate(views):
-            if vi == 1:
-                def run_join():
-                    lib.stream_wait_event(sptr, ev_join)    # halos have landed: the boundary slices may be computed
+        for tag, di, p1, p2, py in views:
+            if tag == "lower":
                 self._emit(run_join, "halo.join", 0.0, "comm.join")
-            desc = ConvDesc(0, k[0], k[1], k[2], 1, 1, p[0], p[1], p[2], x1.n, x1.c, 0 if x2 is None else x2.c, cout, di,
-                            x1.h, x1.w, 1)
-            plan = C.c_void_p()
-            lib.conv_plan_create(C.byref(plan), C.byref(desc))
-            self.plans.append(plan)
-            if cin_w is not None:
-                lib.conv_plan_set_weight_cin(plan, cin_w)
-            wbytes = lib.conv_plan_weight_bytes(plan)
-            bm, bn, mode = C.c_int(), C.c_int(), C.c_int()
-            lib.conv_plan_config(plan, C.byref(bm), C.byref(bn), C.byref(mode))
-            sig = _pack_sig(lib, plan, 0, k, (1, 1), x1.c, 0 if x2 is None else x2.c, cout, cin_w)
-            holder: List[Optional[torch.Tensor]] = [None]
-
-            def pack(plan=plan, sig=sig, wbytes=wbytes, holder=holder):
-                wt = weight_fn().detach().to(device=prog.ctx.device, dtype=torch.float32).contiguous()
-                cache = _PACKED.setdefault(prog.ctx.device.index, weakref.WeakValueDictionary())
-                key = (sig, _content_key(wt))
-                t = cache.get(key)
-                if t is None:
-                    t = torch.empty(wbytes, dtype=torch.uint8, device=prog.ctx.device)
-                    lib.conv_plan_pack_weights(plan, _ptr(wt), _ptr(t), sptr)
-                    cache[key] = t
-                    prog.pack_stats["packed"] += 1
-                else:
-                    prog.pack_stats["shared"] += 1
-                wt.record_stream(prog.ctx.stream)
-                if holder[0] is not t:
-                    prog._weights_moved = prog._weights_moved or holder[0] is not None
-                    holder[0] = t
-
-            self.pack_fns.append(pack)
-            fl = lib.conv_plan_flops(plan)
-            self.flops += fl
-            self.conv_flops.append((name + "." + tag, fl))
-            co = ConvOut()
-            co.workspace = self._conv_workspace(plan)
-            co.y, co.mode, co.cout_stride, co.c_off = py, 0, cout, 0
-            self.keep.append(co)
-            off = col_off
+            desc = ConvDesc(0, k[0], k[1], k[2], 1, 1, p[0], p[1], p[2], x1.n, x1.c, c2, cout, di, x1.h, x1.w, 1)
+            cp = self._conv_setup(name + "." + tag, desc, weight_fn, cin_w)
             if want_stats:
-                tiles, cpad = lib.conv_plan_tiles(plan), lib.conv_plan_cout_pad(plan)
-                parts.append(dict(tps=lib.conv_plan_tiles_per_sample(plan), cpad=cpad, nclass=1, off=off))
-                col_off += 2 * tiles * cpad
-            bp = _ptr(bias)
-
-            def run(plan=plan, co=co, p1=p1, p2=p2, holder=holder, off=off):
-                co.colsum = (prog._colsum.data_ptr() + off * 4) if want_stats else 0
-                lib.conv_fwd(plan, C.c_void_p(p1), C.c_void_p(p2), _ptr(holder[0]), bp, C.byref(co), sptr)
-
-            self._emit(run, name + "." + tag, fl, "conv_mfma_%dx%d_m%d" % (bm.value, bn.value, mode.value))
-        if want_stats:
-            self._colsum_need = max(self._colsum_need, col_off)
+                parts.append(dict(self._conv_stats(cp.tiles, cp.tps, cp.cpad, 1, col_off), off=col_off))
+            co = ConvOut()
+            co.y, co.mode, co.cout_stride, co.c_off = py, 0, cout, 0
+            self._conv_launch(name + "." + tag, cp, C.c_void_p(p1), C.c_void_p(p2), bias, co,
+                              colsum_off=col_off if want_stats else None)
+            col_off += 2 * cp.tiles * cp.cpad
         return out, (dict(parts=parts) if want_stats else None)
 
     # ---- GroupNorm ----------------------------------------------------------------------------------------
@@ -1059,7 +1093,7 @@ class Program:
                 self.lib.graph_destroy(self.graph)
             for p in self.plans:
                 self.lib.conv_plan_destroy(p)
-            for ev in getattr(self, "_events", ()):
+            for ev in self._events:
                 self.lib.event_destroy(ev)
             if self._fast and self._fast.get("graph") is not None:
                 self.lib.graph_destroy(self._fast["graph"])

@@ -19,14 +19,12 @@ call on this path: torch allocates and copies.
 from __future__ import annotations
 
 import ctypes as C
-import weakref
-from typing import List, Optional, Tuple
+from typing import Optional, Tuple
 
 import torch
 import torch.nn as nn
 
-from .engine import (_PACKED, Act, Ctx, UNetProgram, VAEDecodeProgram, VAEEncodeProgram, _content_key,
-                     _ptr)
+from .engine import Act, Ctx, UNetProgram, VAEDecodeProgram, VAEEncodeProgram, _ptr
 from .lib import ConvDesc, ConvOut, CtsiError
 
 PRECISIONS = ("bf16", "fp32")
@@ -61,8 +59,8 @@ class _F32Ops:
              p=(1, 1, 1), cout: int, cin_w: Optional[int] = None, out: Optional[Act] = None, want_stats=False,
              f32_out: Optional[torch.Tensor] = None, f32_strides=None, act: int = 0, fuse_gn=None, ext_out: bool = False,
              norm_in=None, residual: Optional[Act] = None):
-        """engine.Program.conv on ctsi_conv_f32_fwd.  `norm_in` is applied as its own in-place pass first; `residual`
-        (fp32 Act of the output's shape) is added in the epilogue.  The fused GroupNorm tail has no fp32 form."""
+        """engine.Program.conv (which documents the parameters) on ctsi_conv_f32_fwd.  `residual` (fp32 Act of the output's
+        shape) is added in the epilogue.  The fused GroupNorm tail has no fp32 form."""
         lib, prog = self.lib, self
         if fuse_gn is not None or ext_out:
             raise CtsiError("internal: the fused GroupNorm tail / halo-extended outputs are bf16-path features")
@@ -72,9 +70,7 @@ class _F32Ops:
         if x2 is not None and (x2.n, x2.d, x2.h, x2.w) != (x1.n, x1.d, x1.h, x1.w):
             raise CtsiError("internal: concatenated sources of different shapes")
         if norm_in is not None:
-            nslot, ngn, nsilu, ntb = norm_in
-            kw_tb = {} if ntb is None else dict(tbias=ntb[0], tbias_off=ntb[1], tbias_stride=ntb[2], step_ptr=ntb[3])
-            self.gn_apply(x1, nslot, ngn, silu_pre=nsilu, out=x1, **kw_tb)
+            self._norm_in_pass(x1, norm_in)
         desc = ConvDesc(int(transposed), k[0], k[1], k[2], s[0], s[1], p[0], p[1], p[2], x1.n, x1.c, c2, cout, x1.d, x1.h,
                         x1.w, 0)
         if not lib.conv_f32_supported(C.byref(desc)):
@@ -85,54 +81,18 @@ class _F32Ops:
                               C.byref(cpad))
         do, ho, wo, tps, ncls, cpad = do.value, ho.value, wo.value, tps.value, ncls.value, cpad.value
         wbytes = lib.conv_f32_weight_bytes(C.byref(desc))
-        bias = (self.dev_f32(bias_fn, parts=getattr(bias_fn, "parts", None), scale=getattr(bias_fn, "scale", 1.0))
-                if bias_fn is not None else None)
+        bias = self._conv_bias(bias_fn)
         sptr = self.ctx.sptr
-        sig = _f32_pack_sig(desc, cpad, wbytes)
-        holder: List[Optional[torch.Tensor]] = [None]
-
-        def pack():
-            wt = weight_fn().detach().to(device=prog.ctx.device, dtype=torch.float32).contiguous()
-            cache = _PACKED.setdefault(prog.ctx.device.index, weakref.WeakValueDictionary())
-            key = (sig, _content_key(wt))
-            t = cache.get(key)
-            if t is None:
-                t = torch.empty(wbytes, dtype=torch.uint8, device=prog.ctx.device)
-                lib.conv_f32_pack_weights(C.byref(desc), _ptr(wt), _ptr(t), sptr)
-                cache[key] = t
-                prog.pack_stats["packed"] += 1
-            else:
-                prog.pack_stats["shared"] += 1
-            wt.record_stream(prog.ctx.stream)
-            if holder[0] is not t:
-                prog._weights_moved = prog._weights_moved or holder[0] is not None
-                holder[0] = t
-
-        self.pack_fns.append(pack)
+        holder = self._weight_image(weight_fn, _f32_pack_sig(desc, cpad, wbytes), wbytes,
+                                    lambda w, t: lib.conv_f32_pack_weights(C.byref(desc), w, t, sptr))
         fl = lib.conv_f32_flops(C.byref(desc))
-        self.flops += fl
-        self.conv_flops.append((name, fl))
-        stats = None
-        if want_stats:
-            self._colsum_need = max(self._colsum_need, 2 * ncls * x1.n * tps * cpad)
-            stats = dict(tps=tps, cpad=cpad, nclass=ncls)
+        self._count_conv(name, fl)
+        stats = self._conv_stats(ncls * x1.n * tps, tps, cpad, ncls) if want_stats else None
         co = ConvOut()
-        if f32_out is not None:
-            co.y = f32_out.data_ptr()
-            co.mode = 1
-            co.sn, co.sc, co.sd, co.sh, co.sw = [int(v) for v in f32_strides]
-            out_act = None
-        else:
-            if out is None:
-                out = self.act(x1.n, cout, do, ho, wo)
-            if (out.n, out.c, out.d, out.h, out.w) != (x1.n, cout, do, ho, wo):
-                raise CtsiError("internal: conv output buffer of the wrong shape")
-            co.y = out.t.data_ptr()
-            co.mode = 0
-            co.cout_stride = out.c
-            co.c_off = 0
-            out_act = out
-        if residual is not None and (f32_out is not None or residual.t.numel() != out.t.numel()):
+        out_act = self._conv_target(co, x1, cout, (do, ho, wo), out, f32_out, f32_strides)
+        if out_act is not None and (out_act.n, out_act.c, out_act.d, out_act.h, out_act.w) != (x1.n, cout, do, ho, wo):
+            raise CtsiError("internal: conv output buffer of the wrong shape")
+        if residual is not None and (f32_out is not None or residual.t.numel() != out_act.t.numel()):
             raise CtsiError("internal: the residual must have the NDHWC output's shape")
         co.act = act
         self.keep.append(co)
