@@ -220,6 +220,17 @@ int ctsi_attn_broadcast_add(const void* x_bf16, const void* p_bf16, const float*
 int ctsi_attn_softmax_rowsum(const void* qk_bf16, float* rowsum, int n, int c, int d, int h, int w,
                              int heads, void* stream);
 
+/* True depth attention (attention_mode='softmax'): A[q] = sum_k softmax_k(q.k / sqrt(hd)) v_k over the d depth positions of one
+ * (sample, position, head).  qkv = bf16 NDHWC with 3*c channels [q | k | v], heads split inside each third (as the reference's
+ * 'b (head c) t h w'); out = bf16 NDHWC with c channels.  bf16 MFMAs with fp32 accumulation, fp32 softmax; the probabilities
+ * are rounded to bf16 for the P V product.  Head dimension c / heads in {8, 16, 32, 64, 128}; d * (2 * hd + 32) <= 65536 bytes
+ * of LDS per item (backward: d * (4 * hd + 76)); anything else is CTSI_ERR_INVALID.  csrc/attention_core.hip. */
+int ctsi_attn_core(const void* qkv_bf16, void* out_bf16, int n, int c, int d, int h, int w, int heads, void* stream);
+/* its backward: dqkv (bf16, 3*c channels, every element written) from the saved qkv and dA = dLoss/dA (bf16, c channels);
+ * S and P are recomputed.  dV = P^T dA, dP = dA V^T, dS = P o (dP - rowsum(P o dP)), dQ = dS K / sqrt(hd), dK = dS^T Q / sqrt(hd). */
+int ctsi_attn_core_bwd(const void* qkv_bf16, const void* da_bf16, void* dqkv_bf16, int n, int c, int d, int h, int w, int heads,
+                       void* stream);
+
 /* time embedding (models/unet3d.py:18-48 and the per-block Linear of :88-91, 123-125) ------- *
  * temb = Linear2(SiLU(Linear1(sincos(t))));  tbias[r][o] = W_all[o] . SiLU(temb[r]) + b_all[o]
  * for the concatenation of every ResBlock's time_mlp.1 (`total_out` rows of W_all).

@@ -248,7 +248,8 @@ class GaussianDiffusion(nn.Module):
                                       or tuple(cond_keep.shape) != (z_0.shape[0],)):
             raise ValueError(f"cond_keep must be a bool tensor of shape ({z_0.shape[0]},)")
         from .train_engine import UNetTrainProgram, train_step
-        from .engine import Ctx, cached_program
+        from .engine import Ctx, cached_program, check_attention_mode
+        mode = check_attention_mode(getattr(model, "attention_mode", "fast"))
         if not z_0.is_cuda:
             raise CtsiError("training_loss runs on the HIP engine: move the tensors to a ROCm device")
         B, L, d, h, w = z_0.shape
@@ -284,7 +285,8 @@ class GaussianDiffusion(nn.Module):
         ctx = Ctx.get(device)
         with ctx.scope():
             # the epsilon key is what it always was; a v program (q_sample_v, a target buffer) has its own
-            key = ("unet-train", ctx.device.index, B, d, h, w) + ((self.prediction_type,) if v_pred else ())
+            key = ("unet-train", ctx.device.index, B, d, h, w) + ((self.prediction_type,) if v_pred else ()) + (
+                () if mode == "fast" else ("attn-" + mode,))
             kw = dict(prediction=self.prediction_type) if v_pred else {}
             prog = cached_program(model, key, lambda: UNetTrainProgram(ctx, model, B, d, h, w, **kw))
             prog.set_diffusion(self)

@@ -23,6 +23,7 @@ from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 import torch
 import torch.nn as nn
 
+from .attention import ATTENTION_MODES, check_attention_mode, emit_softmax_attention
 from .lib import ConvDesc, ConvOut, CtsiError, get_lib
 from .prediction import add_pred_to_eps, check_prediction_type
 
@@ -924,8 +925,15 @@ class Program:
                            ext_out=self.shard is not None)
         return out
 
+    def attention_softmax(self, m, x: Act, save: bool = False):
+        """TemporalAttention as true attention over depth (attention.py); returns (y, saved)."""
+        return emit_softmax_attention(self, m, x, save)
+
     def attention(self, m, x: Act, mode: str = "fast") -> Act:
-        """TemporalAttention (models/unet3d.py:163-194), see csrc/attention.hip."""
+        """TemporalAttention (models/unet3d.py:163-194), see csrc/attention.hip; mode 'softmax': attention_softmax."""
+        check_attention_mode(mode)
+        if mode == "softmax":
+            return self.attention_softmax(m, x)[0]
         lib, sptr, prog = self.lib, self.ctx.sptr, self
         n, c, d, h, w = x.n, x.c, x.d, x.h, x.w
         dev = self.ctx.device
@@ -1167,7 +1175,7 @@ class UNetProgram(Program):
         L = unet.latent_dim
         self.L = L
         dev = ctx.device
-        self.attention_mode = attention_mode
+        self.attention_mode = check_attention_mode(attention_mode)
         self.max_rows = max_rows
         halo = 0 if shard is None else 1
         self.xin, self.xin2 = self._input_acts(n, d, h, w, halo)

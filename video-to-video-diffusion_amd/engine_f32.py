@@ -13,7 +13,7 @@ capture and launch machinery (one captured hipGraph per sampler step); only the 
   sampler       the `_f32` entry of every engine.SAMPLER_STEPS row (the U-Net's z input written in fp32): the update
                 is engine.UNetProgram.add_sampler_step, only the input slice differs (_sampler_zin)
 
-Not supported here (CtsiError): depth sharding, attention_mode='exact', training.  There is no torch conv, MIOpen or BLAS
+Not supported here (CtsiError): depth sharding, attention_mode='exact' / 'softmax', training.  There is no torch conv, MIOpen or BLAS
 call on this path: torch allocates and copies.
 """
 from __future__ import annotations
@@ -24,7 +24,7 @@ from typing import Optional, Tuple
 import torch
 import torch.nn as nn
 
-from .engine import Act, Ctx, UNetProgram, VAEDecodeProgram, VAEEncodeProgram, _ptr
+from .engine import Act, Ctx, UNetProgram, VAEDecodeProgram, VAEEncodeProgram, _ptr, check_attention_mode
 from .lib import ConvDesc, ConvOut, CtsiError
 
 PRECISIONS = ("bf16", "fp32")
@@ -182,7 +182,7 @@ class _F32Ops:
         """TemporalAttention, fast mode (csrc/attention.hip has the identity it rests on)."""
         if mode != "fast":
             raise CtsiError("the fp32 inference mode supports attention_mode='fast' only (the exact mode evaluates the "
-                            "same mathematics, DESIGN section 3.2)")
+                            "same mathematics, DESIGN section 3.2; the softmax mode has bf16 kernels only, section 19)")
         lib, sptr, prog = self.lib, self.ctx.sptr, self
         n, c, d, h, w = x.n, x.c, x.d, x.h, x.w
         tps = lib.attn_depthsum_f32_tiles(h, w)
@@ -247,9 +247,10 @@ class UNetProgramF32(_F32Ops, UNetProgram):
                  guided: bool = False, rescale: bool = False, prediction: str = "epsilon"):
         if shard is not None:
             raise CtsiError("the fp32 inference mode does not support depth sharding")
+        check_attention_mode(attention_mode)
         if attention_mode != "fast":
             raise CtsiError("the fp32 inference mode supports attention_mode='fast' only (the exact mode evaluates the "
-                            "same mathematics, DESIGN section 3.2)")
+                            "same mathematics, DESIGN section 3.2; the softmax mode has bf16 kernels only, section 19)")
         super().__init__(ctx, unet, n, d, h, w, max_rows, attention_mode, shard=None, guided=guided, rescale=rescale,
                          prediction=prediction)
 

@@ -9,7 +9,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .diffusion import GaussianDiffusion
-from .engine import Ctx, nan_to_num_, trilinear_depth
+from .engine import Ctx, check_attention_mode, nan_to_num_, trilinear_depth
 from .engine_f32 import check_precision
 from .lib import CtsiError
 from .sampler import SAMPLERS, check_guidance
@@ -59,6 +59,9 @@ class VideoToVideoDiffusion(nn.Module):
                            num_heads=config.get('unet_num_heads', 4),
                            time_embed_dim=config.get('unet_time_embed_dim', 512),
                            use_checkpoint=grad_ckpt)
+        # additive key, top level like every U-Net key: how TemporalAttention is evaluated -- 'fast' (default) / 'exact': the
+        # reference's einsum as written (a depth sum); 'softmax': true attention over depth (UNet3D's docstring)
+        self.unet.attention_mode = check_attention_mode(config.get('unet_attention_mode', 'fast'))
         self.diffusion = GaussianDiffusion(noise_schedule=config.get('noise_schedule', 'cosine'),
                                            timesteps=config.get('diffusion_timesteps', 1000),
                                            beta_start=config.get('beta_start', 0.0001),

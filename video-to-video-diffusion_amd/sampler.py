@@ -22,8 +22,8 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .engine import (SAMPLER_STEPS, Ctx, UNetProgram, _ptr, check_device_errors, nan_to_num_, sampler_step_launcher,
-                     trilinear_depth)
+from .engine import (SAMPLER_STEPS, Ctx, UNetProgram, _ptr, check_attention_mode, check_device_errors, nan_to_num_,
+                     sampler_step_launcher, trilinear_depth)
 from .engine_f32 import UNetProgramF32, check_precision
 from .lib import CtsiError
 
@@ -546,6 +546,8 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
     if not _is_engine_unet(model) and not callable(model):
         raise CtsiError(f"the samplers need a model(z, t, c) callable; got {type(model).__name__}")
     unet = model
+    if _is_engine_unet(model):
+        check_attention_mode(unet.attention_mode)     # an unknown mode is an error before anything is drawn or built
     device = torch.device(device)
     ctx = Ctx.get(device if device.type == "cuda" else conditioning.device)
     n, L, d, h, w = [int(v) for v in shape]

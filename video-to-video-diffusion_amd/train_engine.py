@@ -11,7 +11,8 @@ the backward launches, built by replaying a tape of the forward layers in revers
                   wgrad = ctsi_wgrad (MFMA, transposing LDS reads), bias = ctsi_channel_sum
   GroupNorm chain ctsi_gn_bwd
   attention       the depth-sum form of engine.Program.attention, un-folded into its two 1x1x1 convs so that
-                  proj_out / qkv(V) get their own gradients (the q and k thirds get exactly zero: rowsum(softmax) == 1)
+                  proj_out / qkv(V) get their own gradients (the q and k thirds get exactly zero: rowsum(softmax) == 1);
+                  attention_mode='softmax': the block of attention.py and ctsi_attn_core_bwd (all three thirds get gradients)
   time embedding  ctsi_linear_bwd
 
 `train_step` wraps both passes in a torch.autograd.Function over the U-Net parameters, so `loss.backward()`,
@@ -26,6 +27,7 @@ from typing import Callable, Dict, List, Optional
 import torch
 import torch.nn as nn
 
+from .attention import check_attention_mode, emit_softmax_attention_train
 from .engine import Act, Ctx, Program, _ptr
 from .lib import CtsiError, WgradDesc
 from .prediction import check_prediction_type
@@ -289,8 +291,10 @@ class UNetTrainProgram(TrainProgram):
         super().__init__(ctx)
         self.prediction = check_prediction_type(prediction)
         self.weight_cache = False    # weights change every optimizer step: private images, repacked in place
-        if unet.attention_mode != "fast":
-            raise CtsiError("training supports attention_mode='fast' only")
+        self.attention_mode = check_attention_mode(unet.attention_mode)
+        if self.attention_mode == "exact":
+            raise CtsiError("training supports attention_mode='fast' and 'softmax' (the exact mode multiplies in a row sum "
+                            "that is 1: its gradient is the fast mode's)")
         self.unet = unet
         self.n, self.d, self.h, self.w = n, d, h, w
         L = unet.latent_dim
@@ -475,7 +479,7 @@ class UNetTrainProgram(TrainProgram):
         if kind == "ResBlock3D":
             y = self.t_resblock(layer, x, skip)
         elif kind == "TemporalAttention":
-            y = self.t_attention(layer, x)
+            y = self.t_attention_softmax(layer, x) if self.attention_mode == "softmax" else self.t_attention(layer, x)
         else:
             raise CtsiError(f"unsupported U-Net layer {kind}")
         return y
@@ -573,6 +577,10 @@ class UNetTrainProgram(TrainProgram):
 
         self.tape.append(bwd)
         return out
+
+    # ---- TemporalAttention as true attention over depth (attention_mode='softmax', attention.py) ---------------------------
+    def t_attention_softmax(self, m, x: Act) -> Act:
+        return emit_softmax_attention_train(self, m, x)
 
     # ---- time embedding backward ------------------------------------------------------------------------------------------
     def _time_embed_bwd(self):

@@ -11,7 +11,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from .engine import Ctx, UNetProgram, cached_program
+from .engine import Ctx, UNetProgram, cached_program, check_attention_mode
 from .engine_f32 import UNetProgramF32, check_precision
 from .lib import CtsiError
 
@@ -74,7 +74,11 @@ class ResBlock3D(_EngineOnly):
 
 
 class TemporalAttention(_EngineOnly):
-    """unet3d.py:136-194 (attention along depth; see csrc/attention.hip for how it is evaluated)."""
+    """unet3d.py:136-194: attention along depth.  How it is evaluated is the owning UNet3D's `attention_mode`: 'fast' /
+    'exact' reproduce the reference's einsum 'bhqk,bhvc->bhqc' as written -- every query receives the depth SUM of V, the q
+    and k thirds of `qkv` have no effect (csrc/attention.hip) -- and 'softmax' computes softmax(q k^T / sqrt(hd)) v over the
+    depth positions of each (b, h, w) location (csrc/attention_core.hip).  Parameters and state dict are the same in all
+    three."""
 
     def __init__(self, channels, num_heads=4):
         super().__init__()
@@ -104,13 +108,17 @@ class Upsample3D(_EngineOnly):
 class UNet3D(nn.Module):
     """forward(x, t, c) -> predicted noise, all (B, latent_dim, T, h, w) fp32 NCDHW; t int64 (B,).
 
-    Extra attribute `attention_mode` ('fast' | 'exact') selects how TemporalAttention's
-    rowsum(softmax) factor is obtained; both reproduce the reference einsum (see attention.hip).
+    Extra attribute `attention_mode` ('fast' | 'exact' | 'softmax', default 'fast'; anything else is a ValueError).  'fast'
+    and 'exact' both reproduce the reference's einsum, in which every query receives the depth sum of V (they differ in how
+    the rowsum(softmax) == 1 factor is obtained, see attention.hip).  'softmax' is true attention over depth,
+    y = x + proj_out(softmax(q k^T / sqrt(hd)) v): same modules and state dict, so a checkpoint loads in either mode, and
+    forward, every sampler, guidance, v-prediction, stitching and training honour it.  It needs the whole
+    depth on one device (CtsiError with depth sharding) and the bf16 engine (CtsiError with inference_precision='fp32').
 
     Extra attribute `inference_precision` ('bf16' | 'fp32', default 'bf16') selects the arithmetic of `forward` (under
     no_grad) and of the samplers: bf16 activations and bf16 MFMA operands, or fp32 activations and fp32 MFMA operands
     (engine_f32.py: the reference's fp32 inference, models/model.py:254-259).  'fp32' supports attention_mode='fast' and
-    one device only (CtsiError with 'exact' or with depth sharding).  Training (`diffusion.training_loss`) always runs
+    one device only (CtsiError with 'exact' / 'softmax' or with depth sharding).  Training (`diffusion.training_loss`) always runs
     the bf16 programs, whatever this attribute says.
     """
 
@@ -182,6 +190,7 @@ class UNet3D(nn.Module):
 
     def program(self, ctx: Ctx, n: int, d: int, h: int, w: int, max_rows: int) -> UNetProgram:
         precision = check_precision(self.inference_precision)
+        check_attention_mode(self.attention_mode)
         key = ("unet", ctx.device.index, n, d, h, w, max_rows, self.attention_mode, precision)
         if precision == "fp32":
             return cached_program(self, key, lambda: UNetProgramF32(ctx, self, n, d, h, w, max_rows,
@@ -192,6 +201,7 @@ class UNet3D(nn.Module):
     @torch.no_grad()
     def forward(self, x, t, c):
         check_precision(self.inference_precision)
+        check_attention_mode(self.attention_mode)
         if not (x.is_cuda and c.is_cuda):
             raise CtsiError("UNet3D.forward runs on the HIP engine: move the tensors to a ROCm device "
                             "(there is no CPU path; the oracle under oracle/ is test infrastructure only)")
