@@ -590,6 +590,24 @@ int ctsi_pred_to_eps(float* out, const float* z, const float* hist, const float*
 int ctsi_q_sample_v(const float* z0, const float* noise, const float* sqrt_ac, const float* sqrt_1mac, const int* t,
                     void* dst, float* v_target, int n, int c, int d, int h, int w, int c_total, int c_off, void* stream);
 
+/* x0-form sampler update (csrc/x0_step.hip): the DDIM, DDPM and DPM-Solver++ updates of a v-prediction
+ * model on the data prediction -- no division by alpha = sqrt(abar), which is 0 at the last step of a zero-terminal-SNR
+ * schedule.  z, v (the network's raw output) and hist are fp32 NDHWC, noise fp32 NCDHW, zin the U-Net input slice as in
+ * ctsi_ddim_step / ctsi_ddim_step_f32 (bf16 / fp32, channels [c_off, c_off+c) of c_total).  Row coef[*step_ptr] (row 0 when
+ * step_ptr is NULL) = {alpha, sigma, a, b, c, s, clip, 0} (sampler.x0_coef_rows, float64 rounded once):
+ *   X = clamp(nan_to_num(fma(alpha, z, -sigma v)), -clip, clip)   (clip = 0: no clamp)
+ *   z <- zin <- a z + b X + c hist + s noise,   hist <- X.
+ * hist is read only by rows with c != 0 and written whenever it is not NULL; noise is read only by rows with s != 0; hist,
+ * noise, zin, step_ptr and nonfinite may be NULL.  nonfinite as for ctsi_ddim_step: row *step_ptr counts {v NaN, Inf, X NaN,
+ * Inf, z after update NaN, Inf}; v and the result pass through nan_to_num.  16-byte accesses when c % 4 == 0 and the
+ * pointers allow, one element per thread otherwise.  Null z / v / coef, non-positive sizes or a channel slice outside
+ * c_total return CTSI_ERR_INVALID before any launch.  Capture-safe: no allocation, no synchronisation. */
+int ctsi_x0_step(float* z, const float* v, float* hist, const float* noise_ncdhw, void* zin_bf16, int c_total, int c_off,
+                 const float* coef, const int* step_ptr, int n, int c, int d, int h, int w, int* nonfinite, void* stream);
+int ctsi_x0_step_f32(float* z, const float* v, float* hist, const float* noise_ncdhw, float* zin, int c_total, int c_off,
+                     const float* coef, const int* step_ptr, int n, int c, int d, int h, int w, int* nonfinite,
+                     void* stream);
+
 /* hipGraph helpers (one captured graph per denoising step) -------------------------------- */
 typedef struct ctsi_graph ctsi_graph;
 int ctsi_graph_begin_capture(void* stream);

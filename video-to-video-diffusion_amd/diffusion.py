@@ -27,6 +27,12 @@ class GaussianDiffusion(nn.Module):
         super().__init__()
         from .prediction import check_prediction_type
         self.prediction_type = check_prediction_type(prediction_type)
+        # plain attributes like prediction_type (no parameter, no buffer): the form of the sampler updates
+        # ('eps' | 'x0'), whether rescale_zero_terminal_snr() has rewritten the schedule, and the training loss weight
+        # ('min_snr' | 'uniform')
+        self.update_form = "eps"
+        self.zero_terminal_snr = False
+        self.loss_weighting = "min_snr"
         self.timesteps = timesteps
         self.noise_schedule = noise_schedule
         if noise_schedule == 'linear':
@@ -75,6 +81,73 @@ class GaussianDiffusion(nn.Module):
         z_t = (self._extract(self.sqrt_alphas_cumprod, t, z_0.shape) * z_0 +
                self._extract(self.sqrt_one_minus_alphas_cumprod, t, z_0.shape) * noise)
         return z_t, noise
+
+    # ---- zero terminal SNR and the x0 form ------------------------------------------------------
+    def rescale_zero_terminal_snr(self):
+        """Rewrite the ten buffers in place to the zero-terminal-SNR schedule of Lin et al. 2024 (Algorithm 1):
+        sqrt(abar) is shifted and scaled so that abar_{T-1} = 0 exactly and abar_0 stays, in float64, every buffer recomputed
+        from that and rounded once to fp32; beta_{T-1} = 1 (no 0.9999 clip).  All buffers stay finite (coef1 = sqrt(abar_{T-2}),
+        coef2 = 0 at T-1).  Needs 'v_prediction' (ValueError otherwise): at abar = 0 an epsilon output says nothing about
+        z_0.  Sets `zero_terminal_snr = True` and `update_form = 'x0'`, the only form that can evaluate T-1.  Idempotent: a
+        schedule that already ends in abar = 0 is left as it is.  Buffer names and the state dict keys do not change, so a
+        checkpoint of the rescaled model loads under the old names (its config carries `zero_terminal_snr: true`)."""
+        from .x0_form import BUFFERS, check_update_form, rescaled_schedule
+        check_update_form("x0", self.prediction_type)
+        if float(self.alphas_cumprod[-1]) != 0.0:
+            with torch.no_grad():
+                for name, value in rescaled_schedule(self.alphas_cumprod).items():
+                    buf = getattr(self, name)
+                    buf.copy_(value.to(buf.dtype))
+            assert set(BUFFERS) == set(dict(self.named_buffers()))
+        self.zero_terminal_snr = True
+        self.update_form = "x0"
+        return self
+
+    def _x0_form(self) -> bool:
+        from .x0_form import check_update_form
+        return check_update_form(self.update_form, self.prediction_type) == "x0"
+
+    def _x0_rows(self, t, with_noise, clip):
+        """One ctsi_x0_step row per SAMPLE for the single-step API: sampler.x0_coef_rows 'ddpm' at the sample's timestep,
+        s only with a noise tensor, clip 1 or none."""
+        from .x0_form import x0_coef_rows
+        rows = x0_coef_rows(self, "ddpm", t.reshape(-1).tolist(), dtype=torch.float64)
+        if not with_noise:
+            rows[:, 5] = 0.0
+        rows[:, 6] = 1.0 if clip else 0.0
+        return rows.float()
+
+    def _x0_posterior(self, z_t, t, v, noise, clip):
+        """The posterior mean (plus noise) of p_mean_variance / p_sample under update_form 'x0': ctsi_x0_step_f32 on each
+        sample's contiguous elements (c = per_sample, d = h = w = 1, where NCDHW and NDHWC coincide; no input slice), one row
+        per sample.  No division: per-sample timesteps may include T-1 of a zero-terminal-SNR schedule."""
+        from .engine import Ctx, _ptr
+        if not (z_t.is_cuda and v.is_cuda):
+            raise CtsiError("the reverse-process arithmetic runs on the HIP engine: move the tensors to a ROCm device "
+                            "(there is no CPU path)")
+        if tuple(v.shape) != tuple(z_t.shape) or t.reshape(-1).shape[0] != z_t.shape[0]:
+            raise ValueError(f"expected a model output of shape {tuple(z_t.shape)} and one timestep per sample, got "
+                             f"{tuple(v.shape)} and t of shape {tuple(t.shape)}")
+        ctx = Ctx.get(z_t.device)
+        n = int(z_t.shape[0])
+        per = z_t.numel() // n
+        out = z_t.detach().to(torch.float32).clone(memory_format=torch.contiguous_format)
+        vv = v.detach().to(torch.float32).contiguous()
+        nz = None if noise is None else noise.detach().to(device=ctx.device, dtype=torch.float32).contiguous()
+        coef = self._x0_rows(t, nz is not None, clip).to(ctx.device).contiguous()
+        at = lambda tns, b, width: C.c_void_p(0 if tns is None else tns.data_ptr() + 4 * b * width)
+        with ctx.scope():
+            for b in range(n):
+                ctx.lib.x0_step_f32(at(out, b, per), at(vv, b, per), None, at(nz, b, per), None, 0, 0, at(coef, b, 8), None,
+                                    1, per, 1, 1, 1, None, ctx.sptr)
+            for tns in (out, vv, nz, coef):
+                if tns is not None:
+                    tns.record_stream(ctx.stream)
+        return out
+
+    def _check_eps_form(self, t):
+        from .x0_form import check_eps_form_timesteps
+        check_eps_form_timesteps(self.alphas_cumprod, t.reshape(-1).tolist())
 
     # ---- v-prediction (DESIGN section 18) ---------------------------------------------------------------------------
     def v_target(self, z_0, t, noise):
@@ -198,9 +271,14 @@ class GaussianDiffusion(nn.Module):
         """(mean, variance, log_variance) of q(z_{t-1} | z_t, z_0_pred) (diffusion.py:270-308).  `model` is any
         `model(z, t, c) -> eps` callable on the ROCm device (the engine's UNet3D evaluates per-sample timesteps); the
         posterior mean is one ctsi_ddpm_posterior launch.  variance / log_variance are the (B,1,1,1,1) buffer gathers
-        the reference returns.  Under 'v_prediction' the model returns v (model_output_to_eps converts it)."""
-        noise_pred = self.model_output_to_eps(z_t, t, model(z_t, t, c))
-        _, mean = self._posterior(z_t, t, noise_pred, None, clip_denoised, False, True)
+        the reference returns.  Under 'v_prediction' the model returns v (model_output_to_eps converts it); under
+        update_form 'x0' the mean comes from the raw v without a division (_x0_posterior)."""
+        if self._x0_form():
+            mean = self._x0_posterior(z_t, t, model(z_t, t, c), None, clip_denoised)
+        else:
+            self._check_eps_form(t)
+            noise_pred = self.model_output_to_eps(z_t, t, model(z_t, t, c))
+            _, mean = self._posterior(z_t, t, noise_pred, None, clip_denoised, False, True)
         variance = self._extract(self.posterior_variance, t, z_t.shape)
         log_variance = self._extract(self.posterior_log_variance_clipped, t, z_t.shape)
         return mean, variance, log_variance
@@ -216,15 +294,34 @@ class GaussianDiffusion(nn.Module):
         if len(set(tv)) == 1 and clip_denoised and noise is None and _is_engine_unet(model):
             return run_sampler(self, model, tuple(z_t.shape), c, z_t.device, kind="ddpm", t_desc=[tv[0]],
                                progress=False, z_init=z_t)
-        noise_pred = self.model_output_to_eps(z_t, t, model(z_t, t, c))
+        x0_form = self._x0_form()
+        if not x0_form:
+            self._check_eps_form(t)
+        out = model(z_t, t, c)
         if noise is None:
             noise = torch.randn_like(z_t)
+        if x0_form:       # (the raw v, no division)
+            return self._x0_posterior(z_t, t, out, noise, clip_denoised)
+        noise_pred = self.model_output_to_eps(z_t, t, out)
         return self._posterior(z_t, t, noise_pred, noise, clip_denoised, False, True)[1]
+
+    def _snr_weight(self, t):
+        """The per-sample loss weight of training_loss (folded into norm[b] on the host).  'min_snr' -- Min-SNR-5 (Hang et al.
+        2023): min(snr, 5) / snr on an eps target, min(snr, 5) / (snr + 1) on a v target.  'uniform' (DESIGN section 20): 1,
+        the plain loss Lin et al. train with -- at SNR 0, the terminal step of a zero-terminal-SNR schedule, the Min-SNR v
+        weight is 0 and that step would never be trained."""
+        from .x0_form import check_loss_weighting
+        uniform = check_loss_weighting(self.loss_weighting) == "uniform"
+        snr = self.alphas_cumprod[t] / (1 - self.alphas_cumprod[t] + 1e-8)
+        v_pred = self.prediction_type == "v_prediction"
+        snr_weight = torch.clamp(snr, max=5.0) / (snr + 1.0 if v_pred else snr + 1e-8)
+        return torch.ones_like(snr_weight) if uniform else snr_weight
 
     def training_loss(self, model, z_0, c, mask=None, vae=None, v_gt=None, use_ssim=False, ssim_weight=0.0,
                       t=None, noise=None, cond_drop_prob=0.0, cond_keep=None):
         """Min-SNR-5 weighted epsilon-prediction loss (diffusion.py:108-247; under prediction_type='v_prediction' the
-        target is v and the weight min(snr, 5) / (snr + 1), everything else unchanged) with forward AND backward on the HIP
+        target is v and the weight min(snr, 5) / (snr + 1), everything else unchanged; `self.loss_weighting = 'uniform'`
+        makes the weight 1) with forward AND backward on the HIP
         engine: the returned scalar carries an autograd node whose backward launches the engine's gradient kernels
         and feeds the U-Net parameters' .grad.
 
@@ -264,10 +361,8 @@ class GaussianDiffusion(nn.Module):
         if keep is not None:
             keep = keep.to(device)
             c = c * keep.to(c.dtype)[:, None, None, None, None]
-        snr = self.alphas_cumprod[t] / (1 - self.alphas_cumprod[t] + 1e-8)
         v_pred = self.prediction_type == "v_prediction"
-        # Min-SNR-5 (Hang et al. 2023): min(snr, 5) / snr on an eps target, min(snr, 5) / (snr + 1) on a v target
-        snr_weight = torch.clamp(snr, max=5.0) / (snr + 1.0 if v_pred else snr + 1e-8)
+        snr_weight = self._snr_weight(t)
         if mask is not None:
             m = mask.to(device=device, dtype=torch.float32)
             if m.dim() != 3 or m.shape[0] != B or m.shape[2] != d or m.shape[1] not in (1, L):

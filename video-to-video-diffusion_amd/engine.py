@@ -26,6 +26,7 @@ import torch.nn as nn
 from .attention import ATTENTION_MODES, check_attention_mode, emit_softmax_attention
 from .lib import ConvDesc, ConvOut, CtsiError, get_lib
 from .prediction import add_pred_to_eps, check_prediction_type
+from .x0_form import add_x0_step, check_update_form
 
 _CTX: Dict[int, "Ctx"] = {}
 
@@ -1335,7 +1336,8 @@ class UNetProgram(Program):
               _ptr(self.w_all), _ptr(self.b_all), self.total_out, _ptr(self.te_scratch), _ptr(self.tbias), sptr)
 
     def eps_ncdhw(self) -> torch.Tensor:
-        """The noise prediction the update reads, fp32 NCDHW: rows [0, n) of `eps` (the guided eps in a guided program)."""
+        """The noise prediction the update reads, fp32 NCDHW: rows [0, n) of `eps` (the guided eps in a guided program).
+        In an x0-form program (add_sampler_step(update_form='x0')) the update reads the network's raw v: that is returned."""
         out = torch.empty((self.n, self.L, self.d, self.h, self.w), dtype=torch.float32, device=self.ctx.device)
         self.lib.ndhwc_f32_to_ncdhw_f32(_ptr(self.eps), _ptr(out), self.n, self.L, self.d, self.h, self.w,
                                         self.ctx.sptr)
@@ -1394,15 +1396,20 @@ class UNetProgram(Program):
         self._emit(lambda: lib.cfg_mirror(src, dst, rows, L * nbytes, c_total * nbytes, sptr), "cfg.mirror",
                    nbytes=2.0 * rows * L * nbytes, audit=dict(kind="cfg_mirror", zin=self.xin, n=self.n, L=L))
 
-    def add_sampler_step(self, kind: str, with_noise: bool):
+    def add_sampler_step(self, kind: str, with_noise: bool, update_form: str = "eps"):
         """Append the update of sampler `kind` (a SAMPLER_STEPS key) and the step-counter increment (done once, before
         capture).  'heun': one update per U-Net evaluation (predictor, corrector or final row); `with_noise` = churn on.
-        A v-prediction program converts the network output first (prediction.add_pred_to_eps), ahead of the guidance."""
+        A v-prediction program converts the network output first (prediction.add_pred_to_eps), ahead of the guidance.
+        `update_form` 'x0' ('ddim', 'ddpm', 'dpmpp' of a v-prediction program): no conversion launch --
+        the guidance and ctsi_x0_step (x0_form.add_x0_step) read the raw v, and eps_ncdhw() returns it."""
         lib, sptr = self.lib, self.ctx.sptr
         n, L, d, h, w = self.n, self.L, self.d, self.h, self.w
         entry = SAMPLER_STEPS[kind]
+        x0_form = check_update_form(update_form, self.prediction) == "x0"
+        if x0_form and kind == "heun":
+            raise CtsiError("internal: the EDM sampler has no x0-form update")
         self.hist = None
-        if self.prediction != "epsilon":
+        if self.prediction != "epsilon" and not x0_form:
             if entry.hist:      # (the conversion of a Heun corrector row reads the history)
                 self.hist = self.persistent((n, d, h, w, L), torch.float32, zero=True)
             add_pred_to_eps(self)
@@ -1434,14 +1441,18 @@ class UNetProgram(Program):
 
         step_bytes = (4 + 4 + 4 + zin_bytes + (4 if with_noise else 0) + (8 if entry.hist else 0)) * float(
             n * L * d * h * w)
-        self._emit(run_step, "sampler.step", nbytes=step_bytes,
-                   audit=dict(kind="sampler_step", sampler=kind, z=self.z, eps=self.eps, hist=self.hist,
-                              noise=self.noise if with_noise else None, zin=self.xin, coef=self.coef, step_ptr=self.step_ptr,
-                              nonfinite=self.nonfinite if entry.nonfinite else None, n=n, L=L))
+        if x0_form:
+            add_x0_step(self, kind, with_noise)
+        else:
+            self._emit(run_step, "sampler.step", nbytes=step_bytes,
+                       audit=dict(kind="sampler_step", sampler=kind, z=self.z, eps=self.eps, hist=self.hist,
+                                  noise=self.noise if with_noise else None, zin=self.xin, coef=self.coef,
+                                  step_ptr=self.step_ptr, nonfinite=self.nonfinite if entry.nonfinite else None, n=n, L=L))
         if self.guided:
             self._add_guidance_mirror()
         self._emit(run_adv, "sampler.advance", audit=dict(kind="sampler_advance", step_ptr=self.step_ptr))
         self.sampler_kind = (kind, with_noise)
+        self.update_form = update_form
 
 
 # ==========================================================================================================

@@ -192,6 +192,8 @@ SIGNATURES = {
     "ctsi_cfg_mirror": (_i, [_vp, _vp, _ll, _i, _i, _vp], True),
     "ctsi_pred_to_eps": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _vp], True),
     "ctsi_q_sample_v": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_x0_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp], True),
+    "ctsi_x0_step_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp], True),
     "ctsi_graph_begin_capture": (_i, [_vp], True),
     "ctsi_graph_end_capture": (_i, [_vp, C.POINTER(_vp)], True),
     "ctsi_graph_launch": (_i, [_vp, _vp], True),

@@ -68,6 +68,13 @@ class VideoToVideoDiffusion(nn.Module):
                                            beta_end=config.get('beta_end', 0.02),
                                            # additive key, top level like `noise_schedule`: 'epsilon' | 'v_prediction'
                                            prediction_type=config.get('prediction_type', 'epsilon'))
+        # additive keys, top level like `prediction_type`: `update_form` 'eps' | 'x0', `loss_weighting`
+        # 'min_snr' | 'uniform', and `zero_terminal_snr: true`, which rescales the schedule (and sets update_form 'x0')
+        from .x0_form import check_loss_weighting, check_update_form
+        self.diffusion.update_form = check_update_form(config.get('update_form', 'eps'), self.diffusion.prediction_type)
+        self.diffusion.loss_weighting = check_loss_weighting(config.get('loss_weighting', 'min_snr'))
+        if config.get('zero_terminal_snr', False):
+            self.diffusion.rescale_zero_terminal_snr()
         self.config = config
         self.use_pretrained = use_pretrained
         # additive key, top level like every U-Net / diffusion key: the conditioning-dropout probability of `forward`

@@ -26,6 +26,7 @@ from .engine import (SAMPLER_STEPS, Ctx, UNetProgram, _ptr, check_attention_mode
                      sampler_step_launcher, trilinear_depth)
 from .engine_f32 import UNetProgramF32, check_precision
 from .lib import CtsiError
+from .x0_form import check_eps_form_timesteps, check_update_form, x0_coef_rows, x0_step_launcher
 
 logger = logging.getLogger(__name__)
 
@@ -150,9 +151,11 @@ def dpm_coef_rows(alphas_cumprod: torch.Tensor, t_desc: Sequence[int], order: in
 # a(sigma) = sqrt(1 + sigma^2).  Host side in float64; the device update is ctsi_heun_step.
 # ---------------------------------------------------------------------------------------------------------------------
 def sigma_table(alphas_cumprod: torch.Tensor) -> np.ndarray:
-    """sigma_k = sqrt((1 - abar_k) / abar_k), k = 0..T-1, float64 (increasing)."""
+    """sigma_k = sqrt((1 - abar_k) / abar_k), k = 0..T-1, float64 (increasing; the last is inf on a zero-terminal-SNR
+    schedule, abar_{T-1} = 0)."""
     ac = alphas_cumprod.detach().double().cpu().numpy()
-    return np.sqrt((1.0 - ac) / ac)
+    with np.errstate(divide="ignore"):
+        return np.sqrt((1.0 - ac) / ac)
 
 
 def karras_sigmas(n: int, sigma_min: float, sigma_max: float, rho: float = 7.0) -> np.ndarray:
@@ -178,6 +181,7 @@ def sigma_to_t(sigma, alphas_cumprod: torch.Tensor):
     t = k + (ln sigma - ln sigma_k) / (ln sigma_{k+1} - ln sigma_k), clamped to [0, T-1].  Exactly k at a table value.
     Scalar in, float out; array in, float64 array out."""
     table = sigma_table(alphas_cumprod)
+    table = table[np.isfinite(table)]      # a zero-terminal-SNR schedule ends in sigma = inf: t then lies in [0, T-2]
     T = len(table)
     sig = np.asarray(sigma, dtype=np.float64)
     k = np.clip(np.searchsorted(table, sig, side="right") - 1, 0, T - 2)
@@ -316,6 +320,7 @@ class StepPlan(NamedTuple):
     init: Optional[Tuple[float, float]] = None     # z_0 = init[0] eps + init[1] eps_0; None: z_0 = eps
     init_noise: bool = False                       # eps_0 = noise_fn(0, shape) is drawn (step 0 churns)
     pred: Optional[torch.Tensor] = None            # (E, 4) ctsi_pred_to_eps rows under 'v_prediction'; None: the output is eps
+    x0: bool = False                               # update_form 'x0': coef holds ctsi_x0_step rows, the update reads the raw v
 
     def initial_state(self, z0: torch.Tensor, noise_fn, shape, dev) -> torch.Tensor:
         """The loop's start from the initial draw eps = z0 (Heun's zhat_0 is formed in float64)."""
@@ -334,6 +339,10 @@ def _step_plan(diffusion, kind: str, t_desc: Sequence, eta: float, order: int, h
     # v-prediction: the conversion rows, and the prediction type in the program cache keys (the epsilon keys stay as they are)
     v_pred = getattr(diffusion, "prediction_type", "epsilon") == "v_prediction"
     vkey = ("v_prediction",) if v_pred else ()
+    # the x0 form of the three integer-timestep samplers; Heun evaluates finite noise levels only and
+    # keeps its eps-form rows
+    x0 = check_update_form(getattr(diffusion, "update_form", "eps"),
+                           getattr(diffusion, "prediction_type", "epsilon")) == "x0"
     if kind == "heun":
         if heun is None or len(heun.t) != E:
             raise ValueError("kind='heun' needs the rows of heun_coef_rows(...) (heun=) and t_desc = heun.t")
@@ -341,19 +350,24 @@ def _step_plan(diffusion, kind: str, t_desc: Sequence, eta: float, order: int, h
         return StepPlan(kind, heun.rows, tuple(float(t) for t in t_desc), torch.float32, tuple(heun.noise_step),
                         tuple(heun.closes), with_noise, True, (kind, with_noise) + vkey, (order,), init=heun.init,
                         init_noise=bool(heun.gammas[0] > 0), pred=heun_pred_rows(heun) if v_pred else None)
-    if kind == "ddim":
+    if kind not in ("ddim", "ddpm", "dpmpp"):
+        raise ValueError(f"unknown sampler kind {kind!r}: expected 'ddim', 'ddpm', 'dpmpp' or 'heun'")
+    if x0:
+        coef = x0_coef_rows(diffusion, kind, t_desc, eta, order)
+    elif kind == "ddim":
+        check_eps_form_timesteps(diffusion.alphas_cumprod, t_desc)
         coef = ddim_coef_rows(diffusion.alphas_cumprod, t_desc, eta)
     elif kind == "ddpm":
+        check_eps_form_timesteps(diffusion.alphas_cumprod, t_desc)
         coef = diffusion.ddpm_coef_rows(t_desc)
-    elif kind == "dpmpp":
-        coef = dpm_coef_rows(diffusion.alphas_cumprod, t_desc, order)
     else:
-        raise ValueError(f"unknown sampler kind {kind!r}: expected 'ddim', 'ddpm', 'dpmpp' or 'heun'")
+        check_eps_form_timesteps(diffusion.alphas_cumprod, t_desc)
+        coef = dpm_coef_rows(diffusion.alphas_cumprod, t_desc, order)
     with_noise = kind == "ddpm" or eta > 0
     return StepPlan(kind, coef, tuple(int(t) for t in t_desc), torch.long,
                     tuple(range(E)) if with_noise else (-1,) * E, (True,) * E, with_noise, kind != "ddpm",
-                    (kind, with_noise) + vkey, (order,) if kind == "dpmpp" else (),
-                    pred=diffusion.pred_to_eps_rows(t_desc) if v_pred else None)
+                    (kind, with_noise) + vkey + (("x0",) if x0 else ()), (order,) if kind == "dpmpp" else (),
+                    pred=diffusion.pred_to_eps_rows(t_desc) if v_pred and not x0 else None, x0=x0)
 
 
 def _progress(plan: StepPlan, progress: bool):
@@ -383,7 +397,8 @@ def _run_generic(plan: StepPlan, model, shape, conditioning, ctx, z0, *, noise_f
     The model sees t as plan.t_dtype (Heun's fractional timesteps as fp32, as the reference embeds t) and as z the
     input the update writes to `zin`: the new state, or after a Heun predictor row the corrector's z' (z keeps zhat).
     Under 'v_prediction' (plan.pred) the callable returns v: ctsi_pred_to_eps turns the evaluation's rows into eps before
-    the guidance and the update, as in the step programs; eps_trajectory holds that eps.
+    the guidance and the update, as in the step programs; eps_trajectory holds that eps.  Under update_form 'x0' (plan.x0)
+    there is no conversion: the guidance and ctsi_x0_step_f32 read the raw v, and eps_trajectory holds it.
     `guidance` = (s, phi): classifier-free guidance -- two calls per evaluation, model(z, t, c) and model(z, t,
     zeros_like(c)), combined by ctsi_cfg_combine (the entry of the guided step program); eps_trajectory then holds the
     guided eps."""
@@ -391,7 +406,7 @@ def _run_generic(plan: StepPlan, model, shape, conditioning, ctx, z0, *, noise_f
     n, L, d, h, w = [int(v) for v in shape]
     evals = len(plan.t)
     dev = ctx.device
-    step = sampler_step_launcher(lib, plan.kind, f32=True)
+    step = x0_step_launcher(lib, True) if plan.x0 else sampler_step_launcher(lib, plan.kind, f32=True)
     coef = plan.coef.to(dev, torch.float32).contiguous()
     z_nd = torch.empty((n, d, h, w, L), dtype=torch.float32, device=dev)
     zin_nd = torch.empty_like(z_nd)
@@ -490,9 +505,10 @@ def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, 
         key = ("sampler-shard", ctx.device.index, 1, d, h, w, comm.rank, comm.world) + plan.key + plan.key_order
 
         def build():
-            kw = dict(prediction="v_prediction") if plan.pred is not None else {}   # elementwise on the rank's slab
+            v_out = plan.pred is not None or plan.x0
+            kw = dict(prediction="v_prediction") if v_out else {}                   # elementwise on the rank's slab
             prog = UNetProgram(ctx, unet, 1, dl, h, w, diffusion.timesteps + 1, "fast", shard=spec, **kw)
-            prog.add_sampler_step(plan.kind, plan.with_noise)
+            prog.add_sampler_step(plan.kind, plan.with_noise, **(dict(update_form="x0") if plan.x0 else {}))
             return prog
 
         prog = cached_program(unet, key, build)
@@ -539,7 +555,12 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
     m = phi std(eps_c) / std(eps_g) + 1 - phi per sample, to the unchanged update; trajectories and nonfinite counters
     report on that eps.  Not available with depth sharding (CtsiError).
     `diffusion.prediction_type == 'v_prediction'`: the model's output is v; one ctsi_pred_to_eps launch
-    per evaluation turns it into eps ahead of the guidance and the update, so everything above holds as written."""
+    per evaluation turns it into eps ahead of the guidance and the update, so everything above holds as written.
+    `diffusion.update_form == 'x0'` ('ddim', 'ddpm', 'dpmpp' of a v model): no conversion launch; the
+    update is ctsi_x0_step on the raw v, which divides by nothing, so a zero-terminal-SNR schedule can be sampled.  The
+    guidance then combines -- and its rescale takes the statistics of -- the raw v rows (with phi = 0 algebraically the
+    guided eps; with phi > 0 the statistics of the model output, as Lin et al. define the rescale: a difference from the
+    eps statistics of section 18), and `eps_trajectory` receives the (guided) raw v.  'heun' is not affected."""
     s_cfg, phi_cfg = check_guidance(guidance_scale, guidance_rescale)
     guided = s_cfg != 1.0
     plan = _step_plan(diffusion, kind, t_desc, eta, order, heun)
@@ -589,10 +610,10 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
         def build():
             cls = UNetProgramF32 if precision == "fp32" else UNetProgram
             kw = dict(guided=True, rescale=phi_cfg > 0.0) if guided else {}
-            if plan.pred is not None:
+            if plan.pred is not None or plan.x0:
                 kw["prediction"] = "v_prediction"
             prog = cls(ctx, unet, n, d, h, w, max_rows, unet.attention_mode, **kw)
-            prog.add_sampler_step(plan.kind, plan.with_noise)
+            prog.add_sampler_step(plan.kind, plan.with_noise, **(dict(update_form="x0") if plan.x0 else {}))
             return prog
 
         prog: UNetProgram = cached_program(unet, key, build)
@@ -759,7 +780,10 @@ class HeunSampler(_Sampler):
     t(sigma) (sigma_to_t).  Additive: the reference's EDMSampler is an unimplemented stub (kept as is).
     Defaults follow the paper clamped to the model's range: sigma_min = max(0.002, sigma_0), sigma_max = min(80,
     sigma_{T-1}), rho = 7.  Noise: eps from z_init / noise_fn(-1, shape) / torch.randn, then eps_i = noise_fn(i, shape)
-    (else torch.randn) only for the steps that churn (gamma_i > 0)."""
+    (else torch.randn) only for the steps that churn (gamma_i > 0).
+    `diffusion.update_form` does not affect this sampler: it evaluates finite noise levels only, so its eps-form rows and
+    kernels stay.  On a zero-terminal-SNR schedule (sigma_{T-1} = inf) the default sigma_max is the largest finite table
+    entry, sigma_{T-2}, and t(sigma) lies in [0, T-2]; an explicit infinite sigma_max is a ValueError as before."""
 
     def __init__(self, diffusion, model, order=2, sigma_min=None, sigma_max=None, rho=7.0, s_churn=0.0, s_tmin=0.0,
                  s_tmax=float("inf"), s_noise=1.0):
@@ -769,6 +793,8 @@ class HeunSampler(_Sampler):
         self.order = int(order)
         table = sigma_table(diffusion.alphas_cumprod)
         self.sigma_min = float(max(0.002, table[0]) if sigma_min is None else sigma_min)
+        if sigma_max is None and not np.isfinite(table[-1]):      # a zero-terminal-SNR schedule: the largest finite level
+            sigma_max = table[-2]
         self.sigma_max = float(min(80.0, table[-1]) if sigma_max is None else sigma_max)
         self.rho = float(rho)
         self.s_churn, self.s_tmin, self.s_tmax, self.s_noise = float(s_churn), float(s_tmin), float(s_tmax), float(s_noise)
