@@ -509,6 +509,39 @@ int ctsi_gn_colsum_f32(const float* x, float* colsum, int n, int c, int d, int h
 int ctsi_gn_apply_f32(const float* x, float* y, const double* sums, const float* gamma, const float* beta, int n, int c,
                       int d, int h, int w, int d_stat, int groups, float eps, int silu_pre, const float* tbias,
                       int tbias_stride, const int* step_ptr, const float* residual, int silu_post, void* stream);
+/* The ResBlock's middle pass with the ADM-style options (norm_mod.hip).  ctsi_gn_apply_mod has the argument
+ * list of ctsi_gn_apply plus: film (0: y = silu(gn(x)) + e, the time row holds c values; 1: y = silu(gn(x) * (1 + s) + b), the
+ * time row holds (s | b), 2c values, scale first), p_thr16 (dropout threshold in 1/65536 units, 0 = none: an element is kept iff
+ * its 16-bit Philox lane >= p_thr16), inv_keep (65536 / (65536 - p_thr16)), seed (DEVICE pointer to one 64-bit seed; may be
+ * NULL when p_thr16 == 0) and layer_id.  It serves that pass only: silu_pre != 0, tbias != NULL, residual == NULL,
+ * silu_post == 0 (anything else is an argument error).  tbias points at the block's first column of the time rows.
+ * Keep rule: one Philox4x32-10 call per 16-byte chunk g = ((sample * vox + voxel) * c + ch) / 8 of the logical NDHWC tensor,
+ * counter (lo32(g), hi32(g), layer_id, 0), key (seed_lo, seed_hi); channel j of the chunk takes
+ * (out[j >> 1] >> (16 * (j & 1))) & 0xffff.                                                                            */
+int ctsi_gn_apply_mod(const void* x_bf16, void* y_bf16, const double* sums, const float* gamma, const float* beta, int n,
+                      int c, int d, int h, int w, int d_stat, int groups, float eps, int silu_pre, const float* tbias,
+                      int tbias_stride, const int* step_ptr, const void* residual_bf16, int silu_post, int film,
+                      int p_thr16, float inv_keep, const void* seed, int layer_id, void* stream);
+/* fp32-activation twin for the fp32 inference mode (no dropout: inference never drops). */
+int ctsi_gn_apply_mod_f32(const float* x, float* y, const double* sums, const float* gamma, const float* beta, int n, int c,
+                          int d, int h, int w, int d_stat, int groups, float eps, int silu_pre, const float* tbias,
+                          int tbias_stride, const int* step_ptr, const float* residual, int silu_post, int film,
+                          void* stream);
+/* Backward of ctsi_gn_apply_mod.  tbias: the forward's time rows (row i for sample i, no step_ptr: training), read for s in
+ * scale-shift mode.  Writes dx, dgamma / dbeta (c floats), dxsum (optional: sum over samples and voxels of dx = the bias
+ * gradient of the conv that produced x) and, when dtbias is given, row i of the time-row gradient: (d_s | d_b), 2c floats,
+ * in scale-shift mode, d_e (c floats) in additive mode.  Deterministic (fixed-order reductions, no float atomics).
+ * workspace: ctsi_gn_bwd_mod_workspace_floats() floats.                                                                */
+size_t ctsi_gn_bwd_mod_workspace_floats(int n, int c, int d, int h, int w, int groups);
+int ctsi_gn_bwd_mod(const void* x, const void* dy, const double* sums, const float* gamma, const float* beta, int n, int c,
+                    int d, int h, int w, int groups, float eps, const float* tbias, int tbias_stride, int film, int p_thr16,
+                    float inv_keep, const void* seed, int layer_id, void* dx, float* workspace, float* dgamma,
+                    float* dbeta, float* dtbias, long long dtbias_stride, float* dxsum, void* stream);
+/* Test windows onto the keep rule: the keep bytes (1 = kept) of the first `count` elements of a layer, on the device (seed: device
+ * pointer) and on the host, and the generator itself (host only; ctr: 4, key: 2, out: 4 words).                          */
+int ctsi_dropout_mask(const void* seed, int layer_id, int p_thr16, long long count, void* out_u8, void* stream);
+int ctsi_dropout_mask_host(unsigned long long seed, int layer_id, int p_thr16, long long count, void* out_u8);
+int ctsi_philox4x32_10_host(const uint32_t* ctr, const uint32_t* key, uint32_t* out);
 /* TemporalAttention fast mode on fp32: depth sums + GroupNorm column sums (tiles of 64 positions per sample), the normalised
  * depth sum (fp32 [n][h*w][c]; the folded (proj_out . W_v) product is then one fp32 1x1x1 conv), and y = x + p broadcast
  * over depth.  Exact mode has no fp32 form (it is the same mathematics). */

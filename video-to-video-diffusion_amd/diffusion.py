@@ -337,7 +337,14 @@ class GaussianDiffusion(nn.Module):
         only when cond_drop_prob > 0, `cond_keep` is None and the U-Net is in training mode -- so cond_drop_prob = 0 leaves
         the generator where it was, and a seed gives the same t and noise at every probability.  `cond_keep` (bool, (B,))
         injects the mask.  The conditioning carries no gradient, so the backward is unchanged.  loss_dict gains
-        'cond_dropped' (the number of dropped samples) when a mask was in force."""
+        'cond_dropped' (the number of dropped samples) when a mask was in force.
+
+        ResBlock dropout (additive): with `model.dropout` > 0 (read here, at every forward) and the U-Net in
+        training mode, conv2's input of every ResBlock is dropped by a mask that is a pure function of (seed, block, element).
+        The 64-bit seed is drawn from torch's default CPU generator AFTER t and noise, and only when the threshold
+        floor(dropout * 65536) is > 0 -- so dropout = 0 consumes exactly the random numbers it always did; the plain attribute
+        `model.dropout_seed` (an int; None, the default, draws) injects it instead, the test hook beside `t=` / `noise=` (an
+        attribute because this signature is pinned).  `model.eval()` turns dropout off."""
         p_drop = float(cond_drop_prob)
         if not 0.0 <= p_drop <= 1.0:
             raise ValueError(f"cond_drop_prob must lie in [0, 1], got {cond_drop_prob!r}")
@@ -346,7 +353,10 @@ class GaussianDiffusion(nn.Module):
             raise ValueError(f"cond_keep must be a bool tensor of shape ({z_0.shape[0]},)")
         from .train_engine import UNetTrainProgram, train_step
         from .engine import Ctx, cached_program, check_attention_mode
+        from .norm_mod import dropout_active
         mode = check_attention_mode(getattr(model, "attention_mode", "fast"))
+        drop_on = dropout_active(model)                     # (validates the plain attribute, read at every forward)
+        drop_p = getattr(model, "dropout", 0.0)
         if not z_0.is_cuda:
             raise CtsiError("training_loss runs on the HIP engine: move the tensors to a ROCm device")
         B, L, d, h, w = z_0.shape
@@ -355,6 +365,9 @@ class GaussianDiffusion(nn.Module):
             t = torch.randint(0, self.timesteps, (B,), device=device, dtype=torch.long)
         if noise is None:
             noise = torch.randn_like(z_0)
+        dropout_seed = getattr(model, "dropout_seed", None)
+        if drop_on and dropout_seed is None:
+            dropout_seed = int(torch.randint(-(1 << 63), (1 << 63) - 1, (1,), dtype=torch.int64).item())
         keep = cond_keep
         if keep is None and p_drop > 0.0 and getattr(model, "training", False):
             keep = torch.rand(B, device=device) >= p_drop
@@ -380,11 +393,16 @@ class GaussianDiffusion(nn.Module):
         ctx = Ctx.get(device)
         with ctx.scope():
             # the epsilon key is what it always was; a v program (q_sample_v, a target buffer) has its own
+            film = bool(getattr(model, "use_scale_shift_norm", False))
             key = ("unet-train", ctx.device.index, B, d, h, w) + ((self.prediction_type,) if v_pred else ()) + (
-                () if mode == "fast" else ("attn-" + mode,))
+                () if mode == "fast" else ("attn-" + mode,)) + (((film, drop_on),) if (film or drop_on) else ())
             kw = dict(prediction=self.prediction_type) if v_pred else {}
+            if drop_on:
+                kw["dropout"] = True
             prog = cached_program(model, key, lambda: UNetTrainProgram(ctx, model, B, d, h, w, **kw))
             prog.set_diffusion(self)
+            if drop_on:
+                prog.set_dropout(drop_p, dropout_seed)
         loss = train_step(prog, z_0.detach().float(), c.detach().float(), t, noise.float(), norm, m)
         loss_dict = {'mse': loss.item()}
         if keep is not None:

@@ -568,9 +568,12 @@ class Program:
         return holder
 
     def _norm_in_pass(self, x1: Act, norm_in, synced: bool = False):
-        """The `norm_in` of conv(): x1 <- silu?(gn(x1)) + tbias in place, as a pass of its own ahead of the conv."""
-        slot, gn, silu, tb = norm_in
+        """The `norm_in` of conv(): x1 <- silu?(gn(x1)) + tbias in place, as a pass of its own ahead of the conv.  A fifth
+        entry of `norm_in` (film, True) makes it the scale-shift form silu(gn(x1) * (1 + s) + b) of the same pass."""
+        slot, gn, silu, tb, *mode = norm_in
         kw_tb = {} if tb is None else dict(tbias=tb[0], tbias_off=tb[1], tbias_stride=tb[2], step_ptr=tb[3])
+        if mode and mode[0]:
+            kw_tb["film"] = True
         self.gn_apply(x1, slot, gn, silu_pre=silu, out=x1, synced=synced, **kw_tb)
 
     def _conv_bias(self, bias_fn) -> Optional[torch.Tensor]:
@@ -847,11 +850,19 @@ class Program:
     def gn_apply(self, x: Act, slot: int, gn: nn.GroupNorm, *, silu_pre: bool, tbias=None,
                  tbias_off: int = 0, tbias_stride: int = 0, step_ptr: Optional[torch.Tensor] = None,
                  residual: Optional[Act] = None, silu_post: bool = False, out: Optional[Act] = None,
-                 synced: bool = False) -> Act:
+                 synced: bool = False, film: bool = False, drop=None) -> Act:
         """y = [silu](gn(x)) [+ tbias] [+ residual] [silu].  Depth-sharded: first the sync point that all-reduces the
         statistics and exchanges x's RAW boundary slices (unless `synced`: the caller already did), then the
-        normalisation over own + received halo slices -- y's halos are valid without an exchange of its own."""
+        normalisation over own + received halo slices -- y's halos are valid without an exchange of its own.
+        `film` / `drop` (the ResBlock's middle pass only) emit ctsi_gn_apply_mod instead: film: the time row
+        holds (s | b) and y = silu(gn(x) * (1 + s) + b); drop = (state, layer_id): dropout with the threshold, scale and seed
+        buffer of `state` (norm_mod.DropoutState, read at launch time).  Neither given: the default launch, as ever."""
         lib, sptr, prog = self.lib, self.ctx.sptr, self
+        if film or drop is not None:
+            if self.shard is not None:
+                raise CtsiError("use_scale_shift_norm / dropout do not support depth sharding")
+            if tbias is None or residual is not None or silu_post or not silu_pre:
+                raise CtsiError("internal: the scale-shift / dropout pass is the ResBlock's middle pass only")
         if self.shard is not None and not synced:
             self.sync_stats_and_halos(x if x.halo else None, slot, x.n * gn.num_groups * 2)
         if residual is not None and self.shard is not None and residual.halo:
@@ -876,6 +887,16 @@ class Program:
             lib.gn_apply(xp, yp, C.c_void_p(prog._gn_sums.data_ptr() + slot * 8), gp, bp, n, c, d, h, w, d_stat,
                          groups, eps, int(silu_pre), tbp, tbias_stride, stp, rp, int(silu_post), sptr)
 
+        if film or drop is not None:
+            from .norm_mod import emit_gn_apply_mod
+            emit_gn_apply_mod(self, xp=xp, yp=yp, slot=slot, gp=gp, bp=bp, n=n, c=c, d=d, h=h, w=w, d_stat=d_stat, groups=groups,
+                              eps=eps, tbp=tbp, tbias_stride=tbias_stride, stp=stp, film=film, drop=drop,
+                              record=dict(x=x, out=out, sums=lambda: prog._gn_sums, slot=slot, gamma=gamma, beta=beta,
+                                          groups=groups, eps=eps, d_stat=d_stat, silu_pre=True, tbias=tbias,
+                                          tbias_off=tbias_off, tbias_stride=tbias_stride, step_ptr=step_ptr))
+            if fresh:
+                self.zero_end_halos(out)
+            return out
         self._emit(run, "gn.apply", nbytes=(2 + (residual is not None)) * 2.0 * n * c * d * h * w,
                    audit=dict(kind="gn_apply", x=x, out=out, sums=lambda: prog._gn_sums, slot=slot, gamma=gamma, beta=beta,
                               groups=groups, eps=eps, d_stat=d_stat, silu_pre=bool(silu_pre), tbias=tbias, tbias_off=tbias_off,
@@ -899,7 +920,8 @@ class Program:
         # conv2 consumes silu(gn(c1)) + time bias: normalised on load where the plan supports it (c1 is never rewritten)
         c2, st = self.conv("rb.conv2", lambda: m.conv2[0].weight, lambda: m.conv2[0].bias, c1, None, cout=cout,
                            want_stats=True,
-                           norm_in=(slot, m.conv1.norm, True, (tbias, tbias_off, tbias_stride, step_ptr)))
+                           norm_in=(slot, m.conv1.norm, True, (tbias, tbias_off, tbias_stride, step_ptr))
+                           + ((True,) if getattr(m, "scale_shift", False) else ()))
         self.release(c1)
         slot = self.gn_finalize(c2, m.conv2[1].num_groups, st)
         if not has_res_conv:
@@ -1168,6 +1190,7 @@ class UNetProgram(Program):
         if shard is not None and guided:
             raise CtsiError("classifier-free guidance does not support depth sharding: the sharded program holds one "
                             "volume per rank and the rescale statistics would need a collective")
+        check_resblock_options_unsharded(unet, shard is not None)
         self.unet = unet
         self.guided, self.rescale = bool(guided), bool(guided and rescale)
         self.prediction = check_prediction_type(prediction)
@@ -1617,6 +1640,15 @@ def invalidate_engine_cache(module: nn.Module):
     sub-modules; the next call rebuilds from the current parameters."""
     for m in module.modules():
         m.__dict__.pop("_ctsi_programs", None)
+
+
+def check_resblock_options_unsharded(unet, sharded: bool):
+    """CtsiError when a U-Net built with use_scale_shift_norm=True meets depth sharding (out of scope, as
+    softmax attention is -- the scale-shift pass has no halo-extended form)."""
+    if sharded and getattr(unet, "use_scale_shift_norm", False):
+        raise CtsiError("use_scale_shift_norm=True does not support depth sharding (unet.depth_shard_comm): the scale-shift "
+                        "pass has no halo-extended form; drop the communicator or build the model with "
+                        "use_scale_shift_norm=False")
 
 
 def cached_program(module: nn.Module, key, build: Callable[[], Program]) -> Program:

@@ -131,8 +131,13 @@ class _F32Ops:
 
     def gn_apply(self, x: Act, slot: int, gn: nn.GroupNorm, *, silu_pre: bool, tbias=None, tbias_off: int = 0,
                  tbias_stride: int = 0, step_ptr: Optional[torch.Tensor] = None, residual: Optional[Act] = None,
-                 silu_post: bool = False, out: Optional[Act] = None, synced: bool = False) -> Act:
+                 silu_post: bool = False, out: Optional[Act] = None, synced: bool = False, film: bool = False,
+                 drop=None) -> Act:
         lib, sptr, prog = self.lib, self.ctx.sptr, self
+        if drop is not None:
+            raise CtsiError("internal: inference programs never drop")
+        if film and (tbias is None or residual is not None or silu_post or not silu_pre):
+            raise CtsiError("internal: the scale-shift pass is the ResBlock's middle pass only")
         gamma = self.dev_f32(lambda: gn.weight)
         beta = self.dev_f32(lambda: gn.bias)
         self.track(gn.weight, gn.bias)
@@ -148,6 +153,14 @@ class _F32Ops:
             lib.gn_apply_f32(xp, yp, C.c_void_p(prog._gn_sums.data_ptr() + slot * 8), gp, bp, n, c, d, h, w, d, groups, eps,
                              int(silu_pre), tbp, tbias_stride, stp, rp, int(silu_post), sptr)
 
+        if film:
+            from .norm_mod import emit_gn_apply_mod_f32
+            emit_gn_apply_mod_f32(self, xp=xp, yp=yp, slot=slot, gp=gp, bp=bp, n=n, c=c, d=d, h=h, w=w, groups=groups, eps=eps,
+                                  tbp=tbp, tbias_stride=tbias_stride, stp=stp,
+                                  record=dict(x=x, out=out, sums=lambda: prog._gn_sums, slot=slot, gamma=gamma, beta=beta,
+                                              groups=groups, eps=eps, d_stat=d, silu_pre=True, tbias=tbias,
+                                              tbias_off=tbias_off, tbias_stride=tbias_stride, step_ptr=step_ptr))
+            return out
         self._emit(run, "gn.apply", nbytes=(2 + (residual is not None)) * 4.0 * n * c * d * h * w,
                    audit=dict(kind="gn_apply", f32=True, x=x, out=out, sums=lambda: prog._gn_sums, slot=slot, gamma=gamma,
                               beta=beta, groups=groups, eps=eps, d_stat=d, silu_pre=bool(silu_pre), tbias=tbias,
@@ -167,7 +180,8 @@ class _F32Ops:
                            want_stats=True)
         slot = self.gn_finalize(c1, m.conv1.norm.num_groups, st)
         c2, st = self.conv("rb.conv2", lambda: m.conv2[0].weight, lambda: m.conv2[0].bias, c1, None, cout=cout,
-                           want_stats=True, norm_in=(slot, m.conv1.norm, True, (tbias, tbias_off, tbias_stride, step_ptr)))
+                           want_stats=True, norm_in=(slot, m.conv1.norm, True, (tbias, tbias_off, tbias_stride, step_ptr))
+                           + ((True,) if getattr(m, "scale_shift", False) else ()))
         self.release(c1)
         slot = self.gn_finalize(c2, m.conv2[1].num_groups, st)
         if not has_res_conv:

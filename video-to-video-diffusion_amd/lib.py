@@ -175,6 +175,16 @@ SIGNATURES = {
     "ctsi_gn_colsum_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ip, _vp], True),
     "ctsi_gn_apply_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp, _vp,
                                _i, _vp], True),
+    "ctsi_gn_apply_mod": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp, _vp,
+                               _i, _i, _i, _f, _vp, _i, _vp], True),
+    "ctsi_gn_apply_mod_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp, _vp,
+                                   _i, _i, _vp], True),
+    "ctsi_gn_bwd_mod_workspace_floats": (_sz, [_i, _i, _i, _i, _i, _i], False),
+    "ctsi_gn_bwd_mod": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _i, _i, _f, _vp, _i, _vp,
+                             _vp, _vp, _vp, _vp, _ll, _vp, _vp], True),
+    "ctsi_dropout_mask": (_i, [_vp, _i, _i, _ll, _vp, _vp], True),
+    "ctsi_dropout_mask_host": (_i, [C.c_ulonglong, _i, _i, _ll, _vp], True),
+    "ctsi_philox4x32_10_host": (_i, [_vp, _vp, _vp], True),
     "ctsi_attn_depthsum_f32_tiles": (_i, [_i, _i], False),
     "ctsi_attn_depthsum_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], True),
     "ctsi_attn_normsum_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp], True),

@@ -19,6 +19,14 @@ from .vae import VideoVAE
 logger = logging.getLogger(__name__)
 
 
+def _config_bool(config, key, default):
+    """A config key that must hold a real bool (YAML `true` / `false`): a string such as 'false' would otherwise count as true."""
+    v = config.get(key, default)
+    if not isinstance(v, bool):
+        raise ValueError(f"{key} must be true or false, got {v!r}")
+    return v
+
+
 class VideoToVideoDiffusion(nn.Module):
     def __init__(self, config, load_pretrained=False):
         super().__init__()
@@ -58,7 +66,12 @@ class VideoToVideoDiffusion(nn.Module):
                            channel_mult=tuple(config.get('unet_channel_mult', [1, 2, 4, 4])),
                            num_heads=config.get('unet_num_heads', 4),
                            time_embed_dim=config.get('unet_time_embed_dim', 512),
-                           use_checkpoint=grad_ckpt)
+                           use_checkpoint=grad_ckpt,
+                           # additive keys, top level like every U-Net key (UNet3D's docstring): the
+                           # ResBlocks' time conditioning (a real bool; anything else is a ValueError) and their
+                           # training-time dropout probability in [0, 1) (validated by UNet3D)
+                           use_scale_shift_norm=_config_bool(config, 'unet_use_scale_shift_norm', False),
+                           dropout=config.get('unet_dropout', 0.0))
         # additive key, top level like every U-Net key: how TemporalAttention is evaluated -- 'fast' (default) / 'exact': the
         # reference's einsum as written (a depth sum); 'softmax': true attention over depth (UNet3D's docstring)
         self.unet.attention_mode = check_attention_mode(config.get('unet_attention_mode', 'fast'))

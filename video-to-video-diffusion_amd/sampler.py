@@ -22,8 +22,8 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .engine import (SAMPLER_STEPS, Ctx, UNetProgram, _ptr, check_attention_mode, check_device_errors, nan_to_num_,
-                     sampler_step_launcher, trilinear_depth)
+from .engine import (SAMPLER_STEPS, Ctx, UNetProgram, _ptr, check_attention_mode, check_device_errors,
+                     check_resblock_options_unsharded, nan_to_num_, sampler_step_launcher, trilinear_depth)
 from .engine_f32 import UNetProgramF32, check_precision
 from .lib import CtsiError
 from .x0_form import check_eps_form_timesteps, check_update_form, x0_coef_rows, x0_step_launcher
@@ -593,6 +593,7 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
                             guidance=(s_cfg, phi_cfg) if guided else None)
     precision = check_precision(getattr(unet, "inference_precision", "bf16"))
     if comm is not None and comm.world > 1:
+        check_resblock_options_unsharded(unet, True)
         if precision != "bf16":
             raise CtsiError("the fp32 inference mode does not support depth sharding (unet.depth_shard_comm); "
                             "set inference_precision='bf16' or drop the communicator")

@@ -30,6 +30,7 @@ import torch.nn as nn
 from .attention import check_attention_mode, emit_softmax_attention_train
 from .engine import Act, Ctx, Program, _ptr
 from .lib import CtsiError, WgradDesc
+from .norm_mod import DropoutState, emit_gn_bwd_mod
 from .prediction import check_prediction_type
 
 
@@ -207,11 +208,16 @@ class TrainProgram(Program):
 
     # ---- GroupNorm chain ---------------------------------------------------------------------------------------------
     def t_gn(self, x: Act, slot: int, gn: nn.GroupNorm, *, silu_pre: bool, tb_off: Optional[int] = None,
-             residual: Optional[Act] = None, silu_post: bool = False, conv_bias: Optional[torch.Tensor] = None) -> Act:
+             residual: Optional[Act] = None, silu_post: bool = False, conv_bias: Optional[torch.Tensor] = None,
+             film: bool = False, drop=None) -> Act:
         """`conv_bias`: bias parameter of the convolution that produced x; its gradient (sum of dx) then comes out of
-        the GroupNorm backward's statistics and that conv's backward skips its own channel-sum pass."""
+        the GroupNorm backward's statistics and that conv's backward skips its own channel-sum pass.
+        `film` / `drop` = (norm_mod.DropoutState, layer_id): the ResBlock's middle pass in its scale-shift / dropout forms
+        (engine.Program.gn_apply); forward and backward then go to ctsi_gn_apply_mod / ctsi_gn_bwd_mod."""
+        mod = dict(film=film, drop=drop) if (film or drop is not None) else {}
         out = self.gn_apply(x, slot, gn, silu_pre=silu_pre, tbias=self.tbias if tb_off is not None else None,
-                            tbias_off=tb_off or 0, tbias_stride=self.total_out, residual=residual, silu_post=silu_post)
+                            tbias_off=tb_off or 0, tbias_stride=self.total_out, residual=residual, silu_post=silu_post,
+                            **mod)
         lib, sptr, prog = self.lib, self.ctx.sptr, self
         gamma = self.dev_f32(lambda: gn.weight)
         beta = self.dev_f32(lambda: gn.bias)
@@ -220,8 +226,11 @@ class TrainProgram(Program):
             gy = out.grad
             if gy is None:
                 raise CtsiError("internal: no gradient reached a GroupNorm output")
-            self._gn_bwd(x, gy, False, slot, gn, gamma, beta, silu_pre, tb_off, residual, silu_post, None,
-                         dxsum=None if conv_bias is None else self.grad_buf(conv_bias))
+            dxsum = None if conv_bias is None else self.grad_buf(conv_bias)
+            if mod:
+                emit_gn_bwd_mod(self, x, gy, slot, gn, gamma, beta, tb_off, film, drop, dxsum)
+            else:
+                self._gn_bwd(x, gy, False, slot, gn, gamma, beta, silu_pre, tb_off, residual, silu_post, None, dxsum=dxsum)
             self.release(gy)
             out.grad = None
 
@@ -283,12 +292,15 @@ class TrainProgram(Program):
             self.release(tmp)
 
 
-
 class UNetTrainProgram(TrainProgram):
-    def __init__(self, ctx: Ctx, unet, n: int, d: int, h: int, w: int, prediction: str = "epsilon"):
+    def __init__(self, ctx: Ctx, unet, n: int, d: int, h: int, w: int, prediction: str = "epsilon", dropout: bool = False):
         """`prediction` = 'v_prediction' (DESIGN section 18): the inputs come from ctsi_q_sample_v, which also writes the
-        target v into `v_target`, and both loss launches read that buffer where the epsilon program reads the noise."""
+        target v into `v_target`, and both loss launches read that buffer where the epsilon program reads the noise.
+        `dropout`: the ResBlocks' middle passes are the dropout launches; the probability and the seed
+        are set per forward (`set_dropout`).  The scale-shift mode is the module tree's (`unet.use_scale_shift_norm`)."""
         super().__init__(ctx)
+        self.film = bool(getattr(unet, "use_scale_shift_norm", False))
+        self.drop_state = DropoutState(self.persistent((1,), torch.int64, zero=True)) if dropout else None
         self.prediction = check_prediction_type(prediction)
         self.weight_cache = False    # weights change every optimizer step: private images, repacked in place
         self.attention_mode = check_attention_mode(unet.attention_mode)
@@ -347,6 +359,10 @@ class UNetTrainProgram(TrainProgram):
             self.tb_off[id(m)] = off
             off += m.time_mlp[1].out_features
         self.total_out = off
+        # the dropout layer ids: a ResBlock's ordinal in unet.modules() order, the enumeration of tb_off
+        names = {id(m): name for name, m in unet.named_modules()}
+        self.layer_id = {id(m): i for i, m in enumerate(self.blocks)}
+        self.dropout_layers = [(names[id(m)], i, m.conv1.conv.out_channels) for i, m in enumerate(self.blocks)]
         self.w1 = self.dev_f32(lambda: te[1].weight)
         self.b1 = self.dev_f32(lambda: te[1].bias)
         self.w2 = self.dev_f32(lambda: te[3].weight)
@@ -494,7 +510,8 @@ class UNetTrainProgram(TrainProgram):
             r = self.t_conv("res1x1", m.residual_conv, x, skip, k=(1, 1, 1))
         c1, st = self.t_conv("rb.conv1", m.conv1.conv, x, skip, want_stats=True, ret_stats=True, bias_from_gn=True)
         slot = self.gn_finalize(c1, m.conv1.norm.num_groups, st)
-        h1 = self.t_gn(c1, slot, m.conv1.norm, silu_pre=True, tb_off=self.tb_off[id(m)], conv_bias=m.conv1.conv.bias)
+        h1 = self.t_gn(c1, slot, m.conv1.norm, silu_pre=True, tb_off=self.tb_off[id(m)], conv_bias=m.conv1.conv.bias,
+                       film=self.film, drop=None if self.drop_state is None else (self.drop_state, self.layer_id[id(m)]))
         c2, st = self.t_conv("rb.conv2", m.conv2[0], h1, None, want_stats=True, ret_stats=True, bias_from_gn=True)
         slot = self.gn_finalize(c2, m.conv2[1].num_groups, st)
         out = self.t_gn(c2, slot, m.conv2[1], silu_pre=False, residual=r, silu_post=True, conv_bias=m.conv2[0].bias)
@@ -624,6 +641,15 @@ class UNetTrainProgram(TrainProgram):
         self.sqrt_ac = diffusion.sqrt_alphas_cumprod.detach().to(self.ctx.device, torch.float32).contiguous()
         self.sqrt_1mac = diffusion.sqrt_one_minus_alphas_cumprod.detach().to(self.ctx.device, torch.float32).contiguous()
 
+    def set_dropout(self, p: float, seed: int):
+        """Probability and 64-bit seed of the NEXT forward (a program built with dropout=True only); the seed reaches the device
+        buffer in run_forward."""
+        if self.drop_state is None:
+            raise CtsiError("internal: this train program was built without the dropout launches")
+        self.drop_state.set(p, seed)
+        if self.drop_state.thr <= 0:
+            raise CtsiError("internal: a dropout program needs a threshold > 0 (thr == 0 takes the default kernels)")
+
     def run_forward(self, z0, cond, t, noise, norm, mask=None) -> torch.Tensor:
         """Runs the forward launches and overwrites the tape (saved activations, t, noise) of this program: the
         generation counter lets a backward that belongs to an EARLIER forward of the same shape fail loudly instead of
@@ -635,6 +661,8 @@ class UNetTrainProgram(TrainProgram):
         self.noise.copy_(noise)
         self.t_rows.copy_(t.to(torch.int32))
         self.norm.copy_(norm.to(torch.float32))
+        if self.drop_state is not None:
+            self.drop_state.upload()
         self.use_mask = mask is not None
         if mask is not None:
             self.mask.copy_(mask.to(torch.float32))

@@ -14,6 +14,7 @@ import torch.nn as nn
 from .engine import Ctx, UNetProgram, cached_program, check_attention_mode
 from .engine_f32 import UNetProgramF32, check_precision
 from .lib import CtsiError
+from .norm_mod import check_dropout, dropout_threshold  # noqa: F401  (re-exported)
 
 _GROUP_CANDIDATES = (32, 16, 8, 4, 2, 1)
 
@@ -60,12 +61,15 @@ class Conv3DBlock(_EngineOnly):
 
 
 class ResBlock3D(_EngineOnly):
-    """unet3d.py:77-133."""
+    """unet3d.py:77-133.  `scale_shift`: the time projection emits 2 * out_channels values (scale | shift) that modulate the
+    normalised features ahead of the activation, silu(gn(h) * (1 + s) + b), instead of one bias added after it (the owning
+    UNet3D's `use_scale_shift_norm`); only the shape of `time_mlp.1.{weight,bias}` differs."""
 
-    def __init__(self, in_channels, out_channels, time_dim):
+    def __init__(self, in_channels, out_channels, time_dim, scale_shift=False):
         super().__init__()
+        self.scale_shift = bool(scale_shift)
         self.conv1 = Conv3DBlock(in_channels, out_channels)
-        self.time_mlp = nn.Sequential(nn.SiLU(), nn.Linear(time_dim, out_channels))
+        self.time_mlp = nn.Sequential(nn.SiLU(), nn.Linear(time_dim, (2 if scale_shift else 1) * out_channels))
         self.conv2 = nn.Sequential(nn.Conv3d(out_channels, out_channels, kernel_size=3, padding=1),
                                    nn.GroupNorm(_largest_group_count(out_channels), out_channels))
         self.residual_conv = (nn.Conv3d(in_channels, out_channels, kernel_size=1)
@@ -120,11 +124,26 @@ class UNet3D(nn.Module):
     (engine_f32.py: the reference's fp32 inference, models/model.py:254-259).  'fp32' supports attention_mode='fast' and
     one device only (CtsiError with 'exact' / 'softmax' or with depth sharding).  Training (`diffusion.training_loss`) always runs
     the bf16 programs, whatever this attribute says.
+
+    Constructor argument `use_scale_shift_norm` (default False) selects the time conditioning of every ResBlock3D: False is the
+    reference's bias, conv2's input = silu(gn(h)) + e; True is the ADM / EDM scale-shift form, silu(gn(h) * (1 + s) + b) with
+    (s | b) = the block's 2C-wide time projection, scale first.  The state dict differs only in the shape of the blocks'
+    `time_mlp.1.{weight,bias}`, so a checkpoint loads into a model built with the same value; forward, every sampler,
+    guidance, v-prediction, the x0 form, stitching, fp32 inference and training honour it.  It needs the whole
+    depth on one device (CtsiError with depth sharding).  Attribute `dropout` (constructor argument, default 0.0, a float
+    in [0, 1); anything else is a ValueError) drops conv2's input in every ResBlock3D during training only -- `training_loss`
+    with `unet.training` true; inference programs never drop.  It is read at each training forward, and the mask is a pure
+    function of (seed, block, element), regenerated in the backward; the 64-bit seed is drawn from torch's default CPU
+    generator once per training forward, or taken from the attribute `dropout_seed` when that is an int (a test hook).
     """
 
     def __init__(self, latent_dim=4, model_channels=128, num_res_blocks=2, attention_levels=[1, 2],
-                 channel_mult=(1, 2, 4, 4), num_heads=4, time_embed_dim=512, use_checkpoint=False):
+                 channel_mult=(1, 2, 4, 4), num_heads=4, time_embed_dim=512, use_checkpoint=False,
+                 use_scale_shift_norm=False, dropout=0.0):
         super().__init__()
+        self.use_scale_shift_norm = bool(use_scale_shift_norm)
+        self.dropout = check_dropout(dropout)
+        self.dropout_seed = None     # test hook: an int here replaces the seed drawn at each training forward
         self.latent_dim = latent_dim
         self.model_channels = model_channels
         self.num_res_blocks = num_res_blocks
@@ -139,7 +158,7 @@ class UNet3D(nn.Module):
         self.conv_in = nn.Conv3d(latent_dim * 2, model_channels, kernel_size=3, padding=1)
 
         def stage(cin, cout, with_attn):
-            layers = [ResBlock3D(cin, cout, time_embed_dim)]
+            layers = [ResBlock3D(cin, cout, time_embed_dim, self.use_scale_shift_norm)]
             if with_attn:
                 layers.append(TemporalAttention(cout, num_heads))
             return nn.ModuleList(layers)
@@ -156,9 +175,9 @@ class UNet3D(nn.Module):
             self.down_blocks.append(blocks)
             self.down_samples.append(Downsample3D(ch, ch) if level < self.num_levels - 1 else nn.Identity())
 
-        self.mid_block1 = ResBlock3D(ch, ch, time_embed_dim)
+        self.mid_block1 = ResBlock3D(ch, ch, time_embed_dim, self.use_scale_shift_norm)
         self.mid_attn = TemporalAttention(ch, num_heads)
-        self.mid_block2 = ResBlock3D(ch, ch, time_embed_dim)
+        self.mid_block2 = ResBlock3D(ch, ch, time_embed_dim, self.use_scale_shift_norm)
 
         self.up_blocks = nn.ModuleList()
         self.up_samples = nn.ModuleList()
