@@ -90,7 +90,9 @@ typedef struct ctsi_conv_out {
     int cout_stride;     /* mode 0: channels per voxel of y (>= c_off + cout)              */
     int c_off;           /* mode 0: first channel written                                   */
     long long sn, sc, sd, sh, sw; /* mode 1 strides, in elements                           */
-    int act;             /* 0: none, 1: tanh (models/vae.py:203)                           */
+    int act;             /* 0: none, 1: tanh (models/vae.py:203), 2: ReLU -- planar (1,3,3)
+                            halo-tile plans only (ctsi_conv_plan_form, bit 16), bf16 output,
+                            no colsum; ctsi_conv_fwd refuses it on every other plan      */
     float* colsum;       /* optional: per-tile column sums for a following GroupNorm
                             ([2][ctsi_conv_plan_tiles()][cout_pad] floats), or NULL       */
     /* optional fused ResBlock tail (models/unet3d.py:130-133, `self.activation(h + self.residual_conv(x))` with h =
@@ -140,11 +142,14 @@ double ctsi_conv_plan_flops(const ctsi_conv_plan* plan);
 int ctsi_conv_plan_config(const ctsi_conv_plan* plan, int* bm, int* bn, int* mode);
 /* what ctsi_conv_plan_config cannot tell apart (host-only; tests and tools/conv_plan_sweep.py): out[0..2] the tile TD, TH, TW
  * (linear-row gather plans: TD = depth slices a tile can touch), out[3] the split-K factor (ksplit of a k32 plan, gsplit of a
- * gather plan, else 0), out[4] flag bits 1 linear, 2 fast, 4 head2, 8 ds; out[5..7] are reserved (0).                   */
+ * gather plan, else 0), out[4] flag bits 1 linear, 2 fast, 4 head2, 8 ds, 16 planar (the (1,3,3) form of the k32 kernel: TD
+ * counts depth slices, which are independent images; CTSI_CONV_PLANAR=0, read at plan creation, keeps such layers on the
+ * gather kernel); out[5..7] are reserved (0).                                                                            */
 int ctsi_conv_plan_form(const ctsi_conv_plan* plan, int out[8]);
 /* which packed-weight image ctsi_conv_plan_pack_weights writes for this plan, as far as the descriptor's channel / kernel
  * fields, ctsi_conv_plan_cout_pad and the weight cin (ctsi_conv_plan_set_weight_cin) do not already say: bits 0-3 the
- * kernel family (CTSI_PACK_*); k32 plans add their form << 4 (0 Conv3d 3x3x3, 1 ConvTranspose3d, 2 strided Conv3d), the
+ * kernel family (CTSI_PACK_*); k32 plans add their form << 4 (0 Conv3d 3x3x3, 1 ConvTranspose3d, 2 strided Conv3d, 3 planar
+ * Conv3d (1,3,3)), the
  * cout-permuted direct-store image << 6 and bn / 16 << 8; head plans set bit 4 when the image carries the conv3_head2
  * part; stream-tail plans add their n-tile count << 8.  Plans of equal descriptor channel / kernel fields, cout_pad, weight
  * cin and pack layout pack byte-identical images (a cache of packed images may key on exactly these).  0: null plan. */
@@ -640,6 +645,37 @@ int ctsi_x0_step(float* z, const float* v, float* hist, const float* noise_ncdhw
 int ctsi_x0_step_f32(float* z, const float* v, float* hist, const float* noise_ncdhw, float* zin, int c_total, int c_off,
                      const float* coef, const int* step_ptr, int n, int c, int d, int h, int w, int* nonfinite,
                      void* stream);
+
+/* VGG-19 perceptual loss (csrc/vgg_loss.hip): the passes around its planar (1,3,3) convolutions, which run
+ * on conv plans.  Images are bf16 channels-last [image][h][w][c]; c and every `count` are multiples of 8 (16-byte accesses).
+ * ctsi_vgg_prep: image i = b * num + s <- slice slices[s] of sample b of x (fp32 NCDHW, C = 1): channels 0-2 are
+ *   ((x + 1) / 2 - norm[c]) / norm[3 + c] (norm = {mean[3], std[3]}, device), channels 3-7 zero.  slices: num device ints
+ *   in [0, d), all different.
+ * ctsi_vgg_prep_bwd: grad_pred (fp32, the shape of x) = sum_c g_c / (2 std_c) on the sampled slices and exactly zero on the
+ *   others (the entry clears the tensor itself when num < d); g: the 8-channel image gradient.
+ * ctsi_maxpool2_fwd / _bwd: 2 x 2 / stride 2 max pooling of n images (h, w even).  The backward routes each gradient to the
+ *   FIRST maximum of its window in (h, w) row-major order (torch's tie rule) and writes zeros to the other three positions.
+ * ctsi_relu_bf16: x <- max(x, 0) in place.
+ * ctsi_feat_loss_fwd: partials[0 .. ctsi_feat_loss_blocks()) <- fixed-order fp64 partial sums of |pred - target| (squared 0)
+ *   or (pred - target)^2 over `count` elements.  ctsi_feat_loss_finalize: out[1 + l] = (sum of layer l's partials, stored at
+ *   partials + l * ctsi_feat_loss_blocks()) / counts[l], out[0] = the average of the `layers` (<= 64) means; one launch.
+ * ctsi_feat_grad_relu_bwd: g_out = (g_in + coef * grad_loss[0] * f(y - target)) * [y > 0] over `count` elements; kind 1: f =
+ *   sign, kind 2: f(v) = 2 v, kind 0: no loss term (target, grad_loss unused; g_in required); relu 0: no mask; g_in may be
+ *   NULL for kind != 0; g_out may alias g_in.  y is the stored (post-ReLU where masked) activation: no mask is stored.
+ * No entry allocates, synchronises or keeps state; no float atomics: every result is bit-identical run to run.  Bad
+ * arguments return CTSI_ERR_INVALID before any launch. */
+int ctsi_vgg_prep(const float* x, const int* slices, const float* norm, void* dst, int b, int d, int num, int h, int w,
+                  void* stream);
+int ctsi_vgg_prep_bwd(const void* g, const int* slices, const float* norm, float* grad_pred, int b, int d, int num, int h,
+                      int w, void* stream);
+int ctsi_maxpool2_fwd(const void* x, void* y, int n, int h, int w, int c, void* stream);
+int ctsi_maxpool2_bwd(const void* x, const void* gy, void* gx, int n, int h, int w, int c, void* stream);
+int ctsi_relu_bf16(void* x, long long count, void* stream);
+int ctsi_feat_loss_blocks(void);
+int ctsi_feat_loss_fwd(const void* pred, const void* target, long long count, int squared, double* partials, void* stream);
+int ctsi_feat_loss_finalize(const double* partials, const long long* counts, int layers, float* out, void* stream);
+int ctsi_feat_grad_relu_bwd(const void* g_in, const void* y, const void* target, void* g_out, long long count, float coef,
+                            int kind, int relu, const float* grad_loss, void* stream);
 
 /* hipGraph helpers (one captured graph per denoising step) -------------------------------- */
 typedef struct ctsi_graph ctsi_graph;

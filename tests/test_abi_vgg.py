@@ -1,0 +1,218 @@
+"""CPU: the entry points of the VGG perceptual loss (csrc/vgg_loss.hip) are declared in include/ctsi.h, exported by libctsi.so
+and bound by lib.py; their argument checks answer before any launch; which of its (1, 3, 3) convolutions ctsi_conv_plan_create puts on
+the planar form of the k32 halo-tile kernel, what CTSI_CONV_PLANAR changes about that, and that the ReLU epilogue is refused on
+every other plan.  No device is needed or touched."""
+import ctypes as C
+import importlib
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+L = importlib.import_module("video-to-video-diffusion_amd.lib")
+
+NEW = ("ctsi_vgg_prep", "ctsi_vgg_prep_bwd", "ctsi_maxpool2_fwd", "ctsi_maxpool2_bwd", "ctsi_relu_bf16", "ctsi_feat_loss_blocks",
+       "ctsi_feat_loss_fwd", "ctsi_feat_loss_finalize", "ctsi_feat_grad_relu_bwd")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not L.LIB_PATH.exists():
+        L.build()
+    return L.get_lib()
+
+
+def test_new_symbols_are_declared_exported_and_bound(lib):
+    text = re.sub(r"/\*.*?\*/", "", L.HEADER_PATH.read_text(), flags=re.S)
+    declared = set(re.findall(r"\b(ctsi_[a-z0-9_]+)\s*\(", text))
+    dll = C.CDLL(str(L.LIB_PATH))
+    for name in NEW:
+        assert name in declared, f"{name} is not declared in include/ctsi.h"
+        assert hasattr(dll, name), f"{name} is not exported by libctsi.so"
+        assert name in L.SIGNATURES, f"{name} is not bound"
+        assert callable(getattr(lib, name[len("ctsi_"):]))
+        assert L.SIGNATURES[name][2] == (name != "ctsi_feat_loss_blocks")
+    assert "vgg_loss.hip" in (L.CSRC_DIR / "Makefile").read_text()
+    assert lib.feat_loss_blocks() == 256
+
+
+P = C.c_void_p(0x1000)      # never dereferenced: every call below fails its argument check before any launch
+
+
+def test_argument_checks_come_before_any_launch(lib):
+    for fn, name in ((lib.vgg_prep, "ctsi_vgg_prep"), (lib.vgg_prep_bwd, "ctsi_vgg_prep_bwd")):
+        good = dict(x=P, slices=P, norm=P, dst=P, b=1, d=4, num=2, h=16, w=16)
+        for kw in (dict(x=None), dict(slices=None), dict(norm=None), dict(dst=None), dict(b=0), dict(num=0), dict(num=5), dict(h=0)):
+            a = dict(good, **kw)
+            with pytest.raises(L.CtsiError, match=name + ": bad arguments"):
+                fn(a["x"], a["slices"], a["norm"], a["dst"], a["b"], a["d"], a["num"], a["h"], a["w"], None)
+    for kw in (dict(x=None), dict(y=None), dict(n=0), dict(h=15), dict(w=6 + 1), dict(c=12), dict(c=0)):
+        a = dict(dict(x=P, y=P, n=2, h=16, w=16, c=64), **kw)
+        with pytest.raises(L.CtsiError, match="ctsi_maxpool2_fwd: bad arguments"):
+            lib.maxpool2_fwd(a["x"], a["y"], a["n"], a["h"], a["w"], a["c"], None)
+        with pytest.raises(L.CtsiError, match="ctsi_maxpool2_bwd: bad arguments"):
+            lib.maxpool2_bwd(a["x"], P, a["y"], a["n"], a["h"], a["w"], a["c"], None)
+    with pytest.raises(L.CtsiError, match="ctsi_maxpool2_bwd: bad arguments"):
+        lib.maxpool2_bwd(P, None, P, 2, 16, 16, 64, None)
+    for args in ((None, 64), (P, 0), (P, 12), (P, -8)):
+        with pytest.raises(L.CtsiError, match="ctsi_relu_bf16: bad arguments"):
+            lib.relu_bf16(args[0], args[1], None)
+    for args in ((None, P, 64, P), (P, None, 64, P), (P, P, 64, None), (P, P, 0, P), (P, P, 20, P)):
+        with pytest.raises(L.CtsiError, match="ctsi_feat_loss_fwd: bad arguments"):
+            lib.feat_loss_fwd(args[0], args[1], args[2], 0, args[3], None)
+    for args in ((None, P, 5, P), (P, None, 5, P), (P, P, 5, None), (P, P, 0, P), (P, P, 65, P)):
+        with pytest.raises(L.CtsiError, match="ctsi_feat_loss_finalize: bad arguments"):
+            lib.feat_loss_finalize(args[0], args[1], args[2], args[3], None)
+    good = dict(g=P, y=P, t=P, o=P, count=64, kind=1, gl=P)
+    for kw in (dict(y=None), dict(o=None), dict(count=0), dict(count=12), dict(kind=3), dict(kind=-1), dict(t=None), dict(gl=None),
+               dict(kind=0, g=None)):
+        a = dict(good, **kw)
+        with pytest.raises(L.CtsiError, match="ctsi_feat_grad_relu_bwd: bad arguments"):
+            lib.feat_grad_relu_bwd(a["g"], a["y"], a["t"], a["o"], a["count"], 1.0, a["kind"], 1, a["gl"], None)
+
+
+def _plan(lib, cin, cout, images, h, w, cin_w=None):
+    desc = L.ConvDesc(0, 1, 3, 3, 1, 1, 0, 1, 1, 1, cin, 0, cout, images, h, w, 0)
+    plan = C.c_void_p()
+    lib.conv_plan_create(C.byref(plan), C.byref(desc))
+    if cin_w is not None:
+        lib.conv_plan_set_weight_cin(plan, cin_w)
+    return plan
+
+
+@pytest.mark.parametrize("cin,cout,images,h,w,cin_w", [(64, 64, 4, 32, 32, None), (8, 64, 4, 32, 32, 3), (512, 512, 18, 16, 16, None),
+                                                      (64, 8, 4, 32, 32, None)])
+def test_planar_descriptors_are_planned(lib, cin, cout, images, h, w, cin_w):
+    """The loss's convolutions: images along the depth axis, k = (1, 3, 3), pad (0, 1, 1) -- output dims, flops and a packed
+    image size come back; the 3-channel stem (8 stored channels) and the 8-channel data gradient of the stem included."""
+    plan = _plan(lib, cin, cout, images, h, w, cin_w)
+    try:
+        do, ho, wo = C.c_int(), C.c_int(), C.c_int()
+        lib.conv_plan_out_dims(plan, C.byref(do), C.byref(ho), C.byref(wo))
+        assert (do.value, ho.value, wo.value) == (images, h, w)
+        assert lib.conv_plan_flops(plan) == 2.0 * images * h * w * cin * cout * 9
+        assert lib.conv_plan_weight_bytes(plan) >= 2 * 9 * cout * (cin_w or cin)
+        assert lib.conv_plan_workspace_bytes(plan) == 0 or cin >= 256
+    finally:
+        lib.conv_plan_destroy(plan)
+
+
+def _report(lib, plan):
+    bm, bn, mode, form = C.c_int(), C.c_int(), C.c_int(), (C.c_int * 8)()
+    lib.conv_plan_config(plan, C.byref(bm), C.byref(bn), C.byref(mode))
+    lib.conv_plan_form(plan, form)
+    return dict(bm=bm.value, bn=bn.value, mode=mode.value, tile=tuple(form[:3]), split=form[3], planar=bool(form[4] & 16),
+                layout=lib.conv_plan_pack_layout(plan))
+
+
+@pytest.fixture(autouse=True)
+def _no_override(monkeypatch):
+    monkeypatch.delenv("CTSI_CONV_PLANAR", raising=False)
+
+
+def test_a_planar_plan_reports_the_planar_form(lib):
+    plan = _plan(lib, 64, 64, 4, 32, 32)
+    try:
+        r = _report(lib, plan)
+        assert r["planar"] and r["mode"] == 9 and (r["bm"], r["bn"]) == (512, 128) and r["tile"] == (1, 16, 32) and r["split"] == 0
+        # the k32 family's image, form 3 (planar), cout-permuted for the direct-store epilogue, 128 couts per block
+        assert r["layout"] == 4 | (3 << 4) | (1 << 6) | (8 << 8)
+        assert lib.conv_plan_weight_bytes(plan) == (64 // 16) * 9 * 128 * 32        # 36 entries = 9 whole steps of 4
+        assert lib.conv_plan_tiles(plan) == 8 and lib.conv_plan_workspace_bytes(plan) == 0
+    finally:
+        lib.conv_plan_destroy(plan)
+
+
+def test_the_override_keeps_the_gather_kernel():
+    """CTSI_CONV_PLANAR=0, set before the library is loaded, read in a child process."""
+    code = ("import ctypes as C, importlib\n"
+            "L = importlib.import_module('video-to-video-diffusion_amd.lib')\n"
+            "lib = L.get_lib()\n"
+            "plan, mode, form = C.c_void_p(), C.c_int(), (C.c_int * 8)()\n"
+            "lib.conv_plan_create(C.byref(plan), C.byref(L.ConvDesc(0, 1, 3, 3, 1, 1, 0, 1, 1, 1, 64, 0, 64, 4, 32, 32, 0)))\n"
+            "lib.conv_plan_config(plan, None, None, C.byref(mode))\n"
+            "lib.conv_plan_form(plan, form)\n"
+            "print('plan', mode.value, form[4] & 16, lib.conv_plan_pack_layout(plan) & 15)\n")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for value, want in (("0", "plan 2 0 1"), ("1", "plan 9 16 4"), (None, "plan 9 16 4")):
+        env = {k: v for k, v in os.environ.items() if k != "CTSI_CONV_PLANAR"}
+        if value is not None:
+            env["CTSI_CONV_PLANAR"] = value
+        out = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert out.stdout.strip().splitlines()[-1] == want, (value, out.stdout)
+
+
+TILES = {"1x16x32": (1, 16, 32), "2x16x16": (2, 16, 16), "4x8x16": (4, 8, 16), "4x4x24": (4, 4, 24), "8x4x12": (8, 4, 12)}
+
+
+def test_the_override_names_a_tile(lib, monkeypatch):
+    """CTSI_CONV_PLANAR=<tile>: that tile wherever the form applies (the 24- / 12-wide tiles where the plane divides into them
+    and not into 16-wide ones), also where the plan itself keeps the gather kernel."""
+    cases = [((512, 512, 9, 16, 16), ["1x16x32", "2x16x16", "4x8x16"], ["4x4x24", "8x4x12"]),
+             ((64, 128, 3, 24, 40), ["1x16x32", "2x16x16", "4x8x16"], ["4x4x24", "8x4x12"]),
+             ((128, 128, 5, 12, 24), ["1x16x32", "2x16x16", "4x8x16", "4x4x24", "8x4x12"], []),
+             ((64, 64, 9, 18, 12), ["1x16x32", "2x16x16", "4x8x16", "8x4x12"], ["4x4x24"])]
+    for shape, reach, fall in cases:
+        for name in reach + fall:
+            monkeypatch.setenv("CTSI_CONV_PLANAR", name)
+            plan = _plan(lib, *shape)
+            r = _report(lib, plan)
+            lib.conv_plan_destroy(plan)
+            if name in reach:
+                assert r["planar"] and r["tile"] == TILES[name] and r["bm"] == TILES[name][0] * TILES[name][1] * TILES[name][2], (shape, name, r)
+            else:
+                assert not r["planar"] and r["mode"] in (0, 1, 2), (shape, name, r)
+    monkeypatch.setenv("CTSI_CONV_PLANAR", "1")        # wherever it applies: also the deep-K small grid the plan leaves to the gather kernel
+    for shape, planar in (((512, 512, 9, 16, 16), True), ((8, 64, 4, 32, 32, 3), False), ((64, 32, 4, 32, 32), False)):
+        plan = _plan(lib, *shape)
+        assert _report(lib, plan)["planar"] == planar, shape
+        lib.conv_plan_destroy(plan)
+
+
+def test_what_stays_on_the_gather_kernel(lib):
+    """The 3 -> 64 stem (8 stored channels: no whole 16-channel chunk), planes too small for a tile, deep K on a small grid,
+    and every descriptor that is not (1,3,3) / stride 1 / pad (0,1,1)."""
+    for shape in ((8, 64, 4, 32, 32, 3), (64, 128, 3, 24, 40), (512, 512, 4, 4, 6), (512, 512, 9, 16, 16), (256, 256, 2, 16, 16),
+                  (64, 8, 4, 32, 32)):
+        plan = _plan(lib, *shape)
+        r = _report(lib, plan)
+        lib.conv_plan_destroy(plan)
+        assert not r["planar"] and r["mode"] in (0, 1, 2), (shape, r)
+    for desc in (L.ConvDesc(0, 1, 3, 3, 1, 1, 0, 0, 0, 1, 64, 0, 64, 4, 32, 32, 0),       # no padding
+                 L.ConvDesc(0, 1, 3, 3, 2, 2, 0, 1, 1, 1, 64, 0, 64, 4, 32, 32, 0),       # strided
+                 L.ConvDesc(0, 1, 1, 1, 1, 1, 0, 0, 0, 1, 64, 0, 64, 4, 32, 32, 0)):      # pointwise
+        plan = C.c_void_p()
+        lib.conv_plan_create(C.byref(plan), C.byref(desc))
+        assert not _report(lib, plan)["planar"]
+        lib.conv_plan_destroy(plan)
+
+
+def test_relu_epilogue_is_refused_on_other_plans(lib):
+    """ctsi_conv_out.act = 2 on a plan without the planar form: an error string before any launch."""
+    k3 = C.c_void_p()
+    lib.conv_plan_create(C.byref(k3), C.byref(L.ConvDesc(0, 3, 3, 3, 1, 1, 1, 1, 1, 1, 64, 0, 64, 8, 32, 32, 0)))
+    stem = _plan(lib, 8, 64, 4, 32, 32, 3)
+    small = _plan(lib, 512, 512, 4, 4, 6)
+    try:
+        for plan in (k3, stem, small):
+            assert not _report(lib, plan)["planar"]
+            co = L.ConvOut()
+            co.y, co.mode, co.cout_stride, co.act = 0x1000, 0, 512 if plan is small else 64, 2
+            with pytest.raises(L.CtsiError, match=r"ReLU epilogue \(act = 2\) exists on planar"):
+                lib.conv_fwd(plan, P, None, P, None, C.byref(co), None)
+        # on a planar plan the combination with column sums is refused the same way
+        planar = _plan(lib, 64, 64, 4, 32, 32)
+        co = L.ConvOut()
+        co.y, co.mode, co.cout_stride, co.act, co.colsum = 0x1000, 0, 64, 2, 0x1000
+        with pytest.raises(L.CtsiError, match="ReLU epilogue"):
+            lib.conv_fwd(planar, P, None, P, None, C.byref(co), None)
+        co.act = 0
+        with pytest.raises(L.CtsiError, match="writes no column sums"):
+            lib.conv_fwd(planar, P, None, P, None, C.byref(co), None)
+        lib.conv_plan_destroy(planar)
+    finally:
+        for plan in (k3, stem, small):
+            lib.conv_plan_destroy(plan)

@@ -1,0 +1,314 @@
+"""GPU: the single ops of the VGG perceptual loss (csrc/vgg_loss.hip and the (1, 3, 3) conv plans) against torch.
+
+The convolutions are judged as tests/test_gpu_ops.py judges its conv forms (test_downsample_conv_on_halo_tile_kernel): rel-L2
+against the fp32 torch convolution on the same bf16 operands below CONV_TOL = 3e-3.  The elementwise passes compute in fp32
+from bf16 operands that the test chooses exactly representable, so selections (max pooling, its routing, ReLU, the input
+transform) are held to bit equality and sums to the rounding of their output format."""
+import ctypes as C
+import importlib
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests.helpers import bf16_round, formula_input, rel_l2
+from tests.vgg_restatement import MEAN, STD, slice_indices, to_rgb
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+CONV_TOL = 3e-3          # tests/test_gpu_ops.py
+K, P = (1, 3, 3), (0, 1, 1)
+
+
+@pytest.fixture(scope="module")
+def G():
+    from tests import gpu_utils
+    return gpu_utils
+
+
+def _ptr(t):
+    return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _w(shape, k):
+    fan = shape[1] * 9
+    return formula_input(shape, k) * (1.5 / math.sqrt(fan))
+
+
+# name, cin, cout, images, h, w, the planar tiles CTSI_CONV_PLANAR can force on the shape (every one the plan can pick for it)
+WIDE = ["1x16x32", "2x16x16", "4x8x16"]
+CONV_CASES = [("64_64_5x32x32", 64, 64, 5, 32, 32, WIDE),              # ragged in the image dimension
+              ("64_128_3x24x40", 64, 128, 3, 24, 40, WIDE),            # ragged H and W
+              ("256_256_2x16x16", 256, 256, 2, 16, 16, WIDE),
+              ("512_512_9x16x16", 512, 512, 9, 16, 16, WIDE),          # deep K
+              ("128_128_5x12x24", 128, 128, 5, 12, 24, ["4x4x24", "8x4x12"]),   # A tiles that straddle W-lines, ragged images
+              ("64_64_9x18x12", 64, 64, 9, 18, 12, ["8x4x12"])]        # ... ragged H as well
+TILES = {"1x16x32": (1, 16, 32), "2x16x16": (2, 16, 16), "4x8x16": (4, 8, 16), "4x4x24": (4, 4, 24), "8x4x12": (8, 4, 12)}
+_GATHER = {}
+
+
+def _images(x):          # (1, c, images, h, w) <-> (images, c, h, w)
+    return x[0].permute(1, 0, 2, 3)
+
+
+def _case(name, cin, cout, images, h, w):
+    """operands, fp32 references and the gather kernel's results of a case: computed once, shared by its tile forms"""
+    if name not in _GATHER:
+        x = bf16_round(formula_input((1, cin, images, h, w), 1))
+        wt = bf16_round(_w((cout, cin, 3, 3), 3))
+        b = formula_input((cout,), 4) * 0.1
+        g = bf16_round(formula_input((1, cout, images, h, w), 5))
+        _GATHER[name] = dict(x=x, wt=wt, b=b, g=g, ref=F.conv2d(_images(x), wt, b, padding=1),
+                             ref_dx=F.conv_transpose2d(_images(g), wt, padding=1))
+    return _GATHER[name]
+
+
+def _dgrad_weights(G, wt):
+    cout, cin = wt.shape[:2]
+    ctx = G.ctx()
+    with ctx.scope():
+        src = wt.to(DEV).contiguous()
+        wd = torch.empty((cin, cout, 1, 3, 3), dtype=torch.float32, device=DEV)
+        ctx.lib.weight_dgrad_layout(_ptr(src), _ptr(wd), cout, cin, 9, 0, cin, ctx.sptr)
+    torch.cuda.synchronize()
+    assert torch.equal(wd.cpu()[:, :, 0], wt.flip(2, 3).transpose(0, 1))
+    return wd.cpu()
+
+
+def _planned(G, cin, cout, images, h, w):
+    lib, plan, form = G.ctx().lib, C.c_void_p(), (C.c_int * 8)()
+    E = importlib.import_module("video-to-video-diffusion_amd.engine")
+    lib.conv_plan_create(C.byref(plan), C.byref(E.ConvDesc(0, 1, 3, 3, 1, 1, 0, 1, 1, 1, cin, 0, cout, images, h, w, 0)))
+    lib.conv_plan_form(plan, form)
+    lib.conv_plan_destroy(plan)
+    return bool(form[4] & 16), tuple(form[:3])
+
+
+FORMS = [(c, "gather") for c in CONV_CASES] + [(c, t) for c in CONV_CASES for t in c[6]]
+
+
+@pytest.mark.parametrize("case,tile", FORMS, ids=[f"{c[0]}-{t}" for c, t in FORMS])
+def test_planar_conv_forward_and_dgrad(G, monkeypatch, case, tile):
+    """A VGG conv as the loss program plans it -- images along depth, k = (1, 3, 3), pad (0, 1, 1) -- forward and as the data
+    gradient (the same plan on the weights ctsi_weight_dgrad_layout flips and transposes), on the gather kernel and on every
+    tile of the planar halo-tile form, there also with the ReLU epilogue: rel-L2 against torch's fp32 convolution of the same
+    bf16 operands, and the two kernels against each other."""
+    name, cin, cout, images, h, w, _ = case
+    c = _case(name, cin, cout, images, h, w)
+    monkeypatch.setenv("CTSI_CONV_PLANAR", "0" if tile == "gather" else tile)
+    planar, dims = _planned(G, cin, cout, images, h, w)
+    assert (planar, dims) == (True, TILES[tile]) if tile != "gather" else not planar
+    y, _ = G.run_conv(c["x"], None, c["wt"].unsqueeze(2), c["b"], k=K, p=P)
+    assert tuple(y.shape) == (1, cout, images, h, w)
+    wd = _dgrad_weights(G, c["wt"])
+    dx, _ = G.run_conv(c["g"], None, wd, None, k=K, p=P)
+    e_y, e_dx = rel_l2(_images(y), c["ref"]), rel_l2(_images(dx), c["ref_dx"])
+    print(f"[{name} {tile}] forward rel-L2 {e_y:.3e}  dgrad rel-L2 {e_dx:.3e}")
+    assert e_y < CONV_TOL and e_dx < CONV_TOL
+    if tile == "gather":
+        c["gather"] = (y, dx)
+        return
+    # the ReLU epilogue clamps the fp32 accumulators before the one rounding to bf16: exactly relu of the plain output
+    yr, _ = G.run_conv(c["x"], None, c["wt"].unsqueeze(2), c["b"], k=K, p=P, act=2)
+    assert torch.equal(yr, torch.relu(y)) and float((y < 0).float().mean()) > 0.2
+    dxr, _ = G.run_conv(c["g"], None, wd, None, k=K, p=P, act=2)
+    assert torch.equal(dxr, torch.relu(dx))
+    # against the gather kernel (another summation order): test_downsample_conv_on_halo_tile_kernel's bound
+    if "gather" not in c:          # (this case's gather run was deselected)
+        monkeypatch.setenv("CTSI_CONV_PLANAR", "0")
+        c["gather"] = (G.run_conv(c["x"], None, c["wt"].unsqueeze(2), c["b"], k=K, p=P)[0], G.run_conv(c["g"], None, wd, None, k=K, p=P)[0])
+    y2, dx2 = c["gather"]
+    assert float((y - y2).abs().max()) <= 2.0 ** -7 * float(c["ref"].abs().max())
+    assert float((dx - dx2).abs().max()) <= 2.0 ** -7 * float(c["ref_dx"].abs().max())
+
+
+def test_relu_epilogue_is_refused_on_the_gather_kernel(G, monkeypatch):
+    monkeypatch.setenv("CTSI_CONV_PLANAR", "0")
+    c = _case(*CONV_CASES[0][:6])
+    with pytest.raises(importlib.import_module("video-to-video-diffusion_amd").CtsiError, match="ReLU epilogue"):
+        G.run_conv(c["x"], None, c["wt"].unsqueeze(2), c["b"], k=K, p=P, act=2)
+
+
+def test_stem_conv_and_its_dgrad(G):
+    """The 3 -> 64 stem on the 8-channel image (ctsi_conv_plan_set_weight_cin(3)) and its 64 -> 8 data gradient, whose five
+    padding rows are zero weights."""
+    images, h, w = 3, 24, 40
+    x3 = bf16_round(formula_input((1, 3, images, h, w), 1))
+    wt = bf16_round(_w((64, 3, 3, 3), 3))
+    b = formula_input((64,), 4) * 0.1
+    y, _ = G.run_conv(x3, None, wt.unsqueeze(2), b, k=K, p=P, c1_pad=8, cin_w=3)
+    assert rel_l2(_images(y), F.conv2d(_images(x3), wt, b, padding=1)) < CONV_TOL
+    g = bf16_round(formula_input((1, 64, images, h, w), 5))
+    wd = torch.zeros(8, 64, 1, 3, 3)
+    wd[:3, :, 0] = wt.flip(2, 3).transpose(0, 1)
+    dx, _ = G.run_conv(g, None, wd, None, k=K, p=P)
+    assert tuple(dx.shape) == (1, 8, images, h, w) and float(dx[:, 3:].abs().max()) == 0.0
+    assert rel_l2(_images(dx[:, :3]), F.conv_transpose2d(_images(g), wt, padding=1)) < CONV_TOL
+
+
+@pytest.mark.parametrize("tile,images,h,w", [("0", 3, 24, 40), ("1x16x32", 3, 24, 40), ("2x16x16", 3, 24, 40), ("4x8x16", 3, 24, 40),
+                                             ("4x4x24", 5, 12, 24), ("8x4x12", 9, 18, 12)])
+def test_one_hot_tap_copies_the_shifted_input(G, monkeypatch, tile, images, h, w):
+    """One weight tap set to 1: the output is the input shifted by that tap, exactly, zero where the shift leaves the image --
+    and never a pixel of the neighbouring image (the images are the conv's depth axis; a planar tile spans several)."""
+    cin = cout = 64
+    monkeypatch.setenv("CTSI_CONV_PLANAR", tile)
+    assert _planned(G, cin, cout, images, h, w)[0] == (tile != "0")
+    x = bf16_round(formula_input((1, cin, images, h, w), 7))
+    for kh, kw in ((0, 0), (1, 2), (2, 1), (1, 1), (2, 2)):
+        w1 = torch.zeros(cout, cin, 1, 3, 3)
+        for c in range(cout):
+            w1[c, c, 0, kh, kw] = 1.0
+        y, _ = G.run_conv(x, None, w1, None, k=K, p=P)
+        want = F.pad(x, (1, 1, 1, 1))[:, :, :, kh:kh + h, kw:kw + w]     # out[y, x] = in[y + kh - 1, x + kw - 1]
+        assert torch.equal(y, want), (kh, kw)
+
+
+def _nhwc(x_nchw):
+    return x_nchw.permute(0, 2, 3, 1).contiguous().to(device=DEV, dtype=torch.bfloat16)
+
+
+def _nchw(x_nhwc):
+    return x_nhwc.float().cpu().permute(0, 3, 1, 2).contiguous()
+
+
+def test_max_pool_forward_and_backward_with_ties(G):
+    """Half-integer values in [-1.5, 1.5]: most windows hold equal maxima, many of them non-zero.  Forward: torch's values;
+    backward: the gradient goes to the FIRST maximum in (h, w) row-major order, as torch routes it."""
+    n, c, h, w = 3, 72, 6, 10                          # 405 threads: more than one block, a ragged last one
+    gen = torch.Generator().manual_seed(3)
+    x = torch.randint(-3, 4, (n, c, h, w), generator=gen).float() / 2
+    gy = bf16_round(torch.randn(n, c, h // 2, w // 2, generator=gen))
+    xr = x.clone().requires_grad_(True)
+    ref = F.max_pool2d(xr, kernel_size=2, stride=2)
+    ref.backward(gy)
+    win = x.unfold(2, 2, 2).unfold(3, 2, 2).reshape(n, c, h // 2, w // 2, 4)
+    tied = (win == win.amax(-1, keepdim=True)).sum(-1) > 1
+    assert float((tied & (win.amax(-1) != 0)).float().mean()) > 0.2       # ties between equal NON-ZERO values
+    ctx = G.ctx()
+    xb, gb = _nhwc(x), _nhwc(gy)
+    y = torch.full((n, h // 2, w // 2, c), float("nan"), dtype=torch.bfloat16, device=DEV)
+    gx = torch.full((n, h, w, c), float("nan"), dtype=torch.bfloat16, device=DEV)
+    with ctx.scope():
+        ctx.lib.maxpool2_fwd(_ptr(xb), _ptr(y), n, h, w, c, ctx.sptr)
+        ctx.lib.maxpool2_bwd(_ptr(xb), _ptr(gb), _ptr(gx), n, h, w, c, ctx.sptr)
+    torch.cuda.synchronize()
+    assert torch.equal(_nchw(y), ref.detach())
+    assert torch.equal(_nchw(gx), xr.grad)
+    # the device's own torch pooling routes ties the same way (the end-to-end truth is evaluated there)
+    xd = x.to(DEV).requires_grad_(True)
+    F.max_pool2d(xd, kernel_size=2, stride=2).backward(gy.to(DEV))
+    assert torch.equal(xd.grad.cpu(), xr.grad)
+
+
+def test_relu_in_place(G):
+    gen = torch.Generator().manual_seed(4)
+    x = bf16_round(torch.randn(8 * 333, generator=gen))
+    x[::7] = 0.0
+    x[3::11] = -0.0
+    xb = x.to(device=DEV, dtype=torch.bfloat16)
+    ctx = G.ctx()
+    with ctx.scope():
+        ctx.lib.relu_bf16(_ptr(xb), xb.numel(), ctx.sptr)
+    torch.cuda.synchronize()
+    out = xb.float().cpu()
+    assert torch.equal(out, torch.relu(x)) and not torch.signbit(out).any()
+
+
+@pytest.mark.parametrize("b,d,rate", [(2, 10, 0.2), (1, 5, 1.0), (3, 4, 0.5)])
+def test_prep_and_its_backward(G, b, d, rate):
+    h, w = 16, 24
+    gen = torch.Generator().manual_seed(5)
+    x = (torch.rand(b, 1, d, h, w, generator=gen) * 2 - 1).to(DEV)
+    idx = slice_indices(d, rate)
+    num = idx.numel()
+    slices = idx.to(device=DEV, dtype=torch.int32)
+    norm = torch.tensor(MEAN + STD, dtype=torch.float32, device=DEV)
+    img = torch.full((b * num, h, w, 8), float("nan"), dtype=torch.bfloat16, device=DEV)
+    g = bf16_round(torch.randn(b * num, 8, h, w, generator=gen))
+    grad = torch.full((b, 1, d, h, w), float("nan"), dtype=torch.float32, device=DEV)
+    ctx = G.ctx()
+    gb = _nhwc(g)
+    with ctx.scope():
+        ctx.lib.vgg_prep(_ptr(x), _ptr(slices), _ptr(norm), _ptr(img), b, d, num, h, w, ctx.sptr)
+        ctx.lib.vgg_prep_bwd(_ptr(gb), _ptr(slices), _ptr(norm), _ptr(grad), b, d, num, h, w, ctx.sptr)
+    torch.cuda.synchronize()
+    # forward: the torch expressions in fp32, rounded to bf16 once; channels 3-7 zero
+    want = to_rgb(x, rate).to(torch.bfloat16).float().cpu()
+    got = _nchw(img)
+    assert torch.equal(got[:, :3], want) and float(got[:, 3:].abs().max()) == 0.0
+    # backward: autograd of the same expressions in float64; exactly zero on the slices that were not sampled
+    xr = x.double().cpu().requires_grad_(True)
+    to_rgb(xr, rate).backward(g[:, :3].double())
+    got = grad.cpu()
+    assert rel_l2(got, xr.grad.float()) < 1e-6
+    unsampled = [s for s in range(d) if s not in idx.tolist()]
+    assert float(got[:, :, unsampled].abs().max() if unsampled else 0.0) == 0.0
+    assert float(got[:, :, idx].abs().min()) > 0.0
+
+
+@pytest.mark.parametrize("squared", [0, 1])
+def test_feature_distance_against_float64(G, squared):
+    gen = torch.Generator().manual_seed(6)
+    counts = [8 * (256 * 3 + 5), 8 * 40000]              # fewer units than threads in the grid / several rounds of it
+    ctx = G.ctx()
+    blocks = ctx.lib.feat_loss_blocks()
+    partials = torch.full((len(counts) * blocks,), float("nan"), dtype=torch.float64, device=DEV)
+    out = torch.full((1 + len(counts),), float("nan"), dtype=torch.float32, device=DEV)
+    cnt = torch.tensor(counts, dtype=torch.int64, device=DEV)
+    means, keep = [], []
+    with ctx.scope():
+        for l, n in enumerate(counts):
+            p, t = bf16_round(torch.randn(n, generator=gen)), bf16_round(torch.randn(n, generator=gen))
+            diff = p.double() - t.double()
+            means.append(float((diff * diff).mean() if squared else diff.abs().mean()))
+            pb, tb = p.to(device=DEV, dtype=torch.bfloat16), t.to(device=DEV, dtype=torch.bfloat16)
+            keep += [pb, tb]
+            ctx.lib.feat_loss_fwd(_ptr(pb), _ptr(tb), n, squared, C.c_void_p(partials.data_ptr() + 8 * l * blocks), ctx.sptr)
+        ctx.lib.feat_loss_finalize(_ptr(partials), _ptr(cnt), len(counts), _ptr(out), ctx.sptr)
+    torch.cuda.synchronize()
+    got = out.double().cpu()
+    # worst case of the arithmetic: fp32 per 8 elements (a product or |.|, three levels of adds: 4 roundings of 2^-24), fp64 from
+    # there on, one rounding to fp32 at the end -- 5 x 2^-24, held to 2^-21
+    for l, m in enumerate(means):
+        assert abs(float(got[1 + l]) - m) <= 2.0 ** -21 * m, (l, float(got[1 + l]), m)
+    assert abs(float(got[0]) - sum(means) / len(means)) <= 2.0 ** -21 * sum(means) / len(means)
+
+
+@pytest.mark.parametrize("kind,relu,with_g", [(1, 1, True), (2, 1, True), (0, 1, True), (1, 0, False), (2, 0, True), (1, 1, False)])
+def test_feature_gradient_pass_against_float64(G, kind, relu, with_g):
+    """g_out = (g_in + coef * grad_loss * f(y - t)) * [y > 0] on a post-ReLU y with exact zeros and exact y == t ties."""
+    gen = torch.Generator().manual_seed(7)
+    n = 8 * (256 * 5 + 3)
+    y = bf16_round(torch.randn(n, generator=gen))
+    if relu:
+        y = torch.relu(y)
+    t = bf16_round(torch.randn(n, generator=gen))
+    t[::5] = y[::5]                                     # sign(0) = 0
+    g = bf16_round(torch.randn(n, generator=gen) * 1e-3)
+    coef, gl = 1.0 / 4096, 0.75
+    term = {0: torch.zeros(n, dtype=torch.float64), 1: torch.sign(y.double() - t.double()),
+            2: 2 * (y.double() - t.double())}[kind] * coef * gl
+    want = (g.double() if with_g else 0.0) + term
+    if relu:
+        want = want * (y > 0)
+    ctx = G.ctx()
+    yb, tb, gb = (v.to(device=DEV, dtype=torch.bfloat16) for v in (y, t, g))
+    out = torch.full((n,), float("nan"), dtype=torch.bfloat16, device=DEV)
+    gld = torch.tensor([gl], dtype=torch.float32, device=DEV)
+    with ctx.scope():
+        ctx.lib.feat_grad_relu_bwd(_ptr(gb) if with_g else None, _ptr(yb), _ptr(tb), _ptr(out), n, coef, kind, relu, _ptr(gld),
+                                   ctx.sptr)
+    torch.cuda.synchronize()
+    got = out.double().cpu()
+    # one fp32 evaluation rounded to bf16 once: half a bf16 ulp of the result, plus the fp32 roundings inside (a product, a
+    # sum of two terms of the result's size: 2^-20 covers them)
+    assert float(((got - want).abs() - (2.0 ** -8 + 2.0 ** -20) * want.abs()).max()) <= 1e-30
+    if relu:
+        assert float(got[y <= 0].abs().max()) == 0.0
+    if with_g:                # in place, as the program runs it
+        with ctx.scope():
+            ctx.lib.feat_grad_relu_bwd(_ptr(gb), _ptr(yb), _ptr(tb), _ptr(gb), n, coef, kind, relu, _ptr(gld), ctx.sptr)
+        torch.cuda.synchronize()
+        assert torch.equal(gb, out)

@@ -811,6 +811,10 @@ extern "C" int ctsi_conv_fwd(const ctsi_conv_plan* p, const void* x1, const void
                        "(cout=%d stride=%d off=%d)", p->d.cout, o->cout_stride, o->c_off);
     }
     const ConvFamily family = conv_family(p);
+    CTSI_CHECK_ARG(o->act != 2 || (p->planar && o->mode == 0 && o->colsum == nullptr && o->gn_x == nullptr),
+                   "ctsi_conv_fwd: the ReLU epilogue (act = 2) exists on planar (1,3,3) halo-tile plans with plain bf16 output "
+                   "only (ctsi_conv_plan_form: bit 16 of out[4])");
+    CTSI_CHECK_ARG(!p->planar || o->colsum == nullptr, "ctsi_conv_fwd: a planar (1,3,3) halo-tile plan writes no column sums");
     if (p->stem && o->mode == 0 && o->act == 0 && o->gn_x == nullptr) {
         StemParams q;
         memset(&q, 0, sizeof(q));
@@ -862,7 +866,7 @@ extern "C" int ctsi_conv_fwd(const ctsi_conv_plan* p, const void* x1, const void
                            o->gn_count > 0,
                        "ctsi_conv_fwd: bad fused GroupNorm arguments (groups=%d, cout=%d)", o->gn_groups, p->d.cout);
     }
-    if (p->form && (family == CONV_HEAD || (o->mode == 0 && o->act == 0))) {
+    if (p->form && (family == CONV_HEAD || (o->mode == 0 && (o->act == 0 || o->act == 2)))) {
         Conv3HaloParams h;
         memset(&h, 0, sizeof(h));
         h.x1 = (const bf16_t*)x1;
@@ -927,6 +931,7 @@ extern "C" int ctsi_conv_fwd(const ctsi_conv_plan* p, const void* x1, const void
             h.sk_sync = (int*)o->workspace;
             h.sk_ws = (float*)((char*)o->workspace + ((size_t)tiles * 8 + 255) / 256 * 256);
         }
+        if (p->planar) return ctsi_conv3_planar_k32_launch(&h, p->form->code, o->act == 2, stream);
         if (family == CONV_K32) return ctsi_conv3_halo_k32_launch(&h, p->form->code, p->BN, stream);
         return ctsi_conv3_halo_launch(&h, p->form->code, stream);
     }

@@ -49,6 +49,7 @@ struct ctsi_conv_plan {
     int gsplit;     // gather kernel: S-way split-K for launches of a few dozen blocks with a deep K loop (needs a workspace)
     int ds;         // k32 kernel: the strided (3,4,4)/(1,2,2) Downsample form (conv3_halo_k32.hip, DS)
     int head2;      // head: conv3_head2_kernel (taps as the GEMM's N dimension) serves the launches that ask for no column sums
+    int planar;     // k32 kernel: the planar (1,3,3) form (conv3_halo_k32.hip, PL): depth slices are independent images
     int ksplit;     // k32 kernel: 2 = two blocks per (tile, n-tile), each half of the input-channel chunks (needs a workspace)
     int stem;       // 1: conv3_stem_kernel (conv3_stem.hip: 3x3x3 conv of a one-channel volume stored with 8 channels); chosen by
                     // ctsi_conv_plan_set_weight_cin(plan, 1)
@@ -58,8 +59,9 @@ struct ctsi_conv_plan {
 };
 
 static inline ConvFamily conv_family(const ctsi_conv_plan* p) { return p->form ? p->form->family : CONV_GATHER; }
-// k32 plans: the packed image's form (0 Conv3d 3x3x3, 1 ConvTranspose3d, 2 strided Conv3d) and whether it is cout-permuted
-static inline int conv_k32_image(const ctsi_conv_plan* p) { return p->ds ? 2 : p->d.transposed; }
+// k32 plans: the packed image's form (0 Conv3d 3x3x3, 1 ConvTranspose3d, 2 strided Conv3d, 3 planar Conv3d (1,3,3)) and whether
+// it is cout-permuted
+static inline int conv_k32_image(const ctsi_conv_plan* p) { return p->planar ? 3 : p->ds ? 2 : p->d.transposed; }
 static inline int conv_k32_direct(const ctsi_conv_plan* p) { return ctsi_conv3_halo_k32_direct(p->form->code, p->ksplit, p->ds); }
 // few-cout heads: the packed buffer holds conv3_head_kernel's image, padded to 256 B, then conv3_head2_kernel's
 static inline size_t head1_bytes(const ctsi_conv_plan* p) {

@@ -18,7 +18,7 @@ static const double EFF_ST_512 = 1.0, EFF_ST_384 = 0.96;
 static const double EFF_GATHER_STANDIN = 0.6;
 
 enum FormId { H32_4x2x32, H32_4x4x16, H32_3x4x16, K32_4x4x32, K32_4x8x16, K32_3x4x32, K32_3x8x16, K32_4x4x24, K32_8x4x12, HEAD_4x2x16,
-              N_FORMS };
+              PL_1x16x32, PL_2x16x16, PL_4x8x16, PL_4x4x24, PL_8x4x12, N_FORMS };
 // codes: `wide` 1 / 3 / 4 of ctsi_conv3_halo_launch (conv3_halo.hip), `tile` 0 / 2 / 3 / 5 / 6 / 7 of ctsi_conv3_halo_k32_launch
 // (conv3_halo_k32.hip); the 4x4x24 / 8x4x12 tiles are A tiles that straddle W-lines, for 24- / 12-wide planes
 static const ConvForm FORMS[N_FORMS] = {
@@ -32,6 +32,13 @@ static const ConvForm FORMS[N_FORMS] = {
     {CONV_K32, 9, 4, 4, 24, 128, 6, EFF_K32_NARROW, "k32 4x4x24"},
     {CONV_K32, 9, 8, 4, 12, 128, 7, EFF_K32_NARROW, "k32 8x4x12"},
     {CONV_HEAD, 8, 4, 2, 16, 16, 0, 1.0, "head 4x2x16"},                    // x 16 couts, see conv3_head.hip
+    // the planar (1,3,3) form of the k32 kernel (codes 16-20 of ctsi_conv3_planar_k32_launch): td counts depth slices, which
+    // are independent images; no depth halo, so the flat tiles stage the fewest halo voxels per output voxel
+    {CONV_K32, 9, 1, 16, 32, 128, 16, EFF_K32_512, "planar 1x16x32"},
+    {CONV_K32, 9, 2, 16, 16, 128, 17, EFF_K32_512, "planar 2x16x16"},
+    {CONV_K32, 9, 4, 8, 16, 128, 18, EFF_K32_512, "planar 4x8x16"},
+    {CONV_K32, 9, 4, 4, 24, 128, 19, EFF_K32_NARROW, "planar 4x4x24"},
+    {CONV_K32, 9, 8, 4, 12, 128, 20, EFF_K32_NARROW, "planar 8x4x12"},
 };
 static int form_voxels(const ConvForm& f) { return f.td * f.th * f.tw; }
 // the 384-voxel / 512-voxel k32 tile of the same width
@@ -45,6 +52,7 @@ enum SplitK { SK_UNSET, SK_OFF, SK_ON, SK_PLAIN, SK_512 };
 struct PlanEnv {
     bool no_halo3, force_halo3, no_c16, no_head3, no_head2, no_fast;
     Tri m512, m512w16, k32_384, k32t, k32d, narrow, narrow_sk, linear;
+    int planar;               // -1: unset, 0: the gather kernel, 1: the planar form wherever it applies, 16-20: that tile where it applies
     int halo_tile;            // 16 | 32, 0: unset
     int h32w16;               // 1 | 2, 0: unset
     SplitK splitk;
@@ -73,6 +81,14 @@ static PlanEnv read_plan_env() {
     e.k32_384 = env_tri("CTSI_CONV_K32_384");
     e.k32t = env_tri("CTSI_CONV_K32T");                // 0: ConvTranspose3d stays on the gather kernel
     e.k32d = env_tri("CTSI_CONV_K32D");                // 0: the strided Conv3d stays on the gather kernel
+    {   // CTSI_CONV_PLANAR: "0" the (1,3,3) convs stay on the gather kernel | "1" the planar form wherever it applies | a tile
+        // ("1x16x32", "2x16x16", "4x8x16", "4x4x24", "8x4x12"): that tile wherever it applies (A/B timing, parity tests)
+        const char* pl = getenv("CTSI_CONV_PLANAR");
+        e.planar = -1;
+        if (pl && (!strcmp(pl, "0") || !strcmp(pl, "1"))) e.planar = pl[0] - '0';
+        for (int f = PL_1x16x32; pl && f <= PL_8x4x12; ++f)
+            if (!strcmp(pl, FORMS[f].name + 7)) e.planar = FORMS[f].code;   // (the name behind "planar ")
+    }
     e.narrow = env_tri("CTSI_CONV_K32_NARROW");        // 0 / 1: never / wherever the plane divides
     e.narrow_sk = env_tri("CTSI_CONV_K32_NARROW_SK");  // 0 / 1: never / wherever K allows
     e.linear = env_tri("CTSI_CONV_LINEAR");
@@ -379,8 +395,9 @@ static void choose_k32_strided_form(ctsi_conv_plan* p, const PlanEnv& e) {
         return;
     const ConvForm* best = nullptr;
     TileFit bf = {0, 0.0, -1.0};
-    for (const ConvForm& c : FORMS) {
-        if (c.family != CONV_K32 || (c.tw % 16 != 0 && (!narrow_fits(p, c) || e.narrow == OFF))) continue;
+    for (int fi = K32_4x4x32; fi <= K32_8x4x12; ++fi) {   // (the 3x3x3 halo tiles; the planar rows have no depth halo)
+        const ConvForm& c = FORMS[fi];
+        if (c.tw % 16 != 0 && (!narrow_fits(p, c) || e.narrow == OFF)) continue;
         const TileFit f = fit(p, c, 1, ds ? 1 : 4, form_voxels(c) == 512 ? EFF_ST_512 : EFF_ST_384);
         if (ds && f.useful < 0.7 && !e.force_halo3) continue;   // (a 32-wide tile on a 16-wide plane)
         if (f.score > bf.score) { best = &c; bf = f; }
@@ -402,6 +419,34 @@ static void choose_k32_strided_form(ctsi_conv_plan* p, const PlanEnv& e) {
             p->ksplit = 2;
         }
     }
+}
+
+// Planar Conv3d (1,3,3) / stride 1 / pad (0,1,1) with whole 16-channel chunks per source and >= 64 couts (the VGG-19 stack of
+// the perceptual loss: images along depth) on the k32 kernel's planar form; the gather kernel re-stages the activation slab
+// per tap.  Scored like the other forms -- useful tile rows x CU fill x efficiency; a form must cover the row grid at >= 70 %
+// (planes too small for a tile stay on the gather kernel, as does the 3 -> 64 stem with its 8 stored channels).  Deep-K layers
+// on a grid of at most half a round of the CUs (512 -> 512 over a few dozen 12^2 planes) also stay there: the gather kernel's
+// 128-row tiles with S-way split-K (choose_gather_split) put 2-4 x as many blocks on the chip.
+static void choose_planar_form(ctsi_conv_plan* p, const PlanEnv& e) {
+    const ctsi_conv_desc& d = p->d;
+    if (!(!d.transposed && d.kd == 1 && d.kh == 3 && d.kw == 3 && d.sh == 1 && d.sw == 1 && d.pd == 0 && d.ph == 1 && d.pw == 1 &&
+          !p->dshift && d.c1 % 16 == 0 && d.c2 % 16 == 0 && d.cout >= 64 && d.cout % 8 == 0 && halo_fits(p)))
+        return;
+    if (e.planar == 0 || e.no_halo3) return;
+    const ConvForm* best = nullptr;
+    TileFit bf = {0, 0.0, -1.0};
+    for (int f = PL_1x16x32; f <= PL_8x4x12; ++f) {
+        const ConvForm& c = FORMS[f];
+        if (c.tw % 16 != 0 && !narrow_fits(p, c)) continue;
+        if (e.planar >= 16 && c.code != e.planar) continue;
+        const TileFit t = fit(p, c, 1, 1, c.eff);
+        if (t.useful < 0.7 && e.planar < 16) continue;
+        if (t.score > bf.score) { best = &c; bf = t; }
+    }
+    if (!best) return;
+    if (e.planar < 1 && bf.blocks <= 128 && p->Cin >= 256) return;
+    p->form = best;
+    p->planar = 1;
 }
 
 // few output channels (network heads: 128 -> 8, 128 -> 1)
@@ -477,6 +522,7 @@ extern "C" int ctsi_conv_plan_create(ctsi_conv_plan** out, const ctsi_conv_desc*
     plan_k_walk(p);
     choose_gather_tile(p, e);
     if (is_k3(d)) choose_k3_form(p, e);
+    else if (d.kd == 1 && d.kh == 3) choose_planar_form(p, e);
     else choose_k32_strided_form(p, e);
     choose_head_form(p, e);
     if (p->form) {
@@ -545,7 +591,7 @@ extern "C" int ctsi_conv_plan_form(const ctsi_conv_plan* p, int out[8]) {
     memset(out, 0, 8 * sizeof(int));
     out[0] = p->TD; out[1] = p->TH; out[2] = p->TW;
     if (!p->stem && !p->stream1) out[3] = conv_family(p) == CONV_K32 ? p->ksplit : (p->form ? 0 : p->gsplit);
-    out[4] = (p->linear ? 1 : 0) | (p->fast ? 2 : 0) | (p->head2 ? 4 : 0) | (p->ds ? 8 : 0);
+    out[4] = (p->linear ? 1 : 0) | (p->fast ? 2 : 0) | (p->head2 ? 4 : 0) | (p->ds ? 8 : 0) | (p->planar ? 16 : 0);
     return CTSI_OK;
 }
 

@@ -217,4 +217,5 @@ extern "C" int ctsi_conv3_halo_k32_pack(const float* w, void* packed, int cout, 
 extern "C" int ctsi_conv3_halo_k32_direct(int tile, int ksplit, int ds);   // 1: the form stores straight from the accumulators (cout-permuted image)
 extern "C" size_t ctsi_conv3_halo_k32_splitk_bytes(int tiles);
 extern "C" int ctsi_conv3_halo_k32_launch(const Conv3HaloParams* hp, int tile, int bn, void* stream);
+extern "C" int ctsi_conv3_planar_k32_launch(const Conv3HaloParams* hp, int tile, int relu, void* stream);   // the (1,3,3) form, tiles 16-20
 

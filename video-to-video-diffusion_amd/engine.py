@@ -199,9 +199,9 @@ class _ConvPlan(NamedTuple):
 
 
 def _conv_label(bm: int, bn: int, mode: int, desc: ConvDesc, split_k: bool) -> str:
-    """conv_mfma_<bm>x<bn>_m<mode>[t|d][s] -- t: ConvTranspose form, d: Downsample form (both of the k32 family, mode 9),
-    s: split-K form."""
-    form = "t" if desc.transposed else ("d" if (desc.sh, desc.sw) == (2, 2) else "")
+    """conv_mfma_<bm>x<bn>_m<mode>[t|d|p][s] -- t: ConvTranspose form, d: Downsample form, p: planar (1,3,3) form (all of the
+    k32 family, mode 9), s: split-K form."""
+    form = "t" if desc.transposed else ("d" if (desc.sh, desc.sw) == (2, 2) else ("p" if desc.kd == 1 and desc.kh == 3 else ""))
     return "conv_mfma_%dx%d_m%d%s%s" % (bm, bn, mode, form if mode == 9 else "", "s" if split_k else "")
 
 

@@ -164,6 +164,15 @@ SIGNATURES = {
     "ctsi_msssim_workspace_bytes": (_sz, [_i, _i, _i, _i, _i], False),
     "ctsi_msssim_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp], True),
     "ctsi_msssim_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp], True),
+    "ctsi_vgg_prep": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_vgg_prep_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_maxpool2_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp], True),
+    "ctsi_maxpool2_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp], True),
+    "ctsi_relu_bf16": (_i, [_vp, _ll, _vp], True),
+    "ctsi_feat_loss_blocks": (_i, [], False),
+    "ctsi_feat_loss_fwd": (_i, [_vp, _vp, _ll, _i, _vp, _vp], True),
+    "ctsi_feat_loss_finalize": (_i, [_vp, _vp, _i, _vp, _vp], True),
+    "ctsi_feat_grad_relu_bwd": (_i, [_vp, _vp, _vp, _vp, _ll, _f, _i, _i, _vp, _vp], True),
     "ctsi_device_error_status": (_i, [C.POINTER(C.c_uint), C.POINTER(C.c_uint), _i], True),
     "ctsi_conv_f32_supported": (_i, [C.POINTER(ConvDesc)], False),
     "ctsi_conv_f32_weight_bytes": (_sz, [C.POINTER(ConvDesc)], False),

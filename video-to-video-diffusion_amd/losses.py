@@ -3,8 +3,24 @@
 `MS_SSIM_Loss` (losses.py:149-276) is a differentiable loss here: forward and backward are HIP launches
 (csrc/msssim.hip) behind a `torch.autograd.Function`, 6 launches forward and 5 backward, with no
 host read in either direction.  `CombinedLoss` (losses.py:279-361) keeps the reference's bookkeeping around it.
-`VGGPerceptualLoss` needs torchvision and downloaded VGG-19 weights and stays out of scope: it
-raises `NotImplementedError`, so `CombinedLoss(lambda_perceptual=0, ...)` is the usable setting.
+`VGGPerceptualLoss` (losses.py:22-146) runs on the engine too (vgg_loss_engine.py, csrc/vgg_loss.hip),
+forward and backward, once it is given VGG-19 `features` weights: `VGGPerceptualLoss(weights=state_dict_or_path)`.  The
+reference fetches them with `torchvision.models.vgg19(pretrained=True)`; the engine depends on neither the package nor a
+download, and NO weights ship with the project: save `torchvision.models.vgg19(weights="IMAGENET1K_V1").features.state_dict()`
+(or the whole model's state dict) on a machine that has torchvision and pass the file.  Without `weights` the constructor
+raises `NotImplementedError`, so a `CombinedLoss` needs `c.perceptual_loss = VGGPerceptualLoss(weights=...)` before its
+perceptual term is first due, or `lambda_perceptual=0`.
+
+Semantics of `VGGPerceptualLoss(...)(pred, target)`, both (B, 1, D, H, W) in [-1, 1]: `num = max(1, int(D * rate))` slices per
+sample at `torch.linspace(0, D - 1, num, dtype=torch.long)` (all of them when num >= D); each slice becomes the 3-channel image
+`((x + 1) / 2 - mean_c) / std_c`; the VGG-19 `features` stack is cut into blocks `features[prev : idx + 1]` for idx in
+`feature_layers`; the loss is the mean over blocks of `F.l1_loss` (`use_l1=False`: `F.mse_loss`) between the block outputs of
+pred and target.  torchvision's ReLUs are in place: a block that ends on a conv and is followed by another block is compared
+AFTER the next block's leading ReLU has overwritten it, so with the default list the features of convs 2, 7, 12, 21 are
+post-ReLU and that of conv 30 is pre-ReLU.  Deviations from the reference: H and W must be multiples of 16 (`ValueError`; the
+training sizes are 192 and 512); the tensors must be ROCm tensors (`CtsiError`, as for `MS_SSIM_Loss`); the gradient is computed
+for `pred` only (`target` is detached, as the reference's `no_grad` does); activations are bf16 with fp32 accumulation, like
+every engine layer -- the test criterion is the error of the same torch ops under bf16 autocast.
 
 Semantics of `MS_SSIM_Loss()(pred, target)`, both (B, C, D, H, W) in [-1, 1]: every (b, c, d) plane is an H x W image
 of `(v + 1) / 2`; five levels of the full SSIM map under the zero-padded 11 x 11 Gaussian window (sigma 1.5), the
@@ -15,7 +31,8 @@ torch's `pow` does in the reference.  The gradient is computed for `pred` only.
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Tuple
+import os
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -23,6 +40,7 @@ from torch.autograd.function import once_differentiable
 
 from .engine import Ctx, _ptr
 from .lib import CtsiError
+from .vgg_loss_engine import VGG19_MODULES, VGGLossProgram
 
 MIN_SIZE = 16          # four 2 x 2 pools must leave at least one pixel
 MAX_WINDOW = 15        # csrc/msssim.hip: odd windows 1 .. 15
@@ -85,13 +103,168 @@ class _MSSSIMFn(torch.autograd.Function):
         return grad_pred, None, None, None, None
 
 
-class VGGPerceptualLoss(nn.Module):
-    """Not available: the reference's perceptual loss needs torchvision and downloaded VGG-19 weights."""
+def _vgg_state_dict(weights) -> Dict[str, torch.Tensor]:
+    """A state dict, or a path to one saved with torch.save (loaded with weights_only=True)."""
+    if isinstance(weights, (str, os.PathLike)):
+        weights = torch.load(weights, map_location="cpu", weights_only=True)
+    if not isinstance(weights, dict):
+        raise ValueError(f"weights must be a state dict or a path to one, got {type(weights).__name__}")
+    return weights
 
-    def __init__(self, feature_layers: list = [2, 7, 12, 21, 30], use_l1: bool = True, slice_sample_rate: float = 0.2):
-        raise NotImplementedError(
-            "VGGPerceptualLoss needs torchvision and pre-trained VGG-19 weights fetched from the network; it is out of "
-            "scope for the HIP engine (DESIGN.md section 7).  Use CombinedLoss(lambda_perceptual=0, ...) or MS_SSIM_Loss.")
+
+def _vgg_param(sd: Dict[str, torch.Tensor], idx: int, kind: str, shape: Tuple[int, ...]) -> torch.Tensor:
+    """`features.{idx}.{kind}` or `{idx}.{kind}` (torchvision's names for the whole model / its `features`), shape-checked."""
+    names = (f"features.{idx}.{kind}", f"{idx}.{kind}")
+    name = next((n for n in names if n in sd), None)
+    if name is None:
+        raise ValueError(f"VGG-19 weights: key '{names[0]}' (or '{names[1]}') is missing")
+    t = sd[name]
+    if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape):
+        got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"VGG-19 weights: key '{name}' has shape {got}, expected {tuple(shape)}")
+    return t
+
+
+class _VGGLossFn(torch.autograd.Function):
+    """loss = mean over feature blocks of the L1 / L2 feature distance; backward gives pred's gradient (fp32 NCDHW, exactly
+    zero on unsampled slices)."""
+
+    @staticmethod
+    def forward(fctx, pred, target, owner, want_grad):
+        ctx = Ctx.get(pred.device)
+        b, _, d, h, w = pred.shape
+        idx = owner.slice_indices(d)
+        num = idx.numel()
+        with ctx.scope():
+            slices = idx.to(device=pred.device, dtype=torch.int32)
+            norm = torch.cat([owner.mean.reshape(-1), owner.std.reshape(-1)]).to(device=pred.device, dtype=torch.float32)
+            prog = owner._take_program(ctx, b * num, h, w)
+            out = prog.run_forward(pred, target, slices, norm, b, d, num)
+        owner.last_layer_means = out[1:]
+        if want_grad:
+            fctx.save_for_backward(slices, norm)
+            fctx.prog, fctx.owner, fctx.generation, fctx.dims = prog, owner, prog.generation, (b, d, num)
+        else:
+            owner._give_program(prog)          # every use is ordered on the engine stream
+        return out[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(fctx, grad_loss):
+        prog = getattr(fctx, "prog", None)
+        if prog is None:
+            raise CtsiError("VGGPerceptualLoss: backward ran twice on one forward (the saved activations are released after "
+                            "the first backward); run the forward again")
+        slices, norm = fctx.saved_tensors
+        b, d, num = fctx.dims
+        with prog.ctx.scope():
+            g = grad_loss.detach().to(torch.float32).contiguous()
+            grad_pred = prog.run_backward(g, slices, norm, b, d, num, fctx.generation)
+        fctx.owner._give_program(prog)
+        fctx.prog = None
+        return grad_pred, None, None, None
+
+
+class VGGPerceptualLoss(nn.Module):
+    """The reference's VGG-19 perceptual loss on sampled 2-D slices, forward and backward on the HIP engine.
+
+    Args as the reference's (feature_layers: strictly increasing indices into VGG-19 `features`, 0-36; use_l1; slice_sample_rate)
+    plus the keyword `weights`: a state dict of torchvision's VGG-19 (`features.{i}.weight / bias`) or of its `features`
+    (`{i}.weight / bias`), or a path to one (`torch.load(..., weights_only=True)`).  Only the convs up to max(feature_layers)
+    are read; they are held frozen under the reference's names `vgg_blocks.{block}.{j}`.  `weights=None` raises
+    `NotImplementedError`: the engine neither imports torchvision nor downloads, and no weights ship with the project.
+    `last_layer_means` holds the per-block distances of the latest forward as a device tensor.  See the module docstring for
+    the semantics and the deviations (H, W multiples of 16; ROCm tensors; gradient for `pred` only)."""
+
+    def __init__(self, feature_layers: list = [2, 7, 12, 21, 30], use_l1: bool = True, slice_sample_rate: float = 0.2, *,
+                 weights: Optional[Union[Dict[str, torch.Tensor], str, "os.PathLike"]] = None):
+        if weights is None:
+            raise NotImplementedError(
+                "VGGPerceptualLoss needs pre-trained VGG-19 weights, which the reference fetches through torchvision from the "
+                "network; the HIP engine does neither.  Pass them: VGGPerceptualLoss(weights=<state dict or path of "
+                "torchvision's vgg19 / vgg19().features>) (DESIGN.md section 22), or use CombinedLoss(lambda_perceptual=0, ...) "
+                "or MS_SSIM_Loss.")
+        super().__init__()
+        layers = list(feature_layers)
+        if (not layers or any(not isinstance(v, int) or isinstance(v, bool) for v in layers) or layers[0] < 0
+                or layers[-1] >= len(VGG19_MODULES) or any(a >= b for a, b in zip(layers, layers[1:]))):
+            raise ValueError(f"feature_layers must be strictly increasing indices into VGG-19 features (0-"
+                             f"{len(VGG19_MODULES) - 1}), got {feature_layers!r}")
+        if not 0.0 <= float(slice_sample_rate):
+            raise ValueError(f"slice_sample_rate must not be negative, got {slice_sample_rate!r}")
+        sd = _vgg_state_dict(weights)
+        self.feature_layers = layers
+        self.use_l1 = use_l1
+        self.slice_sample_rate = slice_sample_rate
+        self.vgg_blocks = nn.ModuleList()
+        self._convs: Dict[int, nn.Conv2d] = {}
+        prev = 0
+        for idx in layers:
+            block = []
+            for i in range(prev, idx + 1):
+                m = VGG19_MODULES[i]
+                if m[0] == "conv":
+                    conv = nn.Conv2d(m[1], m[2], kernel_size=3, padding=1)
+                    with torch.no_grad():
+                        conv.weight.copy_(_vgg_param(sd, i, "weight", (m[2], m[1], 3, 3)))
+                        conv.bias.copy_(_vgg_param(sd, i, "bias", (m[2],)))
+                    self._convs[i] = conv
+                    block.append(conv)
+                elif m[0] == "relu":
+                    block.append(nn.ReLU(inplace=True))
+                else:
+                    block.append(nn.MaxPool2d(kernel_size=2, stride=2))
+            self.vgg_blocks.append(nn.Sequential(*block))
+            prev = idx + 1
+        for p in self.parameters():
+            p.requires_grad = False
+        self.eval()
+        self.register_buffer('mean', torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1))
+        self.register_buffer('std', torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1))
+        self.last_layer_means = None
+
+    def slice_indices(self, depth: int) -> torch.Tensor:
+        """The sampled slices of a volume of `depth` slices (host, int64): the reference's own expression."""
+        num = max(1, int(depth * self.slice_sample_rate))
+        if num < depth:
+            return torch.linspace(0, depth - 1, num, dtype=torch.long)
+        return torch.arange(depth, dtype=torch.long)
+
+    # free programs per (device index, images, h, w), kept where engine.invalidate_engine_cache finds them.  A forward in grad
+    # mode owns its program (it holds the activations) until its backward has run, so two losses of one shape in one graph
+    # never share one; a program that comes back after the cache was dropped is not kept.
+    def _take_program(self, ctx: Ctx, n_img: int, h: int, w: int) -> VGGLossProgram:
+        key = (ctx.device.index, n_img, h, w)
+        cache = self.__dict__.setdefault("_ctsi_programs", {})
+        free = cache.setdefault(key, [])
+        if free:
+            return free.pop()
+        prog = VGGLossProgram(ctx, self._convs, self.feature_layers, bool(self.use_l1), n_img, h, w)
+        prog.key, prog.home = key, cache
+        return prog
+
+    def _give_program(self, prog: VGGLossProgram):
+        if self.__dict__.get("_ctsi_programs") is prog.home:
+            prog.home.setdefault(prog.key, []).append(prog)
+
+    def forward(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if not isinstance(pred, torch.Tensor) or not isinstance(target, torch.Tensor) or pred.dim() != 5:
+            raise ValueError("VGGPerceptualLoss expects two (B, 1, D, H, W) tensors")
+        if pred.shape != target.shape:
+            raise ValueError(f"shape mismatch: pred {tuple(pred.shape)} vs target {tuple(target.shape)}")
+        if pred.shape[1] != 1:
+            raise AssertionError("Expected grayscale input (C=1)")
+        if pred.numel() == 0:
+            raise ValueError("VGGPerceptualLoss got an empty tensor")
+        if pred.shape[3] % 16 or pred.shape[4] % 16:
+            raise ValueError(f"H and W must be multiples of 16 (the stack halves them four times), got H={pred.shape[3]}, "
+                             f"W={pred.shape[4]}")
+        if not pred.is_cuda or not target.is_cuda:
+            raise CtsiError("VGGPerceptualLoss runs on the HIP engine: pass ROCm tensors (there is no CPU path in the product; "
+                            "tests/vgg_restatement.py is test infrastructure)")
+        p = pred.to(torch.float32).contiguous()             # outside the Function: autograd carries dtype and layout
+        t = target.detach().to(torch.float32).contiguous()
+        return _VGGLossFn.apply(p, t, self, torch.is_grad_enabled() and p.requires_grad)
 
 
 class MS_SSIM_Loss(nn.Module):
@@ -154,8 +327,10 @@ class MS_SSIM_Loss(nn.Module):
 
 class CombinedLoss(nn.Module):
     """diffusion loss + lambda_perceptual * VGG perceptual + lambda_ssim * MS-SSIM, the auxiliary terms every N steps
-    (reference losses.py:279-361).  The SSIM term is the device loss above.  The perceptual term is built when it is first
-    due and raises `NotImplementedError` then: `lambda_perceptual=0` is the usable setting on this engine."""
+    (reference losses.py:279-361).  Both auxiliary terms are the device losses above.  The perceptual term needs VGG-19
+    weights the constructor has no argument for (its signature is the reference's): assign
+    `c.perceptual_loss = VGGPerceptualLoss(weights=...)` before the term is first due.  Otherwise it is built when first due
+    and raises `NotImplementedError` then, which leaves `lambda_perceptual=0` as the setting that needs no weights."""
 
     def __init__(self, lambda_perceptual: float = 0.1, lambda_ssim: float = 0.1, perceptual_every_n_steps: int = 10,
                  ssim_every_n_steps: int = 10):

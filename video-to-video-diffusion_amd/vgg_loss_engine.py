@@ -1,0 +1,228 @@
+"""The VGG-19 perceptual loss on the HIP engine: forward and backward of `losses.VGGPerceptualLoss` (reference
+models/losses.py:22-146).
+
+One `VGGLossProgram` serves one (N images, H, W) key of one loss module.  The N sampled slices of `pred` and the N of `target`
+go through the VGG-19 `features` stack as ONE batch of 2 N images (half the launches, the weights read once): the images are
+the depth axis of a bf16 channels-last tensor and every 3 x 3 convolution is a (1, 3, 3) / pad (0, 1, 1) conv plan, so packed
+weight images go through the engine's content-addressed cache like every other layer's.
+
+  forward   ctsi_vgg_prep (twice: pred, target) | per conv: ctsi_conv_fwd with the ReLU epilogue on the planar halo-tile form
+            (conv3_planar_k32_kernel), ctsi_conv_fwd + ctsi_relu_bf16 in place where the plan keeps the gather kernel (the
+            3 -> 64 stem, planes too small for a tile, deep-K layers on small grids) | ctsi_maxpool2_fwd |
+            per compared feature ctsi_feat_loss_fwd (fixed-order partial sums) | ONE ctsi_feat_loss_finalize -> device scalar
+  backward  over the pred half only, deepest layer first: ctsi_feat_grad_relu_bwd (loss term + ReLU mask from the stored
+            post-ReLU activation, one pass per layer boundary) | the conv's data gradient = the same (1, 3, 3) plan on flipped,
+            transposed weights (ctsi_weight_dgrad_layout, as train_engine._conv_bwd does for stride-1 convs) |
+            ctsi_maxpool2_bwd | ctsi_vgg_prep_bwd -> fp32 NCDHW grad_pred, zero on unsampled slices
+
+No weight gradient exists: the VGG weights are frozen.  Every reduction has a fixed order and nothing uses float atomics, so loss
+and gradient are bit-identical run to run.
+
+In-place ReLU (torchvision's): a feature taken at a conv that another block follows is overwritten by that block's leading
+ReLU before the loss reads it, so it is compared POST-ReLU; only a conv that ends the stack is compared pre-ReLU.  Here the
+ReLU pass runs right behind every conv but the stack's last module, which gives exactly that.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional, Sequence
+
+import torch
+
+from .engine import Act, Ctx, Program, _ptr
+from .lib import ConvDesc, CtsiError
+
+# torchvision's vgg19().features: module index -> ("conv", cin, cout) | ("relu",) | ("pool",); 37 modules, 16 convs
+VGG19_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512, 512, 512, 512, "M"]
+
+
+def vgg19_feature_modules() -> List[tuple]:
+    mods, cin = [], 3
+    for v in VGG19_CFG:
+        if v == "M":
+            mods.append(("pool",))
+        else:
+            mods.extend([("conv", cin, v), ("relu",)])
+            cin = v
+    return mods
+
+
+VGG19_MODULES = vgg19_feature_modules()
+K, P = (1, 3, 3), (0, 1, 1)
+
+
+class VGGLossProgram(Program):
+    """convs: {module index: nn.Conv2d} up to max(feature_layers); n_img: sampled slices per call (B * num)."""
+
+    def __init__(self, ctx: Ctx, convs, feature_layers: Sequence[int], use_l1: bool, n_img: int, h: int, w: int):
+        super().__init__(ctx)
+        lib, sptr, prog = self.lib, ctx.sptr, self
+        self.n_img, self.h, self.w = n_img, h, w
+        self.layers = list(feature_layers)
+        last = self.layers[-1]
+        nl = len(self.layers)
+        n2 = 2 * n_img
+        self.blocks = lib.feat_loss_blocks()
+        self.partials = self.persistent((nl * self.blocks,), torch.float64)
+        self.out = self.persistent((1 + nl,), torch.float32)
+        self.gl = self.persistent((1,), torch.float32)
+        self.xin = Act(self.persistent((n2 * h * w * 8,), torch.bfloat16), 1, 8, n2, h, w)
+        self.generation = 0
+
+        # ---- forward --------------------------------------------------------------------------------------------------------
+        nodes, x = [], self.xin
+        for i, m in enumerate(VGG19_MODULES[:last + 1]):
+            if m[0] == "conv":
+                conv = convs[i]
+                self.track(conv.weight, conv.bias)
+                relu = i < last
+                fused = relu and self._planar(x, m[2])      # the planar halo-tile form applies ReLU in its epilogue
+                out, _ = self.conv(f"vgg.{i}", (lambda c=conv: c.weight.unsqueeze(2)), (lambda c=conv: c.bias), x, None, k=K,
+                                   p=P, cout=m[2], cin_w=3 if i == 0 else None, act=2 if fused else 0)
+                if relu and not fused:
+                    self._emit_relu(f"vgg.{i + 1}.relu", out)
+                nodes.append(dict(kind="conv", i=i, x=x, out=out, relu=relu, conv=conv, feats=[]))
+                x = out
+            elif m[0] == "pool":
+                out = self.act(1, x.c, x.d, x.h // 2, x.w // 2)
+                xp, op, xd, xh, xw, xc = x.ip, out.ip, x.d, x.h, x.w, x.c
+                nbytes = 2.0 * x.d * x.h * x.w * x.c * 1.25
+
+                def run_pool(xp=xp, op=op, xd=xd, xh=xh, xw=xw, xc=xc):
+                    lib.maxpool2_fwd(xp, op, xd, xh, xw, xc, sptr)
+
+                self._emit(run_pool, f"vgg.{i}.pool", 0.0, "maxpool2_fwd", nbytes=nbytes)
+                nodes.append(dict(kind="pool", i=i, x=x, out=out, relu=False, feats=[]))
+                x = out
+            if i in self.layers:       # (a ReLU index lands on its conv's node: the same post-ReLU tensor)
+                nodes[-1]["feats"].append(self.layers.index(i))
+        counts = [0] * nl
+        sq = 0 if use_l1 else 1
+        for node in nodes:
+            a = node["out"]
+            half = n_img * a.h * a.w * a.c
+            for l in node["feats"]:
+                counts[l] = half
+                pp, tp, dst = a.ip, C.c_void_p(a.ip.value + 2 * half), C.c_void_p(self.partials.data_ptr() + 8 * l * self.blocks)
+
+                def run_loss(pp=pp, tp=tp, dst=dst, half=half):
+                    lib.feat_loss_fwd(pp, tp, half, sq, dst, sptr)
+
+                self._emit(run_loss, f"vgg.{node['i']}.loss", 0.0, "feat_loss", nbytes=4.0 * half)
+        self.counts = self.persistent((nl,), torch.int64)
+        self.counts.copy_(torch.tensor(counts, dtype=torch.int64))
+        pa, cn, ob = _ptr(self.partials), _ptr(self.counts), _ptr(self.out)
+
+        def run_fin():
+            lib.feat_loss_finalize(pa, cn, nl, ob, sptr)
+
+        self._emit(run_fin, "vgg.loss.finalize", 0.0, "feat_loss_finalize")
+        self.n_fwd = len(self.ops)
+
+        # ---- backward (pred half) ------------------------------------------------------------------------------------------
+        glp = _ptr(self.gl)
+        kind_loss = 1 if use_l1 else 2
+        g: Optional[Act] = None
+        for node in reversed(nodes):
+            a = node["out"]
+            half = n_img * a.h * a.w * a.c
+            if node["feats"] or node["relu"]:
+                if g is None and not node["feats"]:
+                    raise CtsiError("internal: no gradient reaches the deepest VGG layer")
+                kind = kind_loss if node["feats"] else 0
+                coef = len(node["feats"]) / (nl * float(half))
+                gout = g if g is not None else self.act(1, a.c, n_img, a.h, a.w)
+                gi, yp, tp, go = (g.ip if g is not None else C.c_void_p(0)), a.ip, C.c_void_p(a.ip.value + 2 * half), gout.ip
+                relu = int(node["relu"])
+
+                def run_grad(gi=gi, yp=yp, tp=tp, go=go, half=half, coef=coef, kind=kind, relu=relu):
+                    lib.feat_grad_relu_bwd(gi, yp, tp, go, half, coef, kind, relu, glp, sptr)
+
+                self._emit(run_grad, f"vgg.{node['i']}.grad", 0.0, "feat_grad_relu_bwd", nbytes=(8.0 if kind else 6.0) * half)
+                g = gout
+            xa = node["x"]
+            if node["kind"] == "pool":
+                gx = self.act(1, xa.c, n_img, xa.h, xa.w)
+                xp, gp, gxp, xh, xw, xc = xa.ip, g.ip, gx.ip, xa.h, xa.w, xa.c
+
+                def run_pool_bwd(xp=xp, gp=gp, gxp=gxp, xh=xh, xw=xw, xc=xc):
+                    lib.maxpool2_bwd(xp, gp, gxp, n_img, xh, xw, xc, sptr)
+
+                self._emit(run_pool_bwd, f"vgg.{node['i']}.pool.bwd", 0.0, "maxpool2_bwd",
+                           nbytes=2.0 * n_img * xa.h * xa.w * xa.c * 2.25)
+            else:
+                conv = node["conv"]
+                cout, cin = conv.weight.shape[0], conv.weight.shape[1]
+                gx = self.act(1, xa.c, n_img, xa.h, xa.w)
+
+                def wfn(conv=conv, cout=cout, cin=cin, rows=xa.c):
+                    # (rows, cout, 1, 3, 3): the layer's weights flipped and transposed; rows past cin (the 8-channel input
+                    # image of the 3-channel stem) are zero
+                    src = conv.weight.detach().to(device=ctx.device, dtype=torch.float32).contiguous()
+                    outw = torch.zeros((rows, cout, 1, 3, 3), dtype=torch.float32, device=ctx.device)
+                    lib.weight_dgrad_layout(_ptr(src), _ptr(outw), cout, cin, 9, 0, cin, sptr)
+                    src.record_stream(ctx.stream)
+                    return outw
+
+                self.conv(f"vgg.{node['i']}.dgrad", wfn, None, g, None, k=K, p=P, cout=xa.c, out=gx,
+                          audit=dict(kind="dgrad", op="convT", g=g, weight=lambda c=conv: c.weight.unsqueeze(2), w_ci=None, k=K,
+                                     s=(1, 1), p=P))
+            self.release(g)
+            g = gx
+        self.g_in = g
+        self.finalize_layout()
+
+    def _planar(self, x: Act, cout: int) -> bool:
+        """Whether the (1, 3, 3) conv of `x` to `cout` channels is planned onto the planar halo-tile form (ctsi_conv_plan_form,
+        bit 16; CTSI_CONV_PLANAR=0 keeps every layer on the gather kernel) -- the only form with a ReLU epilogue."""
+        plan, form = C.c_void_p(), (C.c_int * 8)()
+        self.lib.conv_plan_create(C.byref(plan), C.byref(ConvDesc(0, 1, 3, 3, 1, 1, 0, 1, 1, x.n, x.c, 0, cout, x.d, x.h, x.w, 0)))
+        try:
+            self.lib.conv_plan_form(plan, form)
+        finally:
+            self.lib.conv_plan_destroy(plan)
+        return bool(form[4] & 16)
+
+    def _emit_relu(self, name: str, a: Act):
+        lib, sptr = self.lib, self.ctx.sptr
+        ap, cnt = a.ip, a.d * a.h * a.w * a.c
+
+        def run():
+            lib.relu_bf16(ap, cnt, sptr)
+
+        self._emit(run, name, 0.0, "relu_bf16", nbytes=4.0 * cnt)
+
+    # ---- execution -----------------------------------------------------------------------------------------------------------
+    def run_forward(self, pred: torch.Tensor, target: torch.Tensor, slices: torch.Tensor, norm: torch.Tensor, b: int, d: int,
+                    num: int) -> torch.Tensor:
+        """pred, target: fp32 contiguous (B, 1, D, H, W) device tensors; returns the fp32 device tensor [loss, layer means]."""
+        if b * num != self.n_img:
+            raise CtsiError("internal: the VGG loss program was built for another number of images")
+        self.ensure_fresh()
+        self.generation += 1
+        lib, sptr = self.lib, self.ctx.sptr
+        half_bytes = self.n_img * self.h * self.w * 8 * 2
+        lib.vgg_prep(_ptr(pred), _ptr(slices), _ptr(norm), self.xin.ip, b, d, num, self.h, self.w, sptr)
+        lib.vgg_prep(_ptr(target), _ptr(slices), _ptr(norm), C.c_void_p(self.xin.ip.value + half_bytes), b, d, num, self.h,
+                     self.w, sptr)
+        pred.record_stream(self.ctx.stream)
+        target.record_stream(self.ctx.stream)
+        for op in self.ops[:self.n_fwd]:
+            op()
+        out = self.out.clone()
+        self.check_errors()
+        return out
+
+    def run_backward(self, grad_loss: torch.Tensor, slices: torch.Tensor, norm: torch.Tensor, b: int, d: int, num: int,
+                     generation: int) -> torch.Tensor:
+        if generation != self.generation:
+            raise CtsiError("backward of a VGG loss forward whose saved activations were overwritten (internal: a program was "
+                            "handed out twice)")
+        lib, sptr = self.lib, self.ctx.sptr
+        self.gl.copy_(grad_loss.reshape(1))
+        for op in self.ops[self.n_fwd:]:
+            op()
+        grad_pred = torch.empty((b, 1, d, self.h, self.w), dtype=torch.float32, device=self.ctx.device)
+        lib.vgg_prep_bwd(self.g_in.ip, _ptr(slices), _ptr(norm), _ptr(grad_pred), b, d, num, self.h, self.w, sptr)
+        self.check_errors()
+        return grad_pred
