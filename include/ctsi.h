@@ -507,6 +507,25 @@ int ctsi_conv_f32_geometry(const ctsi_conv_desc* desc, int* d_out, int* h_out, i
 int ctsi_conv_f32_pack_weights(const ctsi_conv_desc* desc, const float* w_f32, void* packed, void* stream);
 int ctsi_conv_f32_fwd(const ctsi_conv_desc* desc, const float* x1, const float* x2, const void* packed_w, const float* bias,
                       const float* residual, const ctsi_conv_out* out, void* stream);
+/* bf16x3 inference mode (csrc/conv_bf16x3.hip) ----------------------------------------------------------------------------- *
+ * The convolution of the fp32 mode on the bf16 MFMA (v_mfma_f32_32x32x16_bf16): tensors stay fp32, and inside the kernel each
+ * fp32 operand v is split as hi = bf16(v) (round to nearest even), lo = bf16(v - float(hi)); the kernel sums
+ * xh wh + xh wl + xl wh in fp32 (each product exact).  Everything else of the fp32 mode (GroupNorm, attention, sampler
+ * updates, layout converters) is reused unchanged.  Same descriptor, same output struct, same geometries, same rejections,
+ * same colsum slab layout and same epilogue as ctsi_conv_f32_*; differences:
+ *   _weight_bytes  bytes of the packed image: a hi and a lo bf16 image [class][tap * cpad / 32 + ci / 32][cout_pad][32], cpad =
+ *                c1 + c2 rounded up to 32 (zero rows / columns cover the padding)
+ *   _flops       the useful 2 M N K, not the three products
+ *   _fwd         `packed_w` must be 16-byte aligned.  Fixed summation order, no atomics: a relaunch is bit-identical and a
+ *                sample's result does not depend on the batch around it.                                                    */
+int ctsi_conv_bf16x3_supported(const ctsi_conv_desc* desc);
+size_t ctsi_conv_bf16x3_weight_bytes(const ctsi_conv_desc* desc);
+double ctsi_conv_bf16x3_flops(const ctsi_conv_desc* desc);
+int ctsi_conv_bf16x3_geometry(const ctsi_conv_desc* desc, int* d_out, int* h_out, int* w_out, int* tiles_per_sample,
+                              int* nclass, int* cout_pad);
+int ctsi_conv_bf16x3_pack_weights(const ctsi_conv_desc* desc, const float* w_f32, void* packed, void* stream);
+int ctsi_conv_bf16x3_fwd(const ctsi_conv_desc* desc, const float* x1, const float* x2, const void* packed_w, const float* bias,
+                         const float* residual, const ctsi_conv_out* out, void* stream);
 /* GroupNorm on fp32 NDHWC: column sums in 512-voxel tiles (ctsi_gn_colsum_f32_tiles per sample) and the apply pass with every
  * option of ctsi_gn_apply (SiLU before, time bias row (step_ptr ? *step_ptr : 0) * n + i, fp32 residual, SiLU after). */
 int ctsi_gn_colsum_f32_tiles(int d, int h, int w);

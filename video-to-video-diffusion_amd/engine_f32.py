@@ -27,7 +27,7 @@ import torch.nn as nn
 from .engine import Act, Ctx, UNetProgram, VAEDecodeProgram, VAEEncodeProgram, _ptr, check_attention_mode
 from .lib import ConvDesc, ConvOut, CtsiError
 
-PRECISIONS = ("bf16", "fp32")
+PRECISIONS = ("bf16", "fp32", "bf16x3")       # "bf16x3": engine_x3.py
 
 
 def _f32_pack_sig(desc: ConvDesc, cout_pad: int, wbytes: int) -> tuple:
@@ -39,7 +39,7 @@ def _f32_pack_sig(desc: ConvDesc, cout_pad: int, wbytes: int) -> tuple:
 
 
 def check_precision(p) -> str:
-    """Validate an inference precision value ('bf16' | 'fp32'); raises ValueError otherwise."""
+    """Validate an inference precision value ('bf16' | 'fp32' | 'bf16x3'); raises ValueError otherwise."""
     if not isinstance(p, str) or p not in PRECISIONS:
         raise ValueError(f"unknown inference precision {p!r}: expected one of {PRECISIONS}")
     return p

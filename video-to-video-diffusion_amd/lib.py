@@ -180,6 +180,12 @@ SIGNATURES = {
     "ctsi_conv_f32_geometry": (_i, [C.POINTER(ConvDesc), _ip, _ip, _ip, _ip, _ip, _ip], True),
     "ctsi_conv_f32_pack_weights": (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp], True),
     "ctsi_conv_f32_fwd": (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvOut), _vp], True),
+    "ctsi_conv_bf16x3_supported": (_i, [C.POINTER(ConvDesc)], False),
+    "ctsi_conv_bf16x3_weight_bytes": (_sz, [C.POINTER(ConvDesc)], False),
+    "ctsi_conv_bf16x3_flops": (C.c_double, [C.POINTER(ConvDesc)], False),
+    "ctsi_conv_bf16x3_geometry": (_i, [C.POINTER(ConvDesc), _ip, _ip, _ip, _ip, _ip, _ip], True),
+    "ctsi_conv_bf16x3_pack_weights": (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp], True),
+    "ctsi_conv_bf16x3_fwd": (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvOut), _vp], True),
     "ctsi_gn_colsum_f32_tiles": (_i, [_i, _i, _i], False),
     "ctsi_gn_colsum_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ip, _vp], True),
     "ctsi_gn_apply_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp, _vp,

@@ -94,11 +94,11 @@ class VideoToVideoDiffusion(nn.Module):
         self.cond_drop_prob = float(config.get('cond_drop_prob', 0.0))
         if not 0.0 <= self.cond_drop_prob <= 1.0:
             raise ValueError(f"cond_drop_prob must lie in [0, 1], got {config.get('cond_drop_prob')!r}")
-        # additive key: the arithmetic of generate() / the samplers / encode / decode ('bf16' default, or 'fp32')
+        # additive key: the arithmetic of generate() / the samplers / encode / decode ('bf16' default, 'fp32' or 'bf16x3')
         self.set_inference_precision(config.get('hardware', {}).get('inference_precision', 'bf16'))
 
     def set_inference_precision(self, precision):
-        """'bf16' (default) or 'fp32': sets `unet.inference_precision` and `vae.inference_precision`, i.e. the arithmetic
+        """'bf16' (default), 'fp32' or 'bf16x3' (fp32 tensors, split-bf16 MFMA convolutions: engine_x3.py): sets `unet.inference_precision` and `vae.inference_precision`, i.e. the arithmetic
         of generate(), the samplers and VAE encode / decode (engine_f32.py: fp32 activations, fp32 MFMA operands, the
         reference's fp32 inference of models/model.py:254-259).  Training (`forward`) keeps its bf16 programs."""
         check_precision(precision)
@@ -165,7 +165,7 @@ class VideoToVideoDiffusion(nn.Module):
         `sampler` also accepts 'dpmpp_2m' (additive): DPM-Solver++(2M) with `num_inference_steps` steps
         (sampler.DPMSolverSampler), e.g. 20 steps in place of DDIM-50, and 'heun' (additive): EDM Heun with
         `num_inference_steps` steps on Karras sigmas, 2 N - 1 U-Net evaluations (sampler.HeunSampler).
-        `precision` (additive, default None = the models' `inference_precision` attributes): 'bf16' or 'fp32' for this
+        `precision` (additive, default None = the models' `inference_precision` attributes): 'bf16', 'fp32' or 'bf16x3' for this
         call only; the attributes are restored afterwards."""
         check_guidance(guidance_scale, guidance_rescale)
         if precision is not None:

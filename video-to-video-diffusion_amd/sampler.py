@@ -24,7 +24,8 @@ import torch
 
 from .engine import (SAMPLER_STEPS, Ctx, UNetProgram, _ptr, check_attention_mode, check_device_errors,
                      check_resblock_options_unsharded, nan_to_num_, sampler_step_launcher, trilinear_depth)
-from .engine_f32 import UNetProgramF32, check_precision
+from .engine_f32 import check_precision
+from .engine_x3 import ACT_BYTES, unet_program
 from .lib import CtsiError
 from .x0_form import check_eps_form_timesteps, check_update_form, x0_coef_rows, x0_step_launcher
 
@@ -595,7 +596,7 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
     if comm is not None and comm.world > 1:
         check_resblock_options_unsharded(unet, True)
         if precision != "bf16":
-            raise CtsiError("the fp32 inference mode does not support depth sharding (unet.depth_shard_comm); "
+            raise CtsiError(f"the {precision} inference mode does not support depth sharding (unet.depth_shard_comm); "
                             "set inference_precision='bf16' or drop the communicator")
         if eps_trajectory is not None:
             raise CtsiError("eps_trajectory is not recorded by the depth-sharded sampler")
@@ -609,7 +610,7 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
         from .engine import cached_program
 
         def build():
-            cls = UNetProgramF32 if precision == "fp32" else UNetProgram
+            cls = unet_program(precision)
             kw = dict(guided=True, rescale=phi_cfg > 0.0) if guided else {}
             if plan.pred is not None or plan.x0:
                 kw["prediction"] = "v_prediction"
@@ -928,8 +929,8 @@ def _stitched(sampler, v_thick_full, vae, patch_size, target_patch_size, stride,
             except Exception:
                 total = 64 << 30
             per_window = 2500.0 * b * td * th * tw
-            if getattr(vae, "inference_precision", "bf16") == "fp32":
-                per_window *= 2.0         # fp32 activations: twice the bytes per voxel
+            # fp32 activations (the fp32 and bf16x3 modes): twice the bytes per voxel
+            per_window *= ACT_BYTES.get(getattr(vae, "inference_precision", "bf16"), 2) / 2.0
             if guided:
                 per_window *= 2.0         # a guided window is two rows of the U-Net's batch
             group = max(1, min(len(mine), int(0.2 * total / per_window)))

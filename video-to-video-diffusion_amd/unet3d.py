@@ -12,7 +12,8 @@ import torch
 import torch.nn as nn
 
 from .engine import Ctx, UNetProgram, cached_program, check_attention_mode
-from .engine_f32 import UNetProgramF32, check_precision
+from .engine_f32 import check_precision
+from .engine_x3 import unet_program
 from .lib import CtsiError
 from .norm_mod import check_dropout, dropout_threshold  # noqa: F401  (re-exported)
 
@@ -119,7 +120,8 @@ class UNet3D(nn.Module):
     forward, every sampler, guidance, v-prediction, stitching and training honour it.  It needs the whole
     depth on one device (CtsiError with depth sharding) and the bf16 engine (CtsiError with inference_precision='fp32').
 
-    Extra attribute `inference_precision` ('bf16' | 'fp32', default 'bf16') selects the arithmetic of `forward` (under
+    Extra attribute `inference_precision` ('bf16' | 'fp32' | 'bf16x3', default 'bf16'; 'bf16x3' = the fp32 mode with split-bf16
+    MFMA convolutions, engine_x3.py, same restrictions as 'fp32') selects the arithmetic of `forward` (under
     no_grad) and of the samplers: bf16 activations and bf16 MFMA operands, or fp32 activations and fp32 MFMA operands
     (engine_f32.py: the reference's fp32 inference, models/model.py:254-259).  'fp32' supports attention_mode='fast' and
     one device only (CtsiError with 'exact' / 'softmax' or with depth sharding).  Training (`diffusion.training_loss`) always runs
@@ -211,11 +213,8 @@ class UNet3D(nn.Module):
         precision = check_precision(self.inference_precision)
         check_attention_mode(self.attention_mode)
         key = ("unet", ctx.device.index, n, d, h, w, max_rows, self.attention_mode, precision)
-        if precision == "fp32":
-            return cached_program(self, key, lambda: UNetProgramF32(ctx, self, n, d, h, w, max_rows,
-                                                                    self.attention_mode))
-        return cached_program(self, key, lambda: UNetProgram(ctx, self, n, d, h, w, max_rows,
-                                                             self.attention_mode))
+        cls = unet_program(precision)
+        return cached_program(self, key, lambda: cls(ctx, self, n, d, h, w, max_rows, self.attention_mode))
 
     @torch.no_grad()
     def forward(self, x, t, c):

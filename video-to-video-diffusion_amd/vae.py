@@ -10,7 +10,8 @@ import torch
 import torch.nn as nn
 
 from .engine import Ctx, VAEDecodeProgram, VAEEncodeProgram, cached_program
-from .engine_f32 import VAEDecodeProgramF32, VAEEncodeProgramF32, check_precision
+from .engine_f32 import check_precision
+from .engine_x3 import vae_decode_program, vae_encode_program
 from .lib import CtsiError
 from .unet3d import _EngineOnly
 
@@ -87,7 +88,8 @@ class VideoDecoder(_EngineOnly):
 class SliceInterpolationVAE(nn.Module):
     """encode(x) = encoder(x) * scaling_factor; decode(z) = decoder(z / scaling_factor).
 
-    Extra attribute `inference_precision` ('bf16' | 'fp32', default 'bf16') selects the arithmetic of `encode` / `decode`:
+    Extra attribute `inference_precision` ('bf16' | 'fp32' | 'bf16x3', default 'bf16'; 'bf16x3' = the fp32 mode with split-bf16
+    MFMA convolutions, engine_x3.py, same restrictions as 'fp32') selects the arithmetic of `encode` / `decode`:
     bf16 activations and MFMA operands, or fp32 ones (engine_f32.py).  'fp32' runs on one device (CtsiError with depth
     sharding).  The grad-mode `forward` (training) always runs the bf16 programs, whatever this attribute says."""
 
@@ -134,7 +136,7 @@ class SliceInterpolationVAE(nn.Module):
         ctx = Ctx.get(x.device)
         with ctx.scope():
             key = ("enc", ctx.device.index, n, d, h, w, float(self.scaling_factor), precision)
-            cls = VAEEncodeProgramF32 if precision == "fp32" else VAEEncodeProgram
+            cls = vae_encode_program(precision)
             prog = cached_program(self, key, lambda: cls(ctx, self, n, d, h, w))
             return prog(x)
 
@@ -149,7 +151,7 @@ class SliceInterpolationVAE(nn.Module):
         with ctx.scope():
             if comm is not None and comm.world > 1:
                 if precision != "bf16":
-                    raise CtsiError("the fp32 inference mode does not support depth sharding (vae.depth_shard_comm)")
+                    raise CtsiError(f"the {precision} inference mode does not support depth sharding (vae.depth_shard_comm)")
                 from .parallel import ShardSpec
                 spec = ShardSpec(comm.rank, comm.world, comm, d)
                 key = ("dec-shard", ctx.device.index, 1, d, h, w, comm.rank, comm.world, float(self.scaling_factor))
@@ -159,7 +161,7 @@ class SliceInterpolationVAE(nn.Module):
                 return torch.cat([prog(z[i:i + 1]) for i in range(n)], dim=0)
             else:
                 key = ("dec", ctx.device.index, n, d, h, w, float(self.scaling_factor), precision)
-                cls = VAEDecodeProgramF32 if precision == "fp32" else VAEDecodeProgram
+                cls = vae_decode_program(precision)
                 prog = cached_program(self, key, lambda: cls(ctx, self, n, d, h, w))
             return prog(z)
 
