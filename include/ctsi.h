@@ -665,6 +665,61 @@ int ctsi_x0_step_f32(float* z, const float* v, float* hist, const float* noise_n
                      const float* coef, const int* step_ptr, int n, int c, int d, int h, int w, int* nonfinite,
                      void* stream);
 
+/* Learned reverse variance and the respaced ancestral step (csrc/learned_sigma.hip; Nichol & Dhariwal 2021).
+ * ctsi_sigma_split: out2 is the fp32 NDHWC output of a 2L-channel head, n rows.  One pass writes channels [0, L) of every row,
+ *   packed, into eps (fp32 NDHWC, L channels, n rows) and -- when vraw is not NULL -- channels [L, 2L) of rows [0, n_keep) into
+ *   vraw (fp32 NDHWC, L channels, n_keep rows; under guidance the conditional half).  n_keep in [1, n] with vraw, [0, n] without.
+ * ctsi_ddpm_lv_step / _f32: ctsi_ddpm_step / ctsi_ddpm_step_f32 with the reverse variance taken per element.  Row coef[*step_ptr]
+ *   (row 0 when step_ptr is NULL) = {sqrt(1 - abar), sqrt(abar), coef1', coef2', log beta', log beta~' (clipped), s, clip}
+ *   with s = [not the last step] exp(log beta~' / 2), the fixed-small noise scale (learned_sigma.respaced_ddpm_rows, float64
+ *   rounded once; on the full chain the fp32 values of ctsi_ddpm_step's rows):
+ *     z0   = clamp(nan_to_num((z - c0 nan_to_num(eps)) / c1), -clip, clip)      (clip = 0: no clamp)
+ *     mean = c2 z0 + c3 z
+ *     lv   = f c4 + (1 - f) c5,  f = (vraw + 1) / 2  (not clamped)               (vraw == NULL: lv = c5, the fixed-small variance)
+ *     z <- zin <- nan_to_num(mean + s exp((lv - c5) / 2) noise)                   (= [not last] exp(lv / 2) noise; evaluated as
+ *                                                                                  s exp(f (c4 - c5) / 2), s alone when vraw == NULL;
+ *                                                                                  noise == NULL: the mean)
+ *   z, eps, vraw fp32 NDHWC; noise fp32 NCDHW; zin as in ctsi_ddpm_step.  With vraw == NULL, clip = 1 and the rows of the
+ *   full-length chain the result has ctsi_ddpm_step's bits on every row: the scale is the same fp32 number and the mean is
+ *   written with the same roundings.
+ * ctsi_ddpm_posterior_lv: the same step on fp32 NCDHW tensors with one row per sample (coef[b * 8 ..]), as ctsi_ddpm_posterior:
+ *   out (may be NULL) <- the updated sample, logvar_out (may be NULL; needs vraw) <- lv per element.
+ * ctsi_hybrid_loss_fwd / _bwd: the training loss L_simple + lambda L_vb of a learn_sigma model.  pred2: fp32 NDHWC, 2L channels
+ *   ([0, L) the prediction p, [L, 2L) the variance channels v); z0, noise: fp32 NCDHW; t: n device ints in [0, timesteps); sched:
+ *   one row per timestep {sqrt(abar), sqrt(1 - abar), coef1, coef2, log beta, log beta~ (clipped), log beta - log beta~, 0}
+ *   (learned_sigma.loss_schedule_rows); v_pred: 0 = p is eps, 1 = p is v; mask: fp32 (n, L, d) or NULL; norm[b] / norm_vb[b]: the
+ *   per-sample factors of the two terms (batch, element count, loss weight; lambda / ln 2 for the bound), folded on the host.
+ *   Per element, with z_t = a z0 + s noise rebuilt in registers, z0_pred = (z_t - s p) / a  |  a z_t - s p (not clipped),
+ *   lv = f c4 + (1 - f) c5 = c5 + f c6, f = (v + 1) / 2 (c6 is the float64 difference rounded once: at large t the two logs agree to
+ *   a few 1e-3 and the bound's terms are of that order):
+ *     mse term = (p - target)^2,  target = noise | a noise - s z0
+ *     t > 0: vb term = 1/2 (-1 + lv - c5 + e^(c5 - lv) + (c1 (z0 - z0_pred))^2 e^-lv)     KL(q(z_{t-1} | z_t, z_0) || p_theta), nats
+ *     t = 0: vb term = 1/2 (ln 2 pi + lv + (z0 - c1 z0_pred - c2 z_t)^2 e^-lv)             continuous Gaussian NLL, nats
+ *   forward: loss_out = {total, mse, vb, S_0 .. S_{n-1}, V_0 .. V_{n-1}} with S_b / V_b the sample's masked sums of the two
+ *   terms, mse = sum_b norm[b] S_b, vb = sum_b norm_vb[b] V_b, total = mse + vb; fp64 partials (workspace:
+ *   ctsi_hybrid_loss_workspace_doubles(n) doubles) added in a fixed order.
+ *   backward: dpred (bf16 NDHWC, c_stride >= 2L channels per voxel, padding channels zeroed) <- gscale[0] (1 when NULL) times
+ *   2 norm[b] mask (p - target) in channels [0, L) and norm_vb[b] mask d(vb term)/dv in channels [L, 2L), d lv / dv = (c4 - c5) / 2;
+ *   the bound sends no gradient to p (the mean is detached, as in the paper).
+ * 16-byte accesses in the split and the steps when L (c) % 4 == 0 and the pointers allow, one element per thread otherwise.  Null
+ * pointers / non-positive sizes / a channel slice outside c_total / n_keep outside its range / c_stride < 2L return
+ * CTSI_ERR_INVALID before any launch.  No atomics: every result is bit-identical run to run.  Capture-safe: no allocation, no
+ * synchronisation. */
+int ctsi_sigma_split(const float* out2, float* eps, float* vraw, int n, int n_keep, int L, int d, int h, int w, void* stream);
+int ctsi_ddpm_lv_step(float* z, const float* eps, const float* vraw, const float* noise_ncdhw, void* zin_bf16, int c_total,
+                      int c_off, const float* coef, const int* step_ptr, int n, int c, int d, int h, int w, void* stream);
+int ctsi_ddpm_lv_step_f32(float* z, const float* eps, const float* vraw, const float* noise_ncdhw, float* zin, int c_total,
+                          int c_off, const float* coef, const int* step_ptr, int n, int c, int d, int h, int w, void* stream);
+int ctsi_ddpm_posterior_lv(const float* z, const float* eps, const float* vraw, const float* noise, float* out,
+                           float* logvar_out, const float* coef, int n, long long per_sample, void* stream);
+size_t ctsi_hybrid_loss_workspace_doubles(int n);
+int ctsi_hybrid_loss_fwd(const float* pred2, const float* z0, const float* noise, const int* t, const float* sched,
+                         int timesteps, int v_pred, const float* mask, const float* norm, const float* norm_vb, int n, int L,
+                         int d, int h, int w, double* workspace, float* loss_out, void* stream);
+int ctsi_hybrid_loss_bwd(const float* pred2, const float* z0, const float* noise, const int* t, const float* sched,
+                         int timesteps, int v_pred, const float* mask, const float* norm, const float* norm_vb,
+                         const float* gscale, int n, int L, int d, int h, int w, void* dpred_bf16, int c_stride, void* stream);
+
 /* VGG-19 perceptual loss (csrc/vgg_loss.hip): the passes around its planar (1,3,3) convolutions, which run
  * on conv plans.  Images are bf16 channels-last [image][h][w][c]; c and every `count` are multiples of 8 (16-byte accesses).
  * ctsi_vgg_prep: image i = b * num + s <- slice slices[s] of sample b of x (fp32 NCDHW, C = 1): channels 0-2 are

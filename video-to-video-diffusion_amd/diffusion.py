@@ -27,6 +27,11 @@ class GaussianDiffusion(nn.Module):
         super().__init__()
         from .prediction import check_prediction_type
         self.prediction_type = check_prediction_type(prediction_type)
+        # a plain attribute like update_form (the config key `var_type` sets it): 'fixed_small' (the reference:
+        # the reverse variance is the posterior beta~_t) or 'learned_range' (Nichol & Dhariwal 2021) -- the model, a
+        # UNet3D(learn_sigma=True), emits L more channels v, the reverse log-variance is f log beta_t + (1 - f) log beta~_t with
+        # f = (v + 1) / 2, and training_loss adds the variational-bound term that trains them.  Validated where it is read.
+        self.var_type = "fixed_small"
         # plain attributes like prediction_type (no parameter, no buffer): the form of the sampler updates
         # ('eps' | 'x0'), whether rescale_zero_terminal_snr() has rewritten the schedule, and the training loss weight
         # ('min_snr' | 'uniform')
@@ -225,10 +230,9 @@ class GaussianDiffusion(nn.Module):
         per-step noise tensors instead of torch.randn; `num_steps` truncates the loop to its first
         steps (both are test hooks; defaults reproduce the reference).  `guidance_scale` / `guidance_rescale`
         (additive): classifier-free guidance, see sampler.run_sampler."""
-        from .sampler import run_sampler  # local import: sampler imports this module
-        return run_sampler(self, model, shape, c, device, kind="ddpm",
-                           t_desc=list(reversed(range(self.timesteps)))[:num_steps], progress=progress,
-                           noise_fn=noise_fn, guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
+        from .sampler import DDPMSampler  # local import: sampler imports this module
+        return DDPMSampler(self, model).sample(shape, c, device, progress=progress, noise_fn=noise_fn, num_steps=num_steps,
+                                               guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
 
     # ---- single reverse steps with per-sample timesteps (diffusion.py:249-338) -------------------------------------
     def _posterior_rows(self, t):
@@ -261,6 +265,43 @@ class GaussianDiffusion(nn.Module):
                     tns.record_stream(ctx.stream)
         return z0, out
 
+    def _learned(self) -> bool:
+        from .learned_sigma import check_var_type
+        return check_var_type(self.var_type) == "learned_range"
+
+    def _split_output(self, out, z_t):
+        """(prediction, variance channels) of a learn_sigma model's 2L-channel output (views; CtsiError on another shape)."""
+        L = int(z_t.shape[1])
+        if not torch.is_tensor(out) or tuple(out.shape) != (z_t.shape[0], 2 * L) + tuple(z_t.shape[2:]):
+            raise CtsiError(f"var_type='learned_range' needs a model output of 2 x {L} channels (UNet3D(learn_sigma=True)), got "
+                            f"shape {tuple(getattr(out, 'shape', ()))}")
+        return out[:, :L], out[:, L:]
+
+    def _posterior_lv(self, z_t, t, eps, vraw, noise, clip, want_logvar):
+        """(sample or mean, log-variance per element) under 'learned_range': one ctsi_ddpm_posterior_lv launch, fp32 NCDHW, one
+        full-chain row per sample (learned_sigma.step_rows_per_sample)."""
+        from .engine import Ctx, _ptr
+        from .learned_sigma import step_rows_per_sample
+        if not (z_t.is_cuda and eps.is_cuda):
+            raise CtsiError("the reverse-process arithmetic runs on the HIP engine: move the tensors to a ROCm device "
+                            "(there is no CPU path)")
+        ctx = Ctx.get(z_t.device)
+        n = int(z_t.shape[0])
+        z = z_t.detach().to(torch.float32).contiguous()
+        e = eps.detach().to(torch.float32).contiguous()
+        vr = vraw.detach().to(torch.float32).contiguous()
+        nz = None if noise is None else noise.detach().to(device=ctx.device, dtype=torch.float32).contiguous()
+        coef = step_rows_per_sample(self, t, nz is not None, clip).to(ctx.device).contiguous()
+        out = torch.empty_like(z)
+        logvar = torch.empty_like(z) if want_logvar else None
+        with ctx.scope():
+            ctx.lib.ddpm_posterior_lv(_ptr(z), _ptr(e), _ptr(vr), _ptr(nz), _ptr(out), _ptr(logvar), _ptr(coef), n,
+                                      z.numel() // n, ctx.sptr)
+            for tns in (z, e, vr, nz, coef):
+                if tns is not None:
+                    tns.record_stream(ctx.stream)
+        return out, logvar
+
     @torch.no_grad()
     def _predict_z_0_from_noise(self, z_t, t, noise_pred):
         """z_0 = (z_t - sqrt(1 - abar_t) * noise_pred) / sqrt(abar_t), per-sample t (diffusion.py:249-268)."""
@@ -272,7 +313,17 @@ class GaussianDiffusion(nn.Module):
         `model(z, t, c) -> eps` callable on the ROCm device (the engine's UNet3D evaluates per-sample timesteps); the
         posterior mean is one ctsi_ddpm_posterior launch.  variance / log_variance are the (B,1,1,1,1) buffer gathers
         the reference returns.  Under 'v_prediction' the model returns v (model_output_to_eps converts it); under
-        update_form 'x0' the mean comes from the raw v without a division (_x0_posterior)."""
+        update_form 'x0' the mean comes from the raw v without a division (_x0_posterior).  Under var_type='learned_range'
+         the model returns 2L channels and variance / log_variance are per element, of z_t's shape: the
+        learned exp(lv) and lv = f log beta_t + (1 - f) log beta~_t."""
+        if self._learned():
+            if self._x0_form():
+                raise CtsiError("update_form='x0' does not support a learned reverse variance (var_type='learned_range')")
+            self._check_eps_form(t)
+            pred, vraw = self._split_output(model(z_t, t, c), z_t)
+            noise_pred = self.model_output_to_eps(z_t, t, pred.contiguous())
+            mean, log_variance = self._posterior_lv(z_t, t, noise_pred, vraw, None, clip_denoised, True)
+            return mean, torch.exp(log_variance), log_variance
         if self._x0_form():
             mean = self._x0_posterior(z_t, t, model(z_t, t, c), None, clip_denoised)
         else:
@@ -291,6 +342,15 @@ class GaussianDiffusion(nn.Module):
         the captured-graph path of the sampling loop (same arithmetic, ctsi_ddpm_step)."""
         from .sampler import _is_engine_unet, run_sampler
         tv = [int(v) for v in t.reshape(-1).tolist()]
+        if self._learned():
+            if self._x0_form():
+                raise CtsiError("update_form='x0' does not support a learned reverse variance (var_type='learned_range')")
+            self._check_eps_form(t)
+            pred, vraw = self._split_output(model(z_t, t, c), z_t)
+            if noise is None:
+                noise = torch.randn_like(z_t)
+            noise_pred = self.model_output_to_eps(z_t, t, pred.contiguous())
+            return self._posterior_lv(z_t, t, noise_pred, vraw, noise, clip_denoised, False)[0]
         if len(set(tv)) == 1 and clip_denoised and noise is None and _is_engine_unet(model):
             return run_sampler(self, model, tuple(z_t.shape), c, z_t.device, kind="ddpm", t_desc=[tv[0]],
                                progress=False, z_init=z_t)
@@ -355,6 +415,9 @@ class GaussianDiffusion(nn.Module):
         from .engine import Ctx, cached_program, check_attention_mode
         from .norm_mod import dropout_active
         mode = check_attention_mode(getattr(model, "attention_mode", "fast"))
+        from .learned_sigma import check_pairing, hybrid_norms
+        check_pairing(self, model)
+        learned = self._learned()
         drop_on = dropout_active(model)                     # (validates the plain attribute, read at every forward)
         drop_p = getattr(model, "dropout", 0.0)
         if not z_0.is_cuda:
@@ -384,18 +447,25 @@ class GaussianDiffusion(nn.Module):
             num_valid = m.reshape(B, -1).sum(dim=1) * (h * w)
             if bool((num_valid == num_valid[0]).all()):
                 norm = (snr_weight.mean() / num_valid.sum()).expand(B)
+                count_norm = (1.0 / num_valid.sum()).expand(B)
             else:
                 norm = torch.where(num_valid > 0, snr_weight / (num_valid.clamp(min=1) * B),
                                    torch.zeros_like(snr_weight))
+                count_norm = torch.where(num_valid > 0, 1.0 / (num_valid.clamp(min=1) * B), torch.zeros_like(snr_weight))
         else:
             m = None
             norm = snr_weight / float(B * L * d * h * w)
+            count_norm = torch.full_like(snr_weight, 1.0 / float(B * L * d * h * w))
+        # 'learned_range' (DESIGN section 24): L_simple keeps `norm`; the bound takes the same batch / element normalisation
+        # without the loss weight, times lambda / ln 2
+        norm_vb = hybrid_norms(torch.ones_like(snr_weight), count_norm, self.timesteps)[1] if learned else None
         ctx = Ctx.get(device)
         with ctx.scope():
             # the epsilon key is what it always was; a v program (q_sample_v, a target buffer) has its own
             film = bool(getattr(model, "use_scale_shift_norm", False))
             key = ("unet-train", ctx.device.index, B, d, h, w) + ((self.prediction_type,) if v_pred else ()) + (
-                () if mode == "fast" else ("attn-" + mode,)) + (((film, drop_on),) if (film or drop_on) else ())
+                () if mode == "fast" else ("attn-" + mode,)) + (((film, drop_on),) if (film or drop_on) else ()) + (
+                ("learn_sigma",) if learned else ())
             kw = dict(prediction=self.prediction_type) if v_pred else {}
             if drop_on:
                 kw["dropout"] = True
@@ -403,8 +473,13 @@ class GaussianDiffusion(nn.Module):
             prog.set_diffusion(self)
             if drop_on:
                 prog.set_dropout(drop_p, dropout_seed)
+            if learned:
+                prog.set_vb_norm(norm_vb)
         loss = train_step(prog, z_0.detach().float(), c.detach().float(), t, noise.float(), norm, m)
         loss_dict = {'mse': loss.item()}
+        if learned:       # the program's loss_out = {total, mse, vb, ...}: 'mse' keeps its meaning, 'vb' = lambda L_vb (bits)
+            parts = prog.loss_out[1:3].tolist()
+            loss_dict = {'mse': parts[0], 'vb': parts[1]}
         if keep is not None:
             loss_dict['cond_dropped'] = int((~keep).sum().item())
         prog.check_errors()     # (the stream is synchronised by the .item() above: a sticky split-K hand-off error of this forward,
@@ -421,7 +496,12 @@ class GaussianDiffusion(nn.Module):
                     z_t, _ = self.q_sample(z_0.detach().float(), t, noise.float())
                     eps = torch.empty((B, L, d, h, w), dtype=torch.float32, device=device)
                     with ctx.scope():
-                        ctx.lib.ndhwc_f32_to_ncdhw_f32(C.c_void_p(prog.eps.data_ptr()), C.c_void_p(eps.data_ptr()), B, L, d, h,
+                        pred_nd = prog.eps
+                        if learned:       # the prediction half of the 2L-channel head
+                            pred_nd = torch.empty((B, d, h, w, L), dtype=torch.float32, device=device)
+                            ctx.lib.sigma_split(C.c_void_p(prog.eps.data_ptr()), C.c_void_p(pred_nd.data_ptr()), None, B, 0, L,
+                                                d, h, w, ctx.sptr)
+                        ctx.lib.ndhwc_f32_to_ncdhw_f32(C.c_void_p(pred_nd.data_ptr()), C.c_void_p(eps.data_ptr()), B, L, d, h,
                                                        w, ctx.sptr)
                     z0_pred = (self._predict_z_0_from_v if v_pred else self._predict_z_0_from_noise)(z_t, t, eps)
                     # training keeps the bf16 programs whatever `vae.inference_precision` says
@@ -439,5 +519,5 @@ class GaussianDiffusion(nn.Module):
                 print("Warning: pytorch-msssim not installed. Falling back to MSE-only loss.")
             except Exception as e:
                 print(f"Warning: MS-SSIM calculation failed: {e}. Using MSE-only loss.")
-        loss_dict['total'] = loss_dict['mse']
+        loss_dict['total'] = loss.item() if learned else loss_dict['mse']
         return loss, loss_dict

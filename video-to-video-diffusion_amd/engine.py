@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from .attention import ATTENTION_MODES, check_attention_mode, emit_softmax_attention
+from .learned_sigma import add_sigma_split, check_learn_sigma_unsharded
 from .lib import ConvDesc, ConvOut, CtsiError, get_lib
 from .prediction import add_pred_to_eps, check_prediction_type
 from .x0_form import add_x0_step, check_update_form
@@ -1141,6 +1142,7 @@ class SamplerStep(NamedTuple):
     noise: bool         # takes the fp32 NCDHW noise (may still be NULL at run time)
     hist: bool          # takes a persistent fp32 NDHWC history buffer of z's shape
     nonfinite: bool     # takes the nonfinite table
+    vraw: bool = False  # takes the variance channels of a learn_sigma model (fp32 NDHWC of z's shape; NULL: fixed-small)
 
 
 # Every sampler update.  A new sampler adds one row here and one branch in sampler._step_plan.
@@ -1150,16 +1152,25 @@ SAMPLER_STEPS = {
     "dpmpp": SamplerStep("dpm_step", noise=False, hist=True, nonfinite=True),      # history: x0_{i-1}
     "heun": SamplerStep("heun_step", noise=True, hist=True, nonfinite=True),       # history: the predictor's D1
 }
+# Additive kinds (not in the reference's loops).  'ddpm_lv': the ancestral step on respaced rows, with the learned or the
+# fixed-small variance.
+EXTRA_SAMPLER_STEPS = {
+    "ddpm_lv": SamplerStep("ddpm_lv_step", noise=True, hist=False, nonfinite=False, vraw=True),
+}
+
+
+def sampler_step_row(kind: str) -> SamplerStep:
+    return SAMPLER_STEPS[kind] if kind in SAMPLER_STEPS else EXTRA_SAMPLER_STEPS[kind]
 
 
 def sampler_step_launcher(lib, kind: str, f32: bool) -> Callable:
     """The update of `kind` behind one argument list, (z, eps, hist, noise, zin, c_total, coef, step_ptr, n, L, d, h,
-    w, nonfinite, stream); operands the entry does not take are dropped.  `f32`: the entry that writes an fp32 zin."""
-    s = SAMPLER_STEPS[kind]
+    w, nonfinite, stream, vraw=None); operands the entry does not take are dropped.  `f32`: the entry that writes an fp32 zin."""
+    s = sampler_step_row(kind)
     fn = getattr(lib, s.entry + ("_f32" if f32 else ""))
 
-    def launch(z, eps, hist, noise, zin, c_total, coef, step_ptr, n, L, d, h, w, nonfinite, stream):
-        ops = [z, eps] + ([hist] if s.hist else []) + ([noise] if s.noise else [])
+    def launch(z, eps, hist, noise, zin, c_total, coef, step_ptr, n, L, d, h, w, nonfinite, stream, vraw=None):
+        ops = [z, eps] + ([vraw] if s.vraw else []) + ([hist] if s.hist else []) + ([noise] if s.noise else [])
         tail = [nonfinite] if s.nonfinite else []
         fn(*ops, zin, c_total, 0, coef, step_ptr, n, L, d, h, w, *tail, stream)
     return launch
@@ -1191,7 +1202,9 @@ class UNetProgram(Program):
             raise CtsiError("classifier-free guidance does not support depth sharding: the sharded program holds one "
                             "volume per rank and the rescale statistics would need a collective")
         check_resblock_options_unsharded(unet, shard is not None)
+        check_learn_sigma_unsharded(unet, shard is not None)
         self.unet = unet
+        self.learn_sigma = bool(getattr(unet, "learn_sigma", False))      # a 2L-channel head
         self.guided, self.rescale = bool(guided), bool(guided and rescale)
         self.prediction = check_prediction_type(prediction)
         self.n, self.d, self.h, self.w = n, d, h, w
@@ -1204,6 +1217,10 @@ class UNetProgram(Program):
         halo = 0 if shard is None else 1
         self.xin, self.xin2 = self._input_acts(n, d, h, w, halo)
         self.eps = self.persistent((n, d, h, w, L), torch.float32)
+        # learn_sigma: the head writes `out2`, ctsi_sigma_split packs its first half into `eps`; `vraw` (the variance channels
+        # of rows [0, self.n)) exists once a step that reads it is added
+        self.out2 = self.persistent((n, d, h, w, 2 * L), torch.float32) if self.learn_sigma else None
+        self.vraw = None
         self.z = self.persistent((self.n, d, h, w, L), torch.float32, zero=True)
         self.step_ptr = self.persistent((1,), torch.int32, zero=True)
         self.t_rows = self.persistent((max_rows,), torch.int32, zero=True)
@@ -1275,9 +1292,12 @@ class UNetProgram(Program):
         y = self.gn_apply(x, slot, gn, silu_pre=True)
         self.release(x)
         vox = d * h * w
-        self.conv("conv_out", lambda: conv.weight, lambda: conv.bias, y, None, cout=L, f32_out=self.eps,
-                  f32_strides=(vox * L, 1, h * w * L, w * L, L))
+        Lo = 2 * L if self.learn_sigma else L          # ONE head conv: the variance channels ride along
+        self.conv("conv_out", lambda: conv.weight, lambda: conv.bias, y, None, cout=Lo,
+                  f32_out=self.out2 if self.learn_sigma else self.eps, f32_strides=(vox * Lo, 1, h * w * Lo, w * Lo, Lo))
         self.release(y)
+        if self.learn_sigma:
+            add_sigma_split(self)
         self.unet_op_count = len(self.ops)
         self.finalize_layout()
 
@@ -1366,6 +1386,15 @@ class UNetProgram(Program):
                                         self.ctx.sptr)
         return out
 
+    def out_ncdhw(self) -> torch.Tensor:
+        """What UNet3D.forward returns, fp32 NCDHW: eps_ncdhw(), or all 2L channels of a learn_sigma model's head."""
+        if not self.learn_sigma:
+            return self.eps_ncdhw()
+        out = torch.empty((self.nb, 2 * self.L, self.d, self.h, self.w), dtype=torch.float32, device=self.ctx.device)
+        self.lib.ndhwc_f32_to_ncdhw_f32(_ptr(self.out2), _ptr(out), self.nb, 2 * self.L, self.d, self.h, self.w,
+                                        self.ctx.sptr)
+        return out
+
     def z_ncdhw(self) -> torch.Tensor:
         """The sampler state as fp32 NCDHW (the rank's slab only when depth-sharded; gather with
         shard.comm.gather_depth)."""
@@ -1419,18 +1448,26 @@ class UNetProgram(Program):
         self._emit(lambda: lib.cfg_mirror(src, dst, rows, L * nbytes, c_total * nbytes, sptr), "cfg.mirror",
                    nbytes=2.0 * rows * L * nbytes, audit=dict(kind="cfg_mirror", zin=self.xin, n=self.n, L=L))
 
-    def add_sampler_step(self, kind: str, with_noise: bool, update_form: str = "eps"):
+    def add_sampler_step(self, kind: str, with_noise: bool, update_form: str = "eps", learned_variance: bool = False):
         """Append the update of sampler `kind` (a SAMPLER_STEPS key) and the step-counter increment (done once, before
         capture).  'heun': one update per U-Net evaluation (predictor, corrector or final row); `with_noise` = churn on.
         A v-prediction program converts the network output first (prediction.add_pred_to_eps), ahead of the guidance.
         `update_form` 'x0' ('ddim', 'ddpm', 'dpmpp' of a v-prediction program): no conversion launch --
-        the guidance and ctsi_x0_step (x0_form.add_x0_step) read the raw v, and eps_ncdhw() returns it."""
+        the guidance and ctsi_x0_step (x0_form.add_x0_step) read the raw v, and eps_ncdhw() returns it.
+        `learned_variance` (kind 'ddpm_lv' of a learn_sigma program): the update reads `vraw`, which the
+        split launch then fills; otherwise the kind's variance operand is NULL (fixed-small)."""
         lib, sptr = self.lib, self.ctx.sptr
         n, L, d, h, w = self.n, self.L, self.d, self.h, self.w
-        entry = SAMPLER_STEPS[kind]
+        entry = sampler_step_row(kind)
         x0_form = check_update_form(update_form, self.prediction) == "x0"
         if x0_form and kind == "heun":
             raise CtsiError("internal: the EDM sampler has no x0-form update")
+        if x0_form and entry.vraw:
+            raise CtsiError("internal: the respaced / learned-variance ancestral step has no x0-form update")
+        if entry.vraw and learned_variance and not self.learn_sigma:
+            raise CtsiError("internal: a learned-variance step on a program without variance channels")
+        if entry.vraw and learned_variance:
+            self.vraw = self.persistent((n, d, h, w, L), torch.float32, zero=True)
         self.hist = None
         if self.prediction != "epsilon" and not x0_form:
             if entry.hist:      # (the conversion of a Heun corrector row reads the history)
@@ -1452,17 +1489,19 @@ class UNetProgram(Program):
         if self.hist is None and entry.hist:
             self.hist = self.persistent((n, d, h, w, L), torch.float32, zero=True)
         hp = _ptr(self.hist)
+        vp = _ptr(self.vraw)
         xin = self.xin
 
         def run_step():
-            step(zp, ep, hp, npz, xp, c_total, cp, sp, n, L, d, h, w, nfp, sptr)
+            step(zp, ep, hp, npz, xp, c_total, cp, sp, n, L, d, h, w, nfp, sptr, vp)
             if not f32:
                 xin.dirty = True
 
         def run_adv():
             lib.step_advance(sp, sptr)
 
-        step_bytes = (4 + 4 + 4 + zin_bytes + (4 if with_noise else 0) + (8 if entry.hist else 0)) * float(
+        step_bytes = (4 + 4 + 4 + zin_bytes + (4 if with_noise else 0) + (8 if entry.hist else 0)
+                      + (4 if self.vraw is not None else 0)) * float(
             n * L * d * h * w)
         if x0_form:
             add_x0_step(self, kind, with_noise)
@@ -1470,7 +1509,8 @@ class UNetProgram(Program):
             self._emit(run_step, "sampler.step", nbytes=step_bytes,
                        audit=dict(kind="sampler_step", sampler=kind, z=self.z, eps=self.eps, hist=self.hist,
                                   noise=self.noise if with_noise else None, zin=self.xin, coef=self.coef,
-                                  step_ptr=self.step_ptr, nonfinite=self.nonfinite if entry.nonfinite else None, n=n, L=L))
+                                  step_ptr=self.step_ptr, nonfinite=self.nonfinite if entry.nonfinite else None, n=n, L=L,
+                                  **(dict(vraw=self.vraw) if entry.vraw else {})))
         if self.guided:
             self._add_guidance_mirror()
         self._emit(run_adv, "sampler.advance", audit=dict(kind="sampler_advance", step_ptr=self.step_ptr))

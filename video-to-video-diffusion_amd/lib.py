@@ -219,6 +219,14 @@ SIGNATURES = {
     "ctsi_q_sample_v": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp], True),
     "ctsi_x0_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp], True),
     "ctsi_x0_step_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp], True),
+    "ctsi_sigma_split": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_ddpm_lv_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_ddpm_lv_step_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_ddpm_posterior_lv": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _vp], True),
+    "ctsi_hybrid_loss_workspace_doubles": (_sz, [_i], False),
+    "ctsi_hybrid_loss_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp], True),
+    "ctsi_hybrid_loss_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp],
+                             True),
     "ctsi_graph_begin_capture": (_i, [_vp], True),
     "ctsi_graph_end_capture": (_i, [_vp, C.POINTER(_vp)], True),
     "ctsi_graph_launch": (_i, [_vp, _vp], True),

@@ -71,7 +71,9 @@ class VideoToVideoDiffusion(nn.Module):
                            # ResBlocks' time conditioning (a real bool; anything else is a ValueError) and their
                            # training-time dropout probability in [0, 1) (validated by UNet3D)
                            use_scale_shift_norm=_config_bool(config, 'unet_use_scale_shift_norm', False),
-                           dropout=config.get('unet_dropout', 0.0))
+                           dropout=config.get('unet_dropout', 0.0),
+                           # additive key: a 2L-channel head whose second half is the learned variance
+                           learn_sigma=_config_bool(config, 'unet_learn_sigma', False))
         # additive key, top level like every U-Net key: how TemporalAttention is evaluated -- 'fast' (default) / 'exact': the
         # reference's einsum as written (a depth sum); 'softmax': true attention over depth (UNet3D's docstring)
         self.unet.attention_mode = check_attention_mode(config.get('unet_attention_mode', 'fast'))
@@ -81,6 +83,12 @@ class VideoToVideoDiffusion(nn.Module):
                                            beta_end=config.get('beta_end', 0.02),
                                            # additive key, top level like `noise_schedule`: 'epsilon' | 'v_prediction'
                                            prediction_type=config.get('prediction_type', 'epsilon'))
+        # additive key, top level: `var_type` 'fixed_small' | 'learned_range'; the latter needs
+        # `unet_learn_sigma: true` and the former forbids it (ValueError here, CtsiError at first use elsewhere)
+        from .learned_sigma import check_var_type, pairing_error
+        self.diffusion.var_type = check_var_type(config.get('var_type', 'fixed_small'))
+        if pairing_error(self.diffusion.var_type, self.unet.learn_sigma):
+            raise ValueError(pairing_error(self.diffusion.var_type, self.unet.learn_sigma))
         # additive keys, top level like `prediction_type`: `update_form` 'eps' | 'x0', `loss_weighting`
         # 'min_snr' | 'uniform', and `zero_terminal_snr: true`, which rescales the schedule (and sets update_form 'x0')
         from .x0_form import check_loss_weighting, check_update_form
@@ -162,7 +170,8 @@ class VideoToVideoDiffusion(nn.Module):
         unconditionally.  `guidance_rescale` phi in [0, 1] (additive, default 0) rescales eps to the conditional branch's
         per-sample standard deviation: eps <- phi eps std(eps_c) / std(eps) + (1 - phi) eps.  Encode, depth upsample and
         decode run once per volume.  Only a model trained with `cond_drop_prob` > 0 has seen the null conditioning.
-        `sampler` also accepts 'dpmpp_2m' (additive): DPM-Solver++(2M) with `num_inference_steps` steps
+        `sampler` also accepts 'ddpm_spaced' (additive): the ancestral sampler on `num_inference_steps` strided steps
+        (sampler.DDPMSampler.sample(num_inference_steps=); 'ddpm' keeps walking all of them and ignores the count), 'dpmpp_2m' (additive): DPM-Solver++(2M) with `num_inference_steps` steps
         (sampler.DPMSolverSampler), e.g. 20 steps in place of DDIM-50, and 'heun' (additive): EDM Heun with
         `num_inference_steps` steps on Karras sigmas, 2 N - 1 U-Net evaluations (sampler.HeunSampler).
         `precision` (additive, default None = the models' `inference_precision` attributes): 'bf16', 'fp32' or 'bf16x3' for this

@@ -22,10 +22,11 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .engine import (SAMPLER_STEPS, Ctx, UNetProgram, _ptr, check_attention_mode, check_device_errors,
-                     check_resblock_options_unsharded, nan_to_num_, sampler_step_launcher, trilinear_depth)
+from .engine import (Ctx, UNetProgram, _ptr, check_attention_mode, check_device_errors,
+                     check_resblock_options_unsharded, nan_to_num_, sampler_step_launcher, sampler_step_row, trilinear_depth)
 from .engine_f32 import check_precision
 from .engine_x3 import ACT_BYTES, unet_program
+from .learned_sigma import check_learn_sigma_unsharded, check_pairing, check_var_type, respaced_ddpm_rows
 from .lib import CtsiError
 from .x0_form import check_eps_form_timesteps, check_update_form, x0_coef_rows, x0_step_launcher
 
@@ -305,6 +306,18 @@ def heun_pred_rows(heun: HeunRows, dtype: torch.dtype = torch.float32) -> torch.
     return torch.from_numpy(rows).to(dtype)
 
 
+class LvRows(NamedTuple):
+    """What kind 'ddpm_lv' needs for one sampling run (sampler.lv_rows)."""
+    rows: torch.Tensor            # (N, 8) ctsi_ddpm_lv_step rows of the whole chain (learned_sigma.respaced_ddpm_rows)
+    chain: Tuple[int, ...]        # (N,) its descending timesteps
+    learned: bool                 # the step reads the model's variance channels (var_type 'learned_range')
+
+
+def lv_rows(diffusion, chain: Sequence[int], clip: bool = True) -> LvRows:
+    learned = check_var_type(getattr(diffusion, "var_type", "fixed_small")) == "learned_range"
+    return LvRows(respaced_ddpm_rows(diffusion, chain, clip), tuple(int(t) for t in chain), learned)
+
+
 class StepPlan(NamedTuple):
     """One sampling run as data, per U-Net evaluation e (E = len(t)).  run_sampler, run_sampler_sharded and the
     generic-callable loop read it and never test the sampler kind; only _step_plan builds one."""
@@ -322,6 +335,7 @@ class StepPlan(NamedTuple):
     init_noise: bool = False                       # eps_0 = noise_fn(0, shape) is drawn (step 0 churns)
     pred: Optional[torch.Tensor] = None            # (E, 4) ctsi_pred_to_eps rows under 'v_prediction'; None: the output is eps
     x0: bool = False                               # update_form 'x0': coef holds ctsi_x0_step rows, the update reads the raw v
+    learned: bool = False                          # the update reads the variance channels of a learn_sigma model (section 24)
 
     def initial_state(self, z0: torch.Tensor, noise_fn, shape, dev) -> torch.Tensor:
         """The loop's start from the initial draw eps = z0 (Heun's zhat_0 is formed in float64)."""
@@ -333,9 +347,16 @@ class StepPlan(NamedTuple):
         return zh.float()
 
 
-def _step_plan(diffusion, kind: str, t_desc: Sequence, eta: float, order: int, heun: Optional[HeunRows]) -> StepPlan:
+def _step_plan(diffusion, kind: str, t_desc: Sequence, eta: float, order: int,
+               rows: "Optional[HeunRows | LvRows]") -> StepPlan:
     """The only place that branches on the sampler kind.  A new sampler adds one branch here and one row to
-    engine.SAMPLER_STEPS (its update entry and operands).  'heun' takes the rows `heun` (t_desc = heun.t)."""
+    engine.SAMPLER_STEPS (its update entry and operands).  `rows`: the host rows of the kinds that bring their own -- 'heun'
+    takes HeunRows (t_desc = rows.t); 'ddpm_lv'  takes LvRows, the respaced rows of a chain of which t_desc
+    is a prefix, and reads the learned variance when they say so (diffusion.var_type 'learned_range').  run_sampler and
+    run_sampler_sharded hand over what they receive as `heun=`, the name that slot had while Heun was its only user and
+    that their parameter lists keep."""
+    heun = rows if isinstance(rows, HeunRows) else None
+    lv = rows if isinstance(rows, LvRows) else None
     E = len(t_desc)
     # v-prediction: the conversion rows, and the prediction type in the program cache keys (the epsilon keys stay as they are)
     v_pred = getattr(diffusion, "prediction_type", "epsilon") == "v_prediction"
@@ -351,8 +372,21 @@ def _step_plan(diffusion, kind: str, t_desc: Sequence, eta: float, order: int, h
         return StepPlan(kind, heun.rows, tuple(float(t) for t in t_desc), torch.float32, tuple(heun.noise_step),
                         tuple(heun.closes), with_noise, True, (kind, with_noise) + vkey, (order,), init=heun.init,
                         init_noise=bool(heun.gammas[0] > 0), pred=heun_pred_rows(heun) if v_pred else None)
+    if kind == "ddpm_lv":
+        learned = lv is not None and lv.learned
+        if x0:
+            raise CtsiError("update_form='x0' does not support the strided ancestral sampler or a learned reverse variance: "
+                            "the x0-form DDPM row carries one scalar noise scale; sample with 'ddpm' on fixed_small, a "
+                            "deterministic sampler, or update_form='eps'")
+        if lv is None or [int(t) for t in t_desc] != list(lv.chain[:E]):
+            raise ValueError("kind='ddpm_lv' needs the rows of lv_rows(...) (rows=; heun= of run_sampler) and t_desc = a prefix "
+                             "of their chain")
+        check_eps_form_timesteps(diffusion.alphas_cumprod, t_desc)
+        return StepPlan(kind, lv.rows[:E], tuple(int(t) for t in t_desc), torch.long,
+                        tuple(range(E)), (True,) * E, True, False, (kind, True) + vkey + (("learned",) if learned else ()), (),
+                        pred=diffusion.pred_to_eps_rows(t_desc) if v_pred else None, learned=learned)
     if kind not in ("ddim", "ddpm", "dpmpp"):
-        raise ValueError(f"unknown sampler kind {kind!r}: expected 'ddim', 'ddpm', 'dpmpp' or 'heun'")
+        raise ValueError(f"unknown sampler kind {kind!r}: expected 'ddim', 'ddpm', 'ddpm_lv', 'dpmpp' or 'heun'")
     if x0:
         coef = x0_coef_rows(diffusion, kind, t_desc, eta, order)
     elif kind == "ddim":
@@ -403,6 +437,9 @@ def _run_generic(plan: StepPlan, model, shape, conditioning, ctx, z0, *, noise_f
     `guidance` = (s, phi): classifier-free guidance -- two calls per evaluation, model(z, t, c) and model(z, t,
     zeros_like(c)), combined by ctsi_cfg_combine (the entry of the guided step program); eps_trajectory then holds the
     guided eps."""
+    if plan.learned:
+        raise CtsiError("the generic model(z, t, c) callable path does not support a learned reverse variance (a 2L-channel "
+                        "output): pass the engine's UNet3D(learn_sigma=True), or set var_type='fixed_small'")
     lib, sptr = ctx.lib, ctx.sptr
     n, L, d, h, w = [int(v) for v in shape]
     evals = len(plan.t)
@@ -412,7 +449,7 @@ def _run_generic(plan: StepPlan, model, shape, conditioning, ctx, z0, *, noise_f
     z_nd = torch.empty((n, d, h, w, L), dtype=torch.float32, device=dev)
     zin_nd = torch.empty_like(z_nd)
     eps_nd = torch.empty(((2 if guidance else 1) * n, d, h, w, L), dtype=torch.float32, device=dev)
-    hist = torch.zeros_like(z_nd) if SAMPLER_STEPS[plan.kind].hist else None
+    hist = torch.zeros_like(z_nd) if sampler_step_row(plan.kind).hist else None
     pred = None
     if plan.pred is not None:
         if hist is None and bool((plan.pred[:, 2] != 0).any()):
@@ -543,9 +580,13 @@ def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, 
 def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_desc: Sequence[int],
                 progress: bool, eta: float = 0.0, noise_fn=None, z_init: Optional[torch.Tensor] = None,
                 trajectory: Optional[list] = None, order: int = 2, eps_trajectory: Optional[list] = None,
-                heun: Optional[HeunRows] = None, guidance_scale: float = 1.0, guidance_rescale: float = 0.0):
+                heun: "Optional[HeunRows | LvRows]" = None, guidance_scale: float = 1.0, guidance_rescale: float = 0.0):
     """Shared reverse loop.  kind: 'ddim' | 'ddpm' | 'dpmpp' (DPM-Solver++ of `order` 1 or 2) | 'heun' (EDM of `order` 1
-    or 2 on the rows `heun` = heun_coef_rows(...), t_desc = heun.t); t_desc: descending timestep list.
+    or 2 on the rows `heun` = heun_coef_rows(...), t_desc = heun.t) | 'ddpm_lv' (the ancestral step on the respaced rows
+    `heun` = lv_rows(...) -- the slot takes the host rows of either kind and keeps its first user's name -- t_desc a prefix
+    of their chain; under diffusion.var_type == 'learned_range' the step reads the
+    variance channels of the UNet3D(learn_sigma=True) -- taken from the conditional rows under guidance -- DESIGN section 24);
+    t_desc: descending timestep list.
     `eps_trajectory` (unsharded runs only): receives the noise prediction of every U-Net evaluation, fp32 NCDHW.
     'heun': `trajectory` receives the state after every completed step (the VP latent zhat_{i+1}, which already holds
     step i+1's churn; the output last); the initial draw eps becomes zhat_0 = (sigma_0 eps + churn_0 eps_0) / a(sigma_hat_0),
@@ -570,6 +611,7 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
     unet = model
     if _is_engine_unet(model):
         check_attention_mode(unet.attention_mode)     # an unknown mode is an error before anything is drawn or built
+        check_pairing(diffusion, unet)                # var_type and learn_sigma belong together
     device = torch.device(device)
     ctx = Ctx.get(device if device.type == "cuda" else conditioning.device)
     n, L, d, h, w = [int(v) for v in shape]
@@ -595,6 +637,7 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
     precision = check_precision(getattr(unet, "inference_precision", "bf16"))
     if comm is not None and comm.world > 1:
         check_resblock_options_unsharded(unet, True)
+        check_learn_sigma_unsharded(unet, True)
         if precision != "bf16":
             raise CtsiError(f"the {precision} inference mode does not support depth sharding (unet.depth_shard_comm); "
                             "set inference_precision='bf16' or drop the communicator")
@@ -615,7 +658,8 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
             if plan.pred is not None or plan.x0:
                 kw["prediction"] = "v_prediction"
             prog = cls(ctx, unet, n, d, h, w, max_rows, unet.attention_mode, **kw)
-            prog.add_sampler_step(plan.kind, plan.with_noise, **(dict(update_form="x0") if plan.x0 else {}))
+            prog.add_sampler_step(plan.kind, plan.with_noise, **(dict(update_form="x0") if plan.x0 else {}),
+                                  **(dict(learned_variance=True) if plan.learned else {}))
             return prog
 
         prog: UNetProgram = cached_program(unet, key, build)
@@ -692,25 +736,52 @@ class _Sampler:
 
 
 class DDPMSampler(_Sampler):
-    """Ancestral sampling over all `diffusion.timesteps` steps (reference sampler.py:17-61)."""
+    """Ancestral sampling over all `diffusion.timesteps` steps (reference sampler.py:17-61), or -- additive, DESIGN section 24 --
+    over the strided subset DDIMSampler walks (`num_inference_steps`), on the respaced chain of Improved DDPM."""
+
+    def chain(self, num_inference_steps=None, clip_denoised=True):
+        """(kind, timesteps) of a run: ('ddpm', T-1 .. 0), the reference's loop and rows, when the chain is full-length, clips
+        and the variance is fixed-small; ('ddpm_lv', DDIM's timesteps) otherwise -- ctsi_ddpm_lv_step on respaced rows."""
+        T = self.timesteps
+        if num_inference_steps is not None and not 1 <= int(num_inference_steps) <= T:
+            raise ValueError(f"num_inference_steps must lie in [1, {T}], got {num_inference_steps!r}")
+        full = num_inference_steps is None or int(num_inference_steps) == T
+        learned = check_var_type(getattr(self.diffusion, "var_type", "fixed_small")) == "learned_range"
+        t_desc = list(reversed(range(T))) if full else [int(t) for t in self._get_timesteps(int(num_inference_steps))]
+        return ("ddpm" if full and clip_denoised and not learned else "ddpm_lv"), t_desc
+
+    def coef_rows(self, num_inference_steps=None, clip_denoised=True) -> torch.Tensor:
+        """The update's coefficient rows for such a run (what the step program reads)."""
+        kind, t_desc = self.chain(num_inference_steps, clip_denoised)
+        rows = lv_rows(self.diffusion, t_desc, clip_denoised) if kind == "ddpm_lv" else None
+        return _step_plan(self.diffusion, kind, t_desc, 0.0, 2, rows).coef
 
     @torch.no_grad()
     def sample(self, shape, conditioning, device, progress=True, noise_fn=None, num_steps=None,
-               trajectory=None, guidance_scale=1.0, guidance_rescale=0.0):
-        t_desc = list(reversed(range(self.timesteps)))[:num_steps]
-        return run_sampler(self.diffusion, self.model, shape, conditioning, device, kind="ddpm", t_desc=t_desc,
+               trajectory=None, guidance_scale=1.0, guidance_rescale=0.0, num_inference_steps=None, clip_denoised=True):
+        """`num_inference_steps` N (additive; None or T: every step, as ever): the N-step strided ancestral sampler.  The
+        timesteps are DDIMSampler's for N; the network is evaluated at the original timesteps and the update runs on the
+        respaced chain beta'_i = 1 - abar_{S_i} / abar_{S_{i-1}} with its own posterior coefficients and variances
+        (learned_sigma.respaced_ddpm_rows) -- the fixed-small beta~' or, under var_type='learned_range', the model's.
+        `clip_denoised=False` (additive) drops the clamp of the predicted z_0 to [-1, 1].  `num_steps`: a prefix (test hook)."""
+        kind, chain = self.chain(num_inference_steps, clip_denoised)
+        return run_sampler(self.diffusion, self.model, shape, conditioning, device, kind=kind, t_desc=chain[:num_steps],
                            progress=progress, noise_fn=noise_fn, trajectory=trajectory,
-                           guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
+                           guidance_scale=guidance_scale, guidance_rescale=guidance_rescale,
+                           **(dict(heun=lv_rows(self.diffusion, chain, clip_denoised)) if kind == "ddpm_lv" else {}))
 
     @torch.no_grad()
     def sample_with_stitching(self, v_thick_full, vae, patch_size=(8, 192, 192),
                               target_patch_size=(48, 192, 192), stride=(4, 96, 96), device='cuda',
-                              progress=True, dp_group=None, guidance_scale=1.0, guidance_rescale=0.0):
+                              progress=True, dp_group=None, guidance_scale=1.0, guidance_rescale=0.0,
+                              num_inference_steps=None, clip_denoised=True):
         check_guidance(guidance_scale, guidance_rescale)
+        kw = {} if num_inference_steps is None and clip_denoised else dict(num_inference_steps=num_inference_steps,
+                                                                          clip_denoised=clip_denoised)
         return _stitched(self, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress,
                          lambda shp, cond: self.sample(shp, cond, device, progress=False,
                                                        guidance_scale=guidance_scale,
-                                                       guidance_rescale=guidance_rescale), dp_group=dp_group)
+                                                       guidance_rescale=guidance_rescale, **kw), dp_group=dp_group)
 
 
 class DDIMSampler(_Sampler):
@@ -836,10 +907,11 @@ class HeunSampler(_Sampler):
 
 
 # generate() / generate_batch() sampler names -> how each samples a latent: (diffusion, model, shape, conditioning,
-# num_inference_steps, device, **sample kwargs).  DDPM runs all T steps: it ignores the step count.
+# num_inference_steps, device, **sample kwargs).  'ddpm' runs all T steps: it ignores the step count; 'ddpm_spaced' honours it.
 SAMPLERS = {
     'ddim': lambda df, m, shape, c, n, dev, **kw: DDIMSampler(df, m).sample(shape, c, n, dev, **kw),
     'ddpm': lambda df, m, shape, c, n, dev, **kw: DDPMSampler(df, m).sample(shape, c, dev, **kw),
+    'ddpm_spaced': lambda df, m, shape, c, n, dev, **kw: DDPMSampler(df, m).sample(shape, c, dev, num_inference_steps=n, **kw),
     'dpmpp_2m': lambda df, m, shape, c, n, dev, **kw: DPMSolverSampler(df, m, order=2).sample(shape, c, n, dev, **kw),
     'heun': lambda df, m, shape, c, n, dev, **kw: HeunSampler(df, m).sample(shape, c, n, dev, **kw),
 }

@@ -31,6 +31,7 @@ from .attention import check_attention_mode, emit_softmax_attention_train
 from .engine import Act, Ctx, Program, _ptr
 from .lib import CtsiError, WgradDesc
 from .norm_mod import DropoutState, emit_gn_bwd_mod
+from .learned_sigma import emit_hybrid_loss, loss_schedule_rows
 from .prediction import check_prediction_type
 
 
@@ -297,8 +298,12 @@ class UNetTrainProgram(TrainProgram):
         """`prediction` = 'v_prediction' (DESIGN section 18): the inputs come from ctsi_q_sample_v, which also writes the
         target v into `v_target`, and both loss launches read that buffer where the epsilon program reads the noise.
         `dropout`: the ResBlocks' middle passes are the dropout launches; the probability and the seed
-        are set per forward (`set_dropout`).  The scale-shift mode is the module tree's (`unet.use_scale_shift_norm`)."""
+        are set per forward (`set_dropout`).  The scale-shift mode is the module tree's (`unet.use_scale_shift_norm`).
+        A `unet.learn_sigma` model: the head, its weight gradient and its data gradient are 2L channels wide
+        (`eps` then holds both halves, `d_eps` both gradients), and the loss pair is ctsi_hybrid_loss_fwd / _bwd, which read
+        z0, the noise and the per-timestep rows `lv_sched` (set_diffusion) instead of a target buffer."""
         super().__init__(ctx)
+        self.learn_sigma = bool(getattr(unet, "learn_sigma", False))
         self.film = bool(getattr(unet, "use_scale_shift_norm", False))
         self.drop_state = DropoutState(self.persistent((1,), torch.int64, zero=True)) if dropout else None
         self.prediction = check_prediction_type(prediction)
@@ -311,7 +316,10 @@ class UNetTrainProgram(TrainProgram):
         self.n, self.d, self.h, self.w = n, d, h, w
         L = unet.latent_dim
         self.L = L
-        self.Lp = (L + 7) // 8 * 8
+        Lo = self.Lo = 2 * L if self.learn_sigma else L        # channels of the head
+        if unet.conv_out[2].out_channels != Lo:
+            raise CtsiError(f"internal: the head has {unet.conv_out[2].out_channels} channels, expected {Lo}")
+        self.Lp = (Lo + 7) // 8 * 8
         dev = ctx.device
         vox = d * h * w
         self.tape: List[Callable[[], None]] = []
@@ -342,9 +350,15 @@ class UNetTrainProgram(TrainProgram):
         self.mask = self.persistent((n, L, d), torch.float32, zero=True)
         self.use_mask = False
         self.gscale = self.persistent((1,), torch.float32, zero=True)
-        self.eps = self.persistent((n, d, h, w, L), torch.float32)
-        self.loss_out = self.persistent((1 + n,), torch.float32, zero=True)
-        self.loss_ws = self.persistent((self.lib.mse_loss_workspace_doubles(n),), torch.float64)
+        self.eps = self.persistent((n, d, h, w, Lo), torch.float32)
+        if self.learn_sigma:      # {total, mse, vb, per-sample sums of the two terms}
+            self.loss_out = self.persistent((3 + 2 * n,), torch.float32, zero=True)
+            self.loss_ws = self.persistent((self.lib.hybrid_loss_workspace_doubles(n),), torch.float64)
+            self.norm_vb = self.persistent((n,), torch.float32, zero=True)
+            self.lv_sched = self.persistent((1, 8), torch.float32)      # replaced by set_diffusion()
+        else:
+            self.loss_out = self.persistent((1 + n,), torch.float32, zero=True)
+            self.loss_ws = self.persistent((self.lib.mse_loss_workspace_doubles(n),), torch.float64)
         self.sqrt_ac = self.persistent((1,), torch.float32)      # replaced by set_diffusion()
         self.sqrt_1mac = self.persistent((1,), torch.float32)
 
@@ -428,16 +442,19 @@ class UNetTrainProgram(TrainProgram):
         slot = self.gn_finalize(x, gn.num_groups, st)
         y = self.t_gn(x, slot, gn, silu_pre=True)
         self.d_eps = Act(self.persistent((n * vox * self.Lp,), torch.bfloat16, zero=True), n, self.Lp, d, h, w, 0)
-        self.t_conv("conv_out", conv, y, None, f32_out=self.eps, f32_strides=(vox * L, 1, h * w * L, w * L, L),
+        self.t_conv("conv_out", conv, y, None, f32_out=self.eps, f32_strides=(vox * Lo, 1, h * w * Lo, w * Lo, Lo),
                     gy=self.d_eps)
 
         def run_loss():
             lib.mse_loss_fwd(_ptr(prog.eps), _ptr(prog.target), _ptr(prog.mask) if prog.use_mask else None,
                              _ptr(prog.norm), n, L, d, h, w, _ptr(prog.loss_ws), _ptr(prog.loss_out), sptr)
 
-        self._emit(run_loss, "loss.fwd", audit=dict(
-            kind="loss.fwd", pred=self.eps, noise=self.target, mask=lambda: prog.mask if prog.use_mask else None,
-            norm=self.norm, out=self.loss_out))
+        if self.learn_sigma:
+            emit_hybrid_loss(self, backward=False)
+        else:
+            self._emit(run_loss, "loss.fwd", audit=dict(
+                kind="loss.fwd", pred=self.eps, noise=self.target, mask=lambda: prog.mask if prog.use_mask else None,
+                norm=self.norm, out=self.loss_out))
         self.n_fwd = len(self.ops)
         self.generation = 0   # bumped by every run_forward (see there)
 
@@ -446,9 +463,12 @@ class UNetTrainProgram(TrainProgram):
             lib.mse_loss_bwd(_ptr(prog.eps), _ptr(prog.target), _ptr(prog.mask) if prog.use_mask else None,
                              _ptr(prog.norm), _ptr(prog.gscale), n, L, d, h, w, prog.d_eps.ip, prog.Lp, sptr)
 
-        self._emit(run_loss_bwd, "loss.bwd", audit=dict(
-            kind="loss_bwd", pred=self.eps, noise=self.target, mask=lambda: prog.mask if prog.use_mask else None, norm=self.norm,
-            gscale=self.gscale, out=self.d_eps))
+        if self.learn_sigma:
+            emit_hybrid_loss(self, backward=True)
+        else:
+            self._emit(run_loss_bwd, "loss.bwd", audit=dict(
+                kind="loss_bwd", pred=self.eps, noise=self.target, mask=lambda: prog.mask if prog.use_mask else None,
+                norm=self.norm, gscale=self.gscale, out=self.d_eps))
         for fn in reversed(self.tape):
             fn()
         self._emit_deferred_lin()
@@ -640,6 +660,8 @@ class UNetTrainProgram(TrainProgram):
     def set_diffusion(self, diffusion):
         self.sqrt_ac = diffusion.sqrt_alphas_cumprod.detach().to(self.ctx.device, torch.float32).contiguous()
         self.sqrt_1mac = diffusion.sqrt_one_minus_alphas_cumprod.detach().to(self.ctx.device, torch.float32).contiguous()
+        if self.learn_sigma:
+            self.lv_sched = loss_schedule_rows(diffusion).to(self.ctx.device).contiguous()
 
     def set_dropout(self, p: float, seed: int):
         """Probability and 64-bit seed of the NEXT forward (a program built with dropout=True only); the seed reaches the device
@@ -649,6 +671,12 @@ class UNetTrainProgram(TrainProgram):
         self.drop_state.set(p, seed)
         if self.drop_state.thr <= 0:
             raise CtsiError("internal: a dropout program needs a threshold > 0 (thr == 0 takes the default kernels)")
+
+    def set_vb_norm(self, norm_vb: torch.Tensor):
+        """The bound's per-sample factors of the NEXT forward (a learn_sigma program only): learned_sigma.hybrid_norms."""
+        if not self.learn_sigma:
+            raise CtsiError("internal: this train program has no variational-bound term")
+        self.norm_vb.copy_(norm_vb.to(torch.float32))
 
     def run_forward(self, z0, cond, t, noise, norm, mask=None) -> torch.Tensor:
         """Runs the forward launches and overwrites the tape (saved activations, t, noise) of this program: the

@@ -137,12 +137,22 @@ class UNet3D(nn.Module):
     with `unet.training` true; inference programs never drop.  It is read at each training forward, and the mask is a pure
     function of (seed, block, element), regenerated in the backward; the 64-bit seed is drawn from torch's default CPU
     generator once per training forward, or taken from the attribute `dropout_seed` when that is an int (a test hook).
+
+    Constructor argument `learn_sigma` (default False): True makes `conv_out[2]` a Conv3d(ch, 2 * latent_dim, 3,
+    padding=1) -- nothing else in the state dict changes, so a checkpoint loads into a model built with the same value -- and
+    forward returns (B, 2 * latent_dim, T, h, w): channels [0, L) the prediction (eps or v), channels [L, 2L) the raw variance
+    channels v of Improved DDPM, read when the diffusion's attribute `var_type` is 'learned_range'.  Every sampler, guidance, the three
+    inference precisions, stitching and training honour it; the deterministic samplers ignore the variance channels.  It needs
+    the whole depth on one device (CtsiError with depth sharding).
     """
 
     def __init__(self, latent_dim=4, model_channels=128, num_res_blocks=2, attention_levels=[1, 2],
                  channel_mult=(1, 2, 4, 4), num_heads=4, time_embed_dim=512, use_checkpoint=False,
-                 use_scale_shift_norm=False, dropout=0.0):
+                 use_scale_shift_norm=False, dropout=0.0, learn_sigma=False):
         super().__init__()
+        if not isinstance(learn_sigma, bool):
+            raise ValueError(f"learn_sigma must be True or False, got {learn_sigma!r}")
+        self.learn_sigma = learn_sigma
         self.use_scale_shift_norm = bool(use_scale_shift_norm)
         self.dropout = check_dropout(dropout)
         self.dropout_seed = None     # test hook: an int here replaces the seed drawn at each training forward
@@ -195,7 +205,7 @@ class UNet3D(nn.Module):
             self.up_samples.append(Upsample3D(ch) if level < self.num_levels - 1 else nn.Identity())
 
         self.conv_out = nn.Sequential(nn.GroupNorm(_largest_group_count(ch), ch), nn.SiLU(),
-                                      nn.Conv3d(ch, latent_dim, kernel_size=3, padding=1))
+                                      nn.Conv3d(ch, (2 if learn_sigma else 1) * latent_dim, kernel_size=3, padding=1))
 
     @staticmethod
     def _get_num_groups(channels):
@@ -239,4 +249,4 @@ class UNet3D(nn.Module):
             t_vals = torch.as_tensor(t).reshape(-1).tolist()
             prog_plain.set_schedule([int(v) if float(v).is_integer() else float(v) for v in t_vals])
             prog_plain.launch()
-            return prog_plain.eps_ncdhw()
+            return prog_plain.out_ncdhw()
