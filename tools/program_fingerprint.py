@@ -1,18 +1,16 @@
 """What the engine's program builders emit, as text two commits can be compared on.  For each of a fixed set of small
-programs (formula weights from tests/helpers.py; every path a conv can take: single-GPU, guided, fp32, depth-sharded with
-and without the overlap split, the VAE legs, both training programs) one line per op -- name, flops, kernel label, bytes,
-algorithmic bytes, the audit record's kind and a digest of its key set -- then the program's totals, the packed-weight cache
-keys it added and a SHA-256 of every output after an eager run (the U-Nets: again after capture() + two launch()es; the
-training programs: of every weight image after repack() and after an in-place update + fast_repack()).  The long uniform
-lists (op lines other than the launches of an overlapped conv, cache keys, weight images) are folded into one digest line
-each; --full prints them line by line, to find what a digest that differs hides.
+programs (formula weights from tests/helpers.py; every path a conv can take: single-GPU, guided, fp32 and bf16x3 on all
+three column tiles, depth-sharded with and without the overlap split, the VAE legs, both training programs) one line per
+op -- name, flops, kernel label, bytes, algorithmic bytes, the audit record's kind and a digest of its key set -- then the
+program's totals, the packed-weight cache keys it added and a SHA-256 of every output after an eager run (the U-Nets: again
+after capture() + two launch()es; the training programs: of every weight image after repack() and after an in-place update
++ fast_repack()).  The long uniform lists (op lines other than the launches of an overlapped conv, cache keys, weight
+images) are folded into one digest line each; --full prints them line by line, to find what a digest that differs hides.
 
     python tools/program_fingerprint.py [--full] > out.txt           # on a ROCm device
     python tools/program_fingerprint.py --compare a1.txt a2.txt b.txt
         a1 / a2: two runs of the parent commit, b: the new commit.  Lines a1 and a2 disagree on are named and left out;
-        the rest must be identical, except what the conv-emitter refactor may change: the kernel label (a split-K suffix)
-        and the algorithmic bytes of the three launches of an overlapped conv, and `pack_meta` (images now registered for
-        fp32 and overlapped convs).  Exit status 1 on any other difference."""
+        the rest must be identical.  Exit status 1 on any difference."""
 import gc
 import hashlib
 import importlib
@@ -74,6 +72,7 @@ def main():
     pkg = importlib.import_module("video-to-video-diffusion_amd")
     E = importlib.import_module("video-to-video-diffusion_amd.engine")
     EF = importlib.import_module("video-to-video-diffusion_amd.engine_f32")
+    EX = importlib.import_module("video-to-video-diffusion_amd.engine_x3")
     P = importlib.import_module("video-to-video-diffusion_amd.parallel")
     S = importlib.import_module("video-to-video-diffusion_amd.sampler")
     T = importlib.import_module("video-to-video-diffusion_amd.train_engine")
@@ -141,6 +140,10 @@ def main():
     unet_section("unet.tiny", TINY_UNET, (1, 8, 4, 8, 8))
     unet_section("unet.mid", MID_UNET, (1, 4, 8, 12, 8))
     unet_section("unet.tiny.f32", TINY_UNET, (1, 8, 4, 8, 8), cls=EF.UNetProgramF32)
+    unet_section("unet.tiny.x3", TINY_UNET, (1, 8, 4, 8, 8), cls=EX.UNetProgramX3)
+    # MID_UNET's third level has 128 channels: the 128x128 tile, column sums included, which TINY_UNET never reaches
+    unet_section("unet.mid.f32", MID_UNET, (1, 4, 8, 12, 8), cls=EF.UNetProgramF32)
+    unet_section("unet.mid.x3", MID_UNET, (1, 4, 8, 12, 8), cls=EX.UNetProgramX3)
     unet_section("unet.tiny.guided", TINY_UNET, (1, 8, 4, 8, 8), guided=True)
     comm1 = P.RcclComm.single(with_rccl=True)      # one rank, overlap forced: fork / join inside the capture too
     unet_section("unet.tiny.force1", TINY_UNET, (1, 8, 4, 8, 8), shard=lambda: P.ShardSpec(0, 1, comm1, 4, overlap="force"))
@@ -177,7 +180,8 @@ def main():
     vae.to(DEV)
     vid, lat = formula_input((1, 1, 3, 16, 12), 16).clamp(-1, 1), formula_input((1, 8, 3, 4, 3), 17)
     for prec, enc, dec in (("bf16", E.VAEEncodeProgram, E.VAEDecodeProgram),
-                           ("f32", EF.VAEEncodeProgramF32, EF.VAEDecodeProgramF32)):
+                           ("f32", EF.VAEEncodeProgramF32, EF.VAEDecodeProgramF32),
+                           ("x3", EX.VAEEncodeProgramX3, EX.VAEDecodeProgramX3)):
         section(f"vae.enc.{prec}", lambda: [enc(ctx, vae, 1, 3, 16, 12)], lambda ps: [("out", ps[0](vid))])
         section(f"vae.dec.{prec}", lambda: [dec(ctx, vae, 1, 3, 4, 3)], lambda ps: [("out", ps[0](lat))])
     lat6 = torch.cat([lat, lat.flip(2)], dim=2)
@@ -241,16 +245,9 @@ def compare(a1, a2, b):
         if x1 != x2:
             print(f"not reproduced by the parent, left out:\n  {x1}\n  {x2}")
         elif x1 != y:
-            f1, f2 = x1.split(), y.split()
-            overlapped = f1[1] == "op" and f1[3].rsplit(".", 1)[-1] in OVERLAPPED
-            if overlapped and f1[:5] == f2[:5] and f2[5] in (f1[5], f1[5] + "s") and f1[6:9] == f2[6:9] and f1[10:] == f2[10:]:
-                why = "permitted: label / algorithmic bytes of an overlapped launch"
-            elif f1[1] == f2[1] == "pack_meta":
-                why = "permitted: fp32 / overlapped images now registered in _pack_meta"
-            else:
-                why, bad = "NOT PERMITTED", bad + 1
-            print(f"- {x1}\n+ {y}    [{why}]")
-    print(f"{len(la1)} lines compared, {bad} differences that are not permitted")
+            bad += 1
+            print(f"- {x1}\n+ {y}")
+    print(f"{len(la1)} lines compared, {bad} differences")
     return 1 if bad else 0
 
 

@@ -1,11 +1,8 @@
-// bf16x3 inference mode: the implicit-GEMM convolution of conv_f32.hip with the inner product on the bf16 MFMA
+// bf16x3 inference mode: the implicit-GEMM convolution on fp32 tensors with the inner product on the bf16 MFMA
 // (v_mfma_f32_32x32x16_bf16) through a two-term split of both fp32 operands (include/ctsi.h, "bf16x3 inference mode"):
 //   xh = bf16(x) (round to nearest even), xl = bf16(x - float(xh)); the same for w;
 //   y = act(sum_k (xh wh + xh wl + xl wh) + bias [+ residual]),  every product exact in fp32, every sum in fp32.
-// Same four geometries, same GEMM view, same masked two-source reads, same 128 x {128, 64, 32} block of 4 waves with 32 x 32
-// accumulator tiles, same epilogue (bias, fp32 residual, tanh, NDHWC / strided store, column sums) as conv_f32_kernel.
-//
-// What differs:
+// Geometry, parameter block and epilogue are conv_f32_frame.h's, shared with conv_f32.hip.  This file's own:
 //   K slice     32 channels (cpad = c1 + c2 rounded up to 32) = two k-steps of 16; double-buffered, one barrier per slice.
 //   LDS images  k-contiguous: [row or column][32 bf16] with an 80-byte row stride, a `hi` and a `lo` image per operand.  Lane l
 //               of the MFMA holds A[row l & 31][k = 8 (l >> 5) + j] and B[k = 8 (l >> 5) + j][col l & 31], j = 0..7: one
@@ -18,132 +15,25 @@
 //   accumulation  two register sets per tile: `acc` takes xh wh, `crs` the two cross terms (about 2^-8 of the main term: summed
 //               among themselves they lose nothing to the main sum's rounding); crs is added to acc once, after the last slice.
 //               The order depends on the layer only: no atomics, no split-K, a relaunch is bit-identical.
-#include "ctsi_internal.h"
-#include <math.h>
+#include "conv_f32_frame.h"
 
-#define CX_BM 128
 #define CX_BK 32           // channels per K slice
 #define CX_RS 80           // LDS row stride in bytes (64 data + 16 padding)
-#define CX_MAXTAPS 48
 
-struct ConvX3Params {
-    const float* x1;
-    const float* x2;
+struct ConvX3Params : ConvF32Common {
     const bf16_t* wh;      // [class][slice][cout_pad][32]
     const bf16_t* wl;
-    const float* bias;
-    const float* res;
-    float* y;
-    float* colsum;         // optional [2][ncls * n * tps][cout_pad]
-    int C1, C2, Cin, Di, Hi, Wi;
-    int Do, Ho, Wo, Mh, Mw;
-    long long mrows;
-    int ntaps, cpad, K, Cout, CoutPad;
-    int n, tps, vec4, transposed;
-    int sh, sw, pd, ph, pw;
-    int mode, cout_stride, c_off, act;
-    long long sn, sc, sd, shs, sws;
-    signed char off[4][CX_MAXTAPS][3];
-    int rh[4], rw[4];
 };
 
-struct ConvX3Geom {
-    int ok;
-    int ncls, ntaps, cpad, K, bn, cout_pad;
-    int Do, Ho, Wo, Mh, Mw;
-    long long mrows;
-    int tps;
-    double flops;
-};
-
-static int cx_bn(int cout) { return cout <= 32 ? 32 : (cout <= 64 ? 64 : 128); }
-
-static void cx_tap(const ctsi_conv_desc& d, int cls, int t, int* kd, int* kh, int* kw) {
-    if (!d.transposed) {
-        *kd = t / (d.kh * d.kw);
-        *kh = (t / d.kw) % d.kh;
-        *kw = t % d.kw;
-    } else {
-        const int rh = cls >> 1, rw = cls & 1;
-        *kd = t / 4;
-        *kh = ((rh + d.ph) & 1) + 2 * ((t >> 1) & 1);
-        *kw = ((rw + d.pw) & 1) + 2 * (t & 1);
-    }
-}
-
-static ConvX3Geom cx_geom(const ctsi_conv_desc* dp, bool set_error) {
-    ConvX3Geom g = {};
-    g.ok = 0;
-#define CX_REJECT(...)                                      \
-    do {                                                    \
-        if (set_error) ctsi_set_error(__VA_ARGS__);        \
-        return g;                                           \
-    } while (0)
-    if (!dp) CX_REJECT("ctsi_conv_bf16x3: null descriptor");
-    const ctsi_conv_desc& d = *dp;
-    if (!(d.n > 0 && d.c1 > 0 && d.c2 >= 0 && d.cout > 0 && d.di > 0 && d.hi > 0 && d.wi > 0))
-        CX_REJECT("ctsi_conv_bf16x3: sizes must be positive (n=%d c1=%d c2=%d cout=%d in=%dx%dx%d)", d.n, d.c1, d.c2, d.cout,
-                  d.di, d.hi, d.wi);
-    if (d.halo_d) CX_REJECT("ctsi_conv_bf16x3: depth-sharded inputs (halo_d = 1) are not supported in the bf16x3 mode");
-    const bool k333 = !d.transposed && d.kd == 3 && d.kh == 3 && d.kw == 3 && d.sh == 1 && d.sw == 1 && d.pd == 1 &&
-                      d.ph == 1 && d.pw == 1;
-    const bool k111 = !d.transposed && d.kd == 1 && d.kh == 1 && d.kw == 1 && d.sh == 1 && d.sw == 1 && d.pd == 0 &&
-                      d.ph == 0 && d.pw == 0;
-    const bool k344 = d.kd == 3 && d.kh == 4 && d.kw == 4 && d.sh == 2 && d.sw == 2 && d.pd == 1 && d.ph == 1 && d.pw == 1;
-    if (d.transposed != 0 && d.transposed != 1) CX_REJECT("ctsi_conv_bf16x3: transposed=%d must be 0 or 1", d.transposed);
-    if (!(k333 || k111 || k344))
-        CX_REJECT("ctsi_conv_bf16x3: unsupported geometry (%s k=%dx%dx%d s=%dx%d p=%dx%dx%d); supported: 3x3x3 p1, 1x1x1, "
-                  "Conv3d / ConvTranspose3d (3,4,4) s(1,2,2) p1",
-                  d.transposed ? "ConvTranspose3d" : "Conv3d", d.kd, d.kh, d.kw, d.sh, d.sw, d.pd, d.ph, d.pw);
-    const long long cin = (long long)d.c1 + d.c2;
-    if (cin > 8192 || d.cout > 8192) CX_REJECT("ctsi_conv_bf16x3: channel counts above 8192 (cin=%lld cout=%d)", cin, d.cout);
-    g.ncls = d.transposed ? 4 : 1;
-    g.ntaps = d.transposed ? 12 : d.kd * d.kh * d.kw;
-    g.cpad = (int)((cin + CX_BK - 1) / CX_BK * CX_BK);
-    g.K = g.ntaps * g.cpad;
-    g.bn = cx_bn(d.cout);
-    g.cout_pad = (d.cout + g.bn - 1) / g.bn * g.bn;
-    if (d.transposed) {
-        g.Do = d.di - 2 * d.pd + d.kd - 1;
-        g.Ho = (d.hi - 1) * d.sh - 2 * d.ph + d.kh;
-        g.Wo = (d.wi - 1) * d.sw - 2 * d.pw + d.kw;
-        g.Mh = d.hi;
-        g.Mw = d.wi;
-    } else {
-        g.Do = d.di + 2 * d.pd - d.kd + 1;
-        g.Ho = (d.hi + 2 * d.ph - d.kh) / d.sh + 1;
-        g.Wo = (d.wi + 2 * d.pw - d.kw) / d.sw + 1;
-        g.Mh = g.Ho;
-        g.Mw = g.Wo;
-    }
-    if (g.Do < 1 || g.Ho < 1 || g.Wo < 1)
-        CX_REJECT("ctsi_conv_bf16x3: input %dx%dx%d too small for the kernel", d.di, d.hi, d.wi);
-    g.mrows = (long long)g.Do * g.Mh * g.Mw;
-    const long long tps = (g.mrows + CX_BM - 1) / CX_BM;
-    const long long in_elems = (long long)d.n * d.di * d.hi * d.wi * (cin > 0 ? cin : 1);
-    const long long out_elems = (long long)d.n * g.Do * g.Ho * g.Wo * d.cout;
-    if (tps >= (1ll << 31) || (long long)g.ncls * d.n > 65535 || in_elems >= (1ll << 40) || out_elems >= (1ll << 40))
-        CX_REJECT("ctsi_conv_bf16x3: tensor too large (rows per sample %lld, n=%d)", g.mrows, d.n);
-    g.tps = (int)tps;
-    // the useful 2 M N K (not the three products)
-    g.flops = 2.0 * d.n * (double)(d.transposed ? (long long)d.di * d.hi * d.wi : (long long)g.Do * g.Ho * g.Wo) * cin *
-              d.cout * d.kd * d.kh * d.kw;
-    g.ok = 1;
-    return g;
-#undef CX_REJECT
-}
+static ConvF32Geom cx_geom(const ctsi_conv_desc* desc) { return cf_geom(desc, CX_BK, "ctsi_conv_bf16x3", "bf16x3"); }
 
 // ---- weight images -----------------------------------------------------------------------------------------------------
 // hi / lo[cls][slice s = tap * (cpad / 32) + ci / 32][co][ci % 32] = the split of w(co, ci, tap of cls); zero for ci >= cin or
 // co >= cout (both halves: bf16(0) and bf16(0 - 0)).
-struct CxTapTable {
-    signed char k[4][CX_MAXTAPS][3];
-};
-
 __global__ void __launch_bounds__(256)
 conv_bf16x3_pack_kernel(const float* __restrict__ w, bf16_t* __restrict__ hi, bf16_t* __restrict__ lo, int cin, int cout,
                         int cpad, int nslices, int cout_pad, int kd, int kh, int kw, int transposed, long long total,
-                        CxTapTable tt) {
+                        CfTapTable tt) {
     const int cchunks = cpad / CX_BK;
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
         const int kk = (int)(e % CX_BK);
@@ -189,13 +79,13 @@ __device__ __forceinline__ void cx_split8(const float* f, cx_u4* h, cx_u4* l) {
 }
 
 template <int BN>
-constexpr int cx_lds_bytes() { return 2 * 2 * (CX_BM + BN) * CX_RS; }
+constexpr int cx_lds_bytes() { return 2 * 2 * (CF_BM + BN) * CX_RS; }
 
 template <int WGM, int WGN, int TM, int TN>
 __global__ void __launch_bounds__(256, 2)
 conv_bf16x3_kernel(const ConvX3Params p) {
     constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
-    static_assert(BM == CX_BM && WGM * WGN == 4, "4 waves over 128 rows");
+    static_assert(BM == CF_BM && WGM * WGN == 4, "4 waves over 128 rows");
     constexpr int A_IMG = BM * CX_RS, B_IMG = BN * CX_RS;      // bytes of one (buffer, half) image
     constexpr int NVB = BN / 32;                               // 16-byte B vectors per thread per slice (hi and lo together)
     extern __shared__ __attribute__((aligned(16))) unsigned char cx_smem[];
@@ -350,131 +240,35 @@ conv_bf16x3_kernel(const ConvX3Params p) {
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] += crs[i][j];
 
-    // ---- epilogue: bias, residual, activation, store, column sums (conv_f32_kernel's, on the same C/D lane map) ----
-    const int plane = p.Mh * p.Mw;
-    const int rh = p.rh[cls], rw = p.rw[cls];
-    float cs1[TN], cs2[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) cs1[j] = cs2[j] = 0.0f;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int col = nt * BN + (wn * TN + j) * 32 + cl;
-        const bool cok = col < p.Cout;
-        const float bias = (cok && p.bias) ? p.bias[col] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kl;
-                const long long m = (long long)tile * BM + row;
-                if (m >= p.mrows || !cok) continue;
-                const int od = (int)(m / plane);
-                const int rem = (int)(m - (long long)od * plane);
-                int oh = rem / p.Mw, ow = rem - (rem / p.Mw) * p.Mw;
-                if (p.transposed) {
-                    oh = 2 * oh + rh;
-                    ow = 2 * ow + rw;
-                }
-                long long idx;
-                if (p.mode == 0)
-                    idx = ((((long long)b * p.Do + od) * p.Ho + oh) * p.Wo + ow) * p.cout_stride + p.c_off + col;
-                else
-                    idx = (long long)b * p.sn + (long long)col * p.sc + (long long)od * p.sd + (long long)oh * p.shs +
-                          (long long)ow * p.sws;
-                float v = acc[i][j][r] + bias;
-                if (p.res) v += p.res[idx];
-                if (p.act == 1) v = tanhf(v);
-                p.y[idx] = v;
-                cs1[j] += v;
-                cs2[j] += v * v;
-            }
-    }
-    if (p.colsum) {
-        // lanes l and l + 32 hold the same column; then the WGM waves of one column range, in wave order, through LDS
-        float* red = reinterpret_cast<float*>(cx_smem);      // [WGM][BN][2]; every wave is past the main loop's last barrier
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const float o1 = __shfl_xor(cs1[j], 32), o2 = __shfl_xor(cs2[j], 32);
-            if (kl == 0) {
-                const int cb = (wn * TN + j) * 32 + cl;
-                red[(wm * BN + cb) * 2 + 0] = cs1[j] + o1;
-                red[(wm * BN + cb) * 2 + 1] = cs2[j] + o2;
-            }
-        }
-        __syncthreads();
-        if (tid < BN) {
-            float t1 = 0.0f, t2 = 0.0f;
-#pragma unroll
-            for (int q = 0; q < WGM; ++q) {
-                t1 += red[(q * BN + tid) * 2 + 0];
-                t2 += red[(q * BN + tid) * 2 + 1];
-            }
-            const long long tg = (long long)blockIdx.z * p.tps + tile;
-            const long long slab = (long long)gridDim.z * p.tps * p.CoutPad;
-            const int col = nt * BN + tid;
-            p.colsum[tg * p.CoutPad + col] = t1;
-            p.colsum[slab + tg * p.CoutPad + col] = t2;
-        }
-    }
+    cf_epilogue<WGM, WGN, TM, TN>(p, acc, reinterpret_cast<float*>(cx_smem), tile, nt, cls, b, wm, wn, kl, cl, tid);
 }
 
 // ---- C ABI -------------------------------------------------------------------------------------------------------------
 extern "C" int ctsi_conv_bf16x3_supported(const ctsi_conv_desc* desc) {
-    return cx_geom(desc, true).ok;
+    return cx_geom(desc).ok;
 }
 
 extern "C" size_t ctsi_conv_bf16x3_weight_bytes(const ctsi_conv_desc* desc) {
-    const ConvX3Geom g = cx_geom(desc, true);
-    if (!g.ok) return 0;
-    return (size_t)2 * g.ncls * g.K * g.cout_pad * sizeof(bf16_t);
+    const ConvF32Geom g = cx_geom(desc);
+    return g.ok ? (size_t)2 * g.ncls * g.K * g.cout_pad * sizeof(bf16_t) : 0;
 }
 
 extern "C" double ctsi_conv_bf16x3_flops(const ctsi_conv_desc* desc) {
-    const ConvX3Geom g = cx_geom(desc, true);
+    const ConvF32Geom g = cx_geom(desc);
     return g.ok ? g.flops : 0.0;
 }
 
 extern "C" int ctsi_conv_bf16x3_geometry(const ctsi_conv_desc* desc, int* d_out, int* h_out, int* w_out, int* tiles_per_sample,
                                          int* nclass, int* cout_pad) {
-    const ConvX3Geom g = cx_geom(desc, true);
-    if (!g.ok) return CTSI_ERR_INVALID;
-    if (d_out) *d_out = g.Do;
-    if (h_out) *h_out = g.Ho;
-    if (w_out) *w_out = g.Wo;
-    if (tiles_per_sample) *tiles_per_sample = g.tps;
-    if (nclass) *nclass = g.ncls;
-    if (cout_pad) *cout_pad = g.cout_pad;
-    return CTSI_OK;
-}
-
-static void cx_taps(const ctsi_conv_desc& d, const ConvX3Geom& g, signed char (*k)[CX_MAXTAPS][3],
-                    signed char (*off)[CX_MAXTAPS][3], int* rh, int* rw) {
-    for (int cls = 0; cls < 4; ++cls) {
-        rh[cls] = cls >> 1;
-        rw[cls] = cls & 1;
-        for (int t = 0; t < CX_MAXTAPS; ++t) {
-            int a = 0, b = 0, c = 0;
-            if (cls < g.ncls && t < g.ntaps) cx_tap(d, cls, t, &a, &b, &c);
-            k[cls][t][0] = (signed char)a; k[cls][t][1] = (signed char)b; k[cls][t][2] = (signed char)c;
-            if (!d.transposed) {
-                off[cls][t][0] = (signed char)a; off[cls][t][1] = (signed char)b; off[cls][t][2] = (signed char)c;
-            } else {   // od = id - pd + kd, oh = 2 ih - ph + kh with oh = 2 mh + rh
-                off[cls][t][0] = (signed char)(d.pd - a);
-                off[cls][t][1] = (signed char)((rh[cls] + d.ph - b) / 2);
-                off[cls][t][2] = (signed char)((rw[cls] + d.pw - c) / 2);
-            }
-        }
-    }
+    return cf_geometry_out(cx_geom(desc), d_out, h_out, w_out, tiles_per_sample, nclass, cout_pad);
 }
 
 extern "C" int ctsi_conv_bf16x3_pack_weights(const ctsi_conv_desc* desc, const float* w, void* packed, void* stream) {
     CTSI_CHECK_ARG(w && packed, "ctsi_conv_bf16x3_pack_weights: null argument");
-    const ConvX3Geom g = cx_geom(desc, true);
+    const ConvF32Geom g = cx_geom(desc);
     if (!g.ok) return CTSI_ERR_INVALID;
-    CxTapTable tt;
-    signed char off[4][CX_MAXTAPS][3];
-    int rh[4], rw[4];
-    cx_taps(*desc, g, tt.k, off, rh, rw);
+    CfTapTable tt;
+    cf_taps(*desc, g, &tt, nullptr);
     const long long total = (long long)g.ncls * g.K * g.cout_pad;
     long long blocks = (total + 255) / 256;
     if (blocks > 8192) blocks = 8192;
@@ -498,35 +292,15 @@ static void cx_launch(const dim3& grid, hipStream_t st, const ConvX3Params& p) {
 extern "C" int ctsi_conv_bf16x3_fwd(const ctsi_conv_desc* desc, const float* x1, const float* x2, const void* packed_w,
                                     const float* bias, const float* residual, const ctsi_conv_out* out, void* stream) {
     CTSI_CHECK_ARG(desc && x1 && packed_w && out && out->y, "ctsi_conv_bf16x3_fwd: null argument");
-    const ConvX3Geom g = cx_geom(desc, true);
+    const ConvF32Geom g = cx_geom(desc);
     if (!g.ok) return CTSI_ERR_INVALID;
-    const ctsi_conv_desc& d = *desc;
-    CTSI_CHECK_ARG(d.c2 == 0 || x2, "ctsi_conv_bf16x3_fwd: c2=%d but x2 is null", d.c2);
-    CTSI_CHECK_ARG(out->mode == 0 || out->mode == 1, "ctsi_conv_bf16x3_fwd: out mode %d (0: fp32 NDHWC, 1: fp32 strided)",
-                   out->mode);
-    CTSI_CHECK_ARG(out->mode != 0 || (out->c_off >= 0 && out->cout_stride >= out->c_off + d.cout),
-                   "ctsi_conv_bf16x3_fwd: channel slice [%d, %d) outside stride %d", out->c_off, out->c_off + d.cout,
-                   out->cout_stride);
-    CTSI_CHECK_ARG(out->act == 0 || out->act == 1, "ctsi_conv_bf16x3_fwd: act %d (0: none, 1: tanh)", out->act);
-    CTSI_CHECK_ARG(out->gn_x == nullptr, "ctsi_conv_bf16x3_fwd: the fused GroupNorm tail is a bf16-path epilogue");
-    CTSI_CHECK_ARG(((uintptr_t)packed_w & 15) == 0, "ctsi_conv_bf16x3_fwd: the packed image must be 16-byte aligned");
     ConvX3Params p = {};
-    p.x1 = x1; p.x2 = x2; p.bias = bias; p.res = residual;
+    const int rc = cf_fill("ctsi_conv_bf16x3_fwd", *desc, g, x1, x2, bias, residual, out, &p);
+    if (rc != CTSI_OK) return rc;
+    CTSI_CHECK_ARG(((uintptr_t)packed_w & 15) == 0, "ctsi_conv_bf16x3_fwd: the packed image must be 16-byte aligned");
     p.wh = (const bf16_t*)packed_w;
     p.wl = p.wh + (long long)g.ncls * g.K * g.cout_pad;
-    p.y = (float*)out->y; p.colsum = out->colsum;
-    p.C1 = d.c1; p.C2 = d.c2; p.Cin = d.c1 + d.c2; p.Di = d.di; p.Hi = d.hi; p.Wi = d.wi;
-    p.Do = g.Do; p.Ho = g.Ho; p.Wo = g.Wo; p.Mh = g.Mh; p.Mw = g.Mw; p.mrows = g.mrows;
-    p.ntaps = g.ntaps; p.cpad = g.cpad; p.K = g.K; p.Cout = d.cout; p.CoutPad = g.cout_pad;
-    p.n = d.n; p.tps = g.tps;
-    p.vec4 = (d.c1 % 4 == 0 && d.c2 % 4 == 0 && ((uintptr_t)x1 & 15) == 0 && ((uintptr_t)x2 & 15) == 0) ? 1 : 0;
-    p.transposed = d.transposed;
-    p.sh = d.sh; p.sw = d.sw; p.pd = d.pd; p.ph = d.ph; p.pw = d.pw;
-    p.mode = out->mode; p.cout_stride = out->cout_stride; p.c_off = out->c_off; p.act = out->act;
-    p.sn = out->sn; p.sc = out->sc; p.sd = out->sd; p.shs = out->sh; p.sws = out->sw;
-    signed char kt[4][CX_MAXTAPS][3];
-    cx_taps(d, g, kt, p.off, p.rh, p.rw);
-    const dim3 grid((unsigned)g.tps, (unsigned)(g.cout_pad / g.bn), (unsigned)(g.ncls * d.n));
+    const dim3 grid = cf_grid(*desc, g);
     hipStream_t st = (hipStream_t)stream;
     if (g.bn == 128)
         cx_launch<2, 2, 2, 2>(grid, st, p);

@@ -19,7 +19,7 @@ call on this path: torch allocates and copies.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -30,11 +30,22 @@ from .lib import ConvDesc, ConvOut, CtsiError
 PRECISIONS = ("bf16", "fp32", "bf16x3")       # "bf16x3": engine_x3.py
 
 
-def _f32_pack_sig(desc: ConvDesc, cout_pad: int, wbytes: int) -> tuple:
-    """The layout half of an fp32 packed-image cache key: ctsi_conv_f32_pack_weights reads the descriptor's channel / kernel
-    fields only (never the batch or the spatial size; each supported kernel geometry has one padding).  The precision leads
-    the key, so a bf16 program never finds it."""
-    return ("fp32", int(desc.transposed), (desc.kd, desc.kh, desc.kw), (desc.sh, desc.sw), desc.c1, desc.c2, desc.cout,
+class ConvFamily(NamedTuple):
+    """One kernel family of the convolution on fp32 tensors (csrc/conv_f32_frame.h has what the families share)."""
+    entry: str          # the C entry points are ctsi_<entry>_{supported, geometry, weight_bytes, pack_weights, flops, fwd}
+    key_lead: str       # leads the packed-image cache key
+    audit_kind: str
+    label: str          # kernel label prefix
+
+
+CONV_F32 = ConvFamily(entry="conv_f32", key_lead="fp32", audit_kind="conv_fwd", label="conv_f32_mfma")
+
+
+def _f32_pack_sig(desc: ConvDesc, cout_pad: int, wbytes: int, lead: str = "fp32") -> tuple:
+    """The layout half of a packed-image cache key of the convolutions on fp32 tensors: ctsi_conv_*_pack_weights reads the
+    descriptor's channel / kernel fields only (never the batch or the spatial size; each supported kernel geometry has one
+    padding).  The precision leads the key, so a program of another precision never finds it."""
+    return (lead, int(desc.transposed), (desc.kd, desc.kh, desc.kw), (desc.sh, desc.sw), desc.c1, desc.c2, desc.cout,
             cout_pad, wbytes)
 
 
@@ -52,16 +63,22 @@ class _F32Ops:
 
     def act(self, n, c, d, h, w, halo: Optional[int] = None) -> Act:
         if halo:
-            raise CtsiError("the fp32 inference mode does not support depth sharding")
+            raise CtsiError(f"the {self.precision} inference mode does not support depth sharding")
         return Act(self.pool.get(n * c * d * h * w, torch.float32), n, c, d, h, w, 0)
 
-    def conv(self, name: str, weight_fn, bias_fn, x1: Act, x2: Optional[Act], *, transposed=False, k=(3, 3, 3), s=(1, 1),
-             p=(1, 1, 1), cout: int, cin_w: Optional[int] = None, out: Optional[Act] = None, want_stats=False,
-             f32_out: Optional[torch.Tensor] = None, f32_strides=None, act: int = 0, fuse_gn=None, ext_out: bool = False,
-             norm_in=None, residual: Optional[Act] = None):
-        """engine.Program.conv (which documents the parameters) on ctsi_conv_f32_fwd.  `residual` (fp32 Act of the output's
-        shape) is added in the epilogue.  The fused GroupNorm tail has no fp32 form."""
+    def conv(self, name: str, weight_fn, bias_fn, x1: Act, x2: Optional[Act], **kw):
+        """engine.Program.conv on ctsi_conv_f32_fwd (_conv_family has the parameters)."""
+        return self._conv_family(CONV_F32, name, weight_fn, bias_fn, x1, x2, **kw)
+
+    def _conv_family(self, fam: ConvFamily, name: str, weight_fn, bias_fn, x1: Act, x2: Optional[Act], *, transposed=False,
+                     k=(3, 3, 3), s=(1, 1), p=(1, 1, 1), cout: int, cin_w: Optional[int] = None, out: Optional[Act] = None,
+                     want_stats=False, f32_out: Optional[torch.Tensor] = None, f32_strides=None, act: int = 0, fuse_gn=None,
+                     ext_out: bool = False, norm_in=None, residual: Optional[Act] = None):
+        """engine.Program.conv (which documents the parameters) on the kernels of `fam`.  `residual` (fp32 Act of the
+        output's shape) is added in the epilogue.  The fused GroupNorm tail has no fp32 form."""
         lib, prog = self.lib, self
+        supported, geometry, weight_bytes, pack_weights, flops, fwd = (
+            getattr(lib, f"{fam.entry}_{f}") for f in ("supported", "geometry", "weight_bytes", "pack_weights", "flops", "fwd"))
         if fuse_gn is not None or ext_out:
             raise CtsiError("internal: the fused GroupNorm tail / halo-extended outputs are bf16-path features")
         c2 = 0 if x2 is None else x2.c
@@ -73,19 +90,18 @@ class _F32Ops:
             self._norm_in_pass(x1, norm_in)
         desc = ConvDesc(int(transposed), k[0], k[1], k[2], s[0], s[1], p[0], p[1], p[2], x1.n, x1.c, c2, cout, x1.d, x1.h,
                         x1.w, 0)
-        if not lib.conv_f32_supported(C.byref(desc)):
+        if not supported(C.byref(desc)):
             raise CtsiError(f"{name}: {lib.last_error().decode()}")
         self.keep.append(desc)
         do, ho, wo, tps, ncls, cpad = (C.c_int() for _ in range(6))
-        lib.conv_f32_geometry(C.byref(desc), C.byref(do), C.byref(ho), C.byref(wo), C.byref(tps), C.byref(ncls),
-                              C.byref(cpad))
+        geometry(C.byref(desc), C.byref(do), C.byref(ho), C.byref(wo), C.byref(tps), C.byref(ncls), C.byref(cpad))
         do, ho, wo, tps, ncls, cpad = do.value, ho.value, wo.value, tps.value, ncls.value, cpad.value
-        wbytes = lib.conv_f32_weight_bytes(C.byref(desc))
+        wbytes = weight_bytes(C.byref(desc))
         bias = self._conv_bias(bias_fn)
         sptr = self.ctx.sptr
-        holder = self._weight_image(weight_fn, _f32_pack_sig(desc, cpad, wbytes), wbytes,
-                                    lambda w, t: lib.conv_f32_pack_weights(C.byref(desc), w, t, sptr))
-        fl = lib.conv_f32_flops(C.byref(desc))
+        holder = self._weight_image(weight_fn, _f32_pack_sig(desc, cpad, wbytes, fam.key_lead), wbytes,
+                                    lambda w, t: pack_weights(C.byref(desc), w, t, sptr))
+        fl = flops(C.byref(desc))
         self._count_conv(name, fl)
         stats = self._conv_stats(ncls * x1.n * tps, tps, cpad, ncls) if want_stats else None
         co = ConvOut()
@@ -101,15 +117,16 @@ class _F32Ops:
 
         def run():
             co.colsum = prog._colsum.data_ptr() if want_stats else 0
-            lib.conv_f32_fwd(C.byref(desc), x1p, x2p, _ptr(holder[0]), bp, rp, C.byref(co), sptr)
+            fwd(C.byref(desc), x1p, x2p, _ptr(holder[0]), bp, rp, C.byref(co), sptr)
 
         bn = 32 if cout <= 32 else (64 if cout <= 64 else 128)
-        kernel = "conv_f32_mfma_128x%d%s" % (bn, "t" if transposed else ("d" if tuple(s) == (2, 2) else ""))
+        kernel = "%s_128x%d%s" % (fam.label, bn, "t" if transposed else ("d" if tuple(s) == (2, 2) else ""))
         alg = (4.0 * x1.n * x1.d * x1.h * x1.w * (x1.c + c2) + float(wbytes) + 4.0 * x1.n * do * ho * wo * cout
                * (2 if residual is not None else 1))
         self._emit(run, name, fl, kernel, alg_bytes=alg,
-                   audit=dict(kind="conv_fwd", f32=True, x1=x1, x2=x2, weight=weight_fn, bias=bias, transposed=bool(transposed),
-                              k=tuple(k), s=tuple(s), p=tuple(p), cout=cout, cin_w=None, act=act, out=out_act, f32_out=f32_out,
+                   audit=dict(kind=fam.audit_kind, f32=True, x1=x1, x2=x2, weight=weight_fn, bias=bias,
+                              transposed=bool(transposed), k=tuple(k), s=tuple(s), p=tuple(p), cout=cout, cin_w=None, act=act,
+                              out=out_act, f32_out=f32_out,
                               f32_strides=None if f32_out is None else tuple(int(v) for v in f32_strides), stats=stats,
                               colsum=(lambda: prog._colsum) if want_stats else None, stream_tail=False, fuse_gn=None,
                               residual=residual))
@@ -195,8 +212,9 @@ class _F32Ops:
     def attention(self, m, x: Act, mode: str = "fast") -> Act:
         """TemporalAttention, fast mode (csrc/attention.hip has the identity it rests on)."""
         if mode != "fast":
-            raise CtsiError("the fp32 inference mode supports attention_mode='fast' only (the exact mode evaluates the "
-                            "same mathematics, DESIGN section 3.2; the softmax mode has bf16 kernels only, section 19)")
+            raise CtsiError(f"the {self.precision} inference mode supports attention_mode='fast' only (the exact mode "
+                            "evaluates the same mathematics, DESIGN section 3.2; the softmax mode has bf16 kernels only, "
+                            "section 19)")
         lib, sptr, prog = self.lib, self.ctx.sptr, self
         n, c, d, h, w = x.n, x.c, x.d, x.h, x.w
         tps = lib.attn_depthsum_f32_tiles(h, w)
@@ -260,11 +278,12 @@ class UNetProgramF32(_F32Ops, UNetProgram):
     def __init__(self, ctx: Ctx, unet, n: int, d: int, h: int, w: int, max_rows: int, attention_mode="fast", shard=None,
                  guided: bool = False, rescale: bool = False, prediction: str = "epsilon"):
         if shard is not None:
-            raise CtsiError("the fp32 inference mode does not support depth sharding")
+            raise CtsiError(f"the {self.precision} inference mode does not support depth sharding")
         check_attention_mode(attention_mode)
         if attention_mode != "fast":
-            raise CtsiError("the fp32 inference mode supports attention_mode='fast' only (the exact mode evaluates the "
-                            "same mathematics, DESIGN section 3.2; the softmax mode has bf16 kernels only, section 19)")
+            raise CtsiError(f"the {self.precision} inference mode supports attention_mode='fast' only (the exact mode "
+                            "evaluates the same mathematics, DESIGN section 3.2; the softmax mode has bf16 kernels only, "
+                            "section 19)")
         super().__init__(ctx, unet, n, d, h, w, max_rows, attention_mode, shard=None, guided=guided, rescale=rescale,
                          prediction=prediction)
 
@@ -311,5 +330,5 @@ class VAEDecodeProgramF32(VAEEncodeProgramF32, VAEDecodeProgram):
 
     def __init__(self, ctx: Ctx, vae, n, d, h, w, shard=None):
         if shard is not None:
-            raise CtsiError("the fp32 inference mode does not support depth sharding")
+            raise CtsiError(f"the {self.precision} inference mode does not support depth sharding")
         VAEDecodeProgram.__init__(self, ctx, vae, n, d, h, w)
