@@ -533,7 +533,7 @@ int ctsi_gn_colsum_f32(const float* x, float* colsum, int n, int c, int d, int h
 int ctsi_gn_apply_f32(const float* x, float* y, const double* sums, const float* gamma, const float* beta, int n, int c,
                       int d, int h, int w, int d_stat, int groups, float eps, int silu_pre, const float* tbias,
                       int tbias_stride, const int* step_ptr, const float* residual, int silu_post, void* stream);
-/* The ResBlock's middle pass with the ADM-style options (norm_mod.hip).  ctsi_gn_apply_mod has the argument
+/* The ResBlock's middle pass with the ADM-style options (norm_act.hip, f32_ops.hip, norm_bwd.hip).  ctsi_gn_apply_mod has the argument
  * list of ctsi_gn_apply plus: film (0: y = silu(gn(x)) + e, the time row holds c values; 1: y = silu(gn(x) * (1 + s) + b), the
  * time row holds (s | b), 2c values, scale first), p_thr16 (dropout threshold in 1/65536 units, 0 = none: an element is kept iff
  * its 16-bit Philox lane >= p_thr16), inv_keep (65536 / (65536 - p_thr16)), seed (DEVICE pointer to one 64-bit seed; may be

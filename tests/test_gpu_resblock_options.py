@@ -1,4 +1,5 @@
-"""GPU: the ResBlock options -- scale-shift time conditioning and dropout on conv2's input (csrc/norm_mod.hip)
+"""GPU: the ResBlock options -- scale-shift time conditioning and dropout on conv2's input (csrc/norm_act.hip, csrc/f32_ops.hip,
+csrc/norm_bwd.hip)
 -- from the kernels up to sampling and training, against tests/resblock_restatement.py.
 
 Kernels: float64 from the kernel's own operands.
@@ -170,6 +171,24 @@ def test_forward_bf16_step_ptr_selects_the_row_block(G, case):
     print(f"forward {case} step_ptr = 1: {res['ulps']:.3f} ulp, rel-L2 {res['rel_l2']:.2e}; row block 0 is {rel_l2(other, ref):.3f} away")
     assert res["ok"], res
     assert rel_l2(other, ref) > 0.25
+
+
+@pytest.mark.parametrize("case", [(2, 32, 3, 5, 7), (2, 40, 3, 5, 7), (1, 192, 2, 3, 5)], ids=lambda c: "n%d_c%d_%dx%dx%d" % c)
+def test_forward_bf16_without_options_is_the_default_pass(G, case):
+    """ctsi_gn_apply_mod(film=0, p_thr16=0) is ctsi_gn_apply(silu_pre=1, tbias): the same raw bf16 (contiguous ranges with a ragged
+    tail, no constant chunk, grid-stride over three blocks' worth of chunks per row)."""
+    n, c, d, h, w = case
+    ops = _operands(case, False)
+    ctx = G.ctx()
+    y = torch.full_like(ops["x"], float("nan"))
+    step_ptr = torch.tensor([1], dtype=torch.int32, device=DEV)
+    with ctx.scope():
+        ctx.lib.gn_apply(_ptr(ops["x"]), _ptr(y), _ptr(ops["sums"]), _ptr(ops["gamma"]), _ptr(ops["beta"]), n, c, d, h, w, d, GROUPS,
+                         EPS, 1, _ptr(ops["rows"], 4 * TB_OFF), ops["stride"], _ptr(step_ptr), None, 0, ctx.sptr)
+    torch.cuda.synchronize()
+    y_mod = _fwd(G, case, ops, False, False, step=1)
+    assert torch.isfinite(y.float()).all()
+    assert torch.equal(y_mod.view(torch.int16), y.view(torch.int16))
 
 
 @pytest.mark.parametrize("case", CASES, ids=IDS)

@@ -1,5 +1,5 @@
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123 constants) and the
-// dropout keep rule built on it.  ONE text for the device kernels and the host entry points (norm_mod.hip): the training
+// dropout keep rule built on it.  ONE text for the device kernels and the host entry points (norm_act.hip, norm_bwd.hip): the training
 // backward regenerates the forward's mask from (seed, layer, element) instead of storing it.
 #pragma once
 #include <stdint.h>

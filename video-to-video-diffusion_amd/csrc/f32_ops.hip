@@ -5,7 +5,7 @@
 // Every reduction has a fixed order and no atomics: a relaunch is bit-identical.  Transcendentals are the accurate libm
 // forms (expf, tanhf), not the 1-ulp hardware approximations the bf16 path rounds away.
 #include "ctsi_internal.h"
-#include <math.h>
+#include "gn_frame.h"
 
 #define F32_GN_TILE_ROWS 512
 #define F32_ATTN_TILE_POS 64
@@ -62,12 +62,15 @@ extern "C" int ctsi_gn_colsum_f32(const float* x, float* colsum, int n, int c, i
 
 // ---- GroupNorm apply: y = [silu](gn(x)) [+ tbias] [+ residual] [silu] ------------------------------------------------------
 // grid (blocks, n); block 256.  Scale / shift / time bias of every channel in LDS; 4 channels per thread when c % 4 == 0.
-template <bool SILU_PRE, bool TB, bool RES, bool SILU_POST, bool V4>
+// FILM (the ResBlock's scale-shift option; inference, so no dropout): with SILU_PRE and a time row (s | b) of
+// 2c values, y = silu(gn(x) * (1 + s) + b) -- the prologue's coefficients change, nothing is added afterwards.
+template <bool SILU_PRE, bool TB, bool RES, bool SILU_POST, bool FILM, bool V4>
 __global__ void __launch_bounds__(256)
 gn_apply_f32_kernel(const float* __restrict__ x, float* __restrict__ y, const double* __restrict__ sums,
                     const float* __restrict__ gamma, const float* __restrict__ beta, int c, long long vox, long long vox_stat,
                     int groups, float eps, const float* __restrict__ tbias, int tbias_stride, const int* __restrict__ step_ptr,
                     int n_total, const float* __restrict__ residual) {
+    constexpr bool ADD_TB = TB && !FILM;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* s_scale = reinterpret_cast<float*>(smem_raw);
     float* s_shift = s_scale + c;
@@ -78,14 +81,18 @@ gn_apply_f32_kernel(const float* __restrict__ x, float* __restrict__ y, const do
     long long trow = nb;
     if (TB && step_ptr) trow += (long long)(*step_ptr) * n_total;
     for (int ch = tid; ch < c; ch += 256) {
-        const int g = ch / cpg;
-        const double m = sums[((long long)nb * groups + g) * 2 + 0] / cnt;
-        double var = sums[((long long)nb * groups + g) * 2 + 1] / cnt - m * m;
-        if (var < 0.0) var = 0.0;
-        const double rstd = 1.0 / sqrt(var + (double)eps);
-        s_scale[ch] = (float)((double)gamma[ch] * rstd);
-        s_shift[ch] = (float)((double)beta[ch] - m * (double)gamma[ch] * rstd);
-        if (TB) s_tb[ch] = tbias[trow * tbias_stride + ch];
+        const GnMeanRstd st = gn_mean_rstd(sums + ((long long)nb * groups + ch / cpg) * 2, cnt, eps);
+        const double m = st.mean, rstd = st.rstd;
+        if (FILM) {      // the shift as mean * (gamma * rstd): the one form the engine emits, kept to the bit
+            const double sc = (double)gamma[ch] * rstd, sh = (double)beta[ch] - m * sc;
+            const double s1 = 1.0 + (double)tbias[trow * tbias_stride + ch];
+            s_scale[ch] = (float)(sc * s1);
+            s_shift[ch] = (float)(sh * s1 + (double)tbias[trow * tbias_stride + c + ch]);
+        } else {
+            s_scale[ch] = (float)((double)gamma[ch] * rstd);
+            s_shift[ch] = (float)((double)beta[ch] - m * (double)gamma[ch] * rstd);
+            if (TB) s_tb[ch] = tbias[trow * tbias_stride + ch];
+        }
     }
     __syncthreads();
     const float* xb = x + (long long)nb * vox * c;
@@ -94,7 +101,7 @@ gn_apply_f32_kernel(const float* __restrict__ x, float* __restrict__ y, const do
     auto one = [&](float v, int ch, float r) {
         v = v * s_scale[ch] + s_shift[ch];
         if (SILU_PRE) v = silu_acc(v);
-        if (TB) v += s_tb[ch];
+        if (ADD_TB) v += s_tb[ch];
         if (RES) v += r;
         if (SILU_POST) v = silu_acc(v);
         return v;
@@ -129,9 +136,28 @@ static gn_apply_f32_fn gn_apply_f32_pick(int idx) {
         return nullptr;
     } else {
         if (idx == I)
-            return gn_apply_f32_kernel<(I & 1) != 0, (I & 2) != 0, (I & 4) != 0, (I & 8) != 0, (I & 16) != 0>;
+            return gn_apply_f32_kernel<(I & 1) != 0, (I & 2) != 0, (I & 4) != 0, (I & 8) != 0, false, (I & 16) != 0>;
         return gn_apply_f32_pick<I + 1>(idx);
     }
+}
+
+static int gn_apply_f32_launch(const float* x, float* y, const double* sums, const float* gamma, const float* beta, int n, int c,
+                               int d, int h, int w, int d_stat, int groups, float eps, int silu_pre, const float* tbias,
+                               int tbias_stride, const int* step_ptr, const float* residual, int silu_post, int film,
+                               void* stream) {
+    const long long vox = (long long)d * h * w;
+    const bool v4 = (c % 4 == 0) && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)residual) & 15) == 0;
+    const long long items = v4 ? vox * (c / 4) : vox * c;
+    long long blocks = (items + 256 * 4 - 1) / (256 * 4);
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    const int idx = (silu_pre ? 1 : 0) | (tbias ? 2 : 0) | (residual ? 4 : 0) | (silu_post ? 8 : 0) | (v4 ? 16 : 0);
+    gn_apply_f32_fn fn = gn_apply_f32_pick<0>(idx);
+    if (film) fn = v4 ? gn_apply_f32_kernel<true, true, false, false, true, true> : gn_apply_f32_kernel<true, true, false, false, true, false>;
+    hipLaunchKernelGGL(fn, dim3((unsigned)blocks, n), dim3(256), (size_t)c * 3 * sizeof(float), (hipStream_t)stream, x, y, sums,
+                       gamma, beta, c, vox, (long long)d_stat * h * w, groups, eps, tbias, tbias_stride, step_ptr, n, residual);
+    CTSI_LAUNCH_CHECK();
+    return CTSI_OK;
 }
 
 extern "C" int ctsi_gn_apply_f32(const float* x, float* y, const double* sums, const float* gamma, const float* beta, int n,
@@ -141,18 +167,24 @@ extern "C" int ctsi_gn_apply_f32(const float* x, float* y, const double* sums, c
     CTSI_CHECK_ARG(n > 0 && c > 0 && c <= 4096 && d > 0 && h > 0 && w > 0, "ctsi_gn_apply_f32: bad sizes (c=%d)", c);
     CTSI_CHECK_ARG(groups > 0 && c % groups == 0, "ctsi_gn_apply_f32: c=%d not divisible by groups=%d", c, groups);
     CTSI_CHECK_ARG(d_stat >= d, "ctsi_gn_apply_f32: d_stat=%d < d=%d", d_stat, d);
-    const long long vox = (long long)d * h * w;
-    const bool v4 = (c % 4 == 0) && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)residual) & 15) == 0;
-    const long long items = v4 ? vox * (c / 4) : vox * c;
-    long long blocks = (items + 256 * 4 - 1) / (256 * 4);
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    const int idx = (silu_pre ? 1 : 0) | (tbias ? 2 : 0) | (residual ? 4 : 0) | (silu_post ? 8 : 0) | (v4 ? 16 : 0);
-    hipLaunchKernelGGL(gn_apply_f32_pick<0>(idx), dim3((unsigned)blocks, n), dim3(256), (size_t)c * 3 * sizeof(float),
-                       (hipStream_t)stream, x, y, sums, gamma, beta, c, vox, (long long)d_stat * h * w, groups, eps, tbias,
-                       tbias_stride, step_ptr, n, residual);
-    CTSI_LAUNCH_CHECK();
-    return CTSI_OK;
+    return gn_apply_f32_launch(x, y, sums, gamma, beta, n, c, d, h, w, d_stat, groups, eps, silu_pre, tbias, tbias_stride, step_ptr,
+                               residual, silu_post, 0, stream);
+}
+
+// The ResBlock's middle pass (silu_pre, a time row, no residual, no outer SiLU); film = 0 is ctsi_gn_apply_f32's own form.
+extern "C" int ctsi_gn_apply_mod_f32(const float* x, float* y, const double* sums, const float* gamma, const float* beta, int n,
+                                     int c, int d, int h, int w, int d_stat, int groups, float eps, int silu_pre,
+                                     const float* tbias, int tbias_stride, const int* step_ptr, const float* residual,
+                                     int silu_post, int film, void* stream) {
+    CTSI_CHECK_ARG(x && y && sums && gamma && beta, "ctsi_gn_apply_mod_f32: null argument");
+    CTSI_CHECK_ARG(n > 0 && c > 0 && c <= 4096 && d > 0 && h > 0 && w > 0, "ctsi_gn_apply_mod_f32: bad sizes (c=%d)", c);
+    CTSI_CHECK_ARG(groups > 0 && c % groups == 0, "ctsi_gn_apply_mod_f32: c=%d not divisible by groups=%d", c, groups);
+    CTSI_CHECK_ARG(d_stat >= d, "ctsi_gn_apply_mod_f32: d_stat=%d < d=%d", d_stat, d);
+    CTSI_CHECK_ARG(silu_pre && tbias && !residual && !silu_post,
+                   "ctsi_gn_apply_mod_f32: the ResBlock's middle pass only (silu_pre, a time row, no residual, no outer SiLU)");
+    CTSI_CHECK_ARG(tbias_stride >= (film ? 2 * c : c), "ctsi_gn_apply_mod_f32: tbias_stride=%d shorter than the time row", tbias_stride);
+    return gn_apply_f32_launch(x, y, sums, gamma, beta, n, c, d, h, w, d_stat, groups, eps, 1, tbias, tbias_stride, step_ptr,
+                               nullptr, 0, film, stream);
 }
 
 // ---- TemporalAttention, fast mode --------------------------------------------------------------------------------------

@@ -4,23 +4,14 @@
 // All tensors are bf16 NDHWC; every global access is a 16-byte (8-channel) vector per lane.
 // Statistics path: per-tile column sums (conv epilogue or gn_colsum_kernel) -> gn_finalize_kernel
 // (fp64 (sum, sumsq) per (sample, group)) -> gn_apply_kernel.
+// gn_apply_kernel also serves the ResBlock's middle pass with the ADM-style options (ctsi_gn_apply_mod); the
+// dropout-mask and Philox windows the tests read are at the end.  What the passes share with the fp32 forward (f32_ops.hip) and
+// the backward (norm_bwd.hip) is gn_frame.h.
 #include "ctsi_internal.h"
-#include <stdlib.h>
+#include "ctsi_philox.h"
+#include "gn_frame.h"
 
 #define GN_TILE_ROWS 512
-
-__device__ __forceinline__ void unpack8(const uint4 v, float* f) {
-    f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-    f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-    f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-    f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-    uint4 v;
-    v.x = pack_bf16x2(f[0], f[1]); v.y = pack_bf16x2(f[2], f[3]);
-    v.z = pack_bf16x2(f[4], f[5]); v.w = pack_bf16x2(f[6], f[7]);
-    return v;
-}
 
 // ---- column sums of a tensor no conv produced ------------------------------------------------
 // grid: (tiles_per_sample, n); block 256.  cpr = c/8 16-byte chunks per voxel.
@@ -45,7 +36,7 @@ gn_colsum_kernel(const bf16_t* __restrict__ x, float* __restrict__ colsum, int n
         for (long long v = v0 + rl; v < v1; v += rows_par) {
             const uint4 raw = *reinterpret_cast<const uint4*>(base + v * c);
             float f[8];
-            unpack8(raw, f);
+            gn_unpack8(raw, f);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 s1[k] += f[k];
@@ -253,37 +244,23 @@ extern "C" int ctsi_gn_finalize(const float* colsum, double* sums, int n, int c,
     return CTSI_OK;
 }
 
-// 16-byte accesses, optionally non-temporal (tensors far larger than the Infinity Cache: streamed once)
-typedef unsigned int gn_u4_t __attribute__((ext_vector_type(4)));
-template <bool NT>
-__device__ __forceinline__ uint4 gn_ld(const bf16_t* p) {
-    if (NT) {
-        const gn_u4_t v = __builtin_nontemporal_load(reinterpret_cast<const gn_u4_t*>(p));
-        return make_uint4(v.x, v.y, v.z, v.w);
-    }
-    return *reinterpret_cast<const uint4*>(p);
-}
-template <bool NT>
-__device__ __forceinline__ void gn_st(bf16_t* p, const uint4 v) {
-    if (NT) {
-        const gn_u4_t w = {v.x, v.y, v.z, v.w};
-        __builtin_nontemporal_store(w, reinterpret_cast<gn_u4_t*>(p));
-    } else {
-        *reinterpret_cast<uint4*>(p) = v;
-    }
-}
-
 // ---- apply --------------------------------------------------------------------------------------
-// grid: (blocks_per_sample, n); block 256.  The four options are template parameters: with run-time flags the compiler
-// if-converted both SiLU sites into unconditional code (2 exp + 2 rcp per element and a select chain: ~25 VALU instructions
-// per element, 2.3 TB/s each way -- VALU-bound, not HBM-bound).  CONSTQ: the grid stride is a multiple of the row's chunk
-// count, so a thread meets the same 8 channels every iteration and keeps their scale / shift / time bias in registers.
-template <bool SILU_PRE, bool TB, bool RES, bool SILU_POST, bool CONSTQ, bool NT>
+// grid: (blocks_per_sample, n); block 256 (gn_fwd_grid of gn_frame.h).  The options are template parameters: with run-time flags
+// the compiler if-converted both SiLU sites into unconditional code (2 exp + 2 rcp per element and a select chain: ~25 VALU
+// instructions per element, 2.3 TB/s each way -- VALU-bound, not HBM-bound).  CONSTQ: the grid stride is a multiple of the row's
+// chunk count, so a thread meets the same 8 channels every iteration and keeps their scale / shift / time bias in registers.
+// The ResBlock's middle pass with the ADM-style options is the form <SILU_PRE, TB, no RES, no SILU_POST> plus
+//   FILM  y = silu(gn(x) * (1 + s) + b) with a time row (s | b) of 2c values: the prologue only -- the per-(sample, channel)
+//         coefficients become sc * (1 + s) and sh * (1 + s) + b, and no time bias is added afterwards;
+//   DROP  y * keep * inv with the keep bits of ctsi_philox.h: one Philox call per 16-byte chunk, applied last, still in fp32.
+template <bool SILU_PRE, bool TB, bool RES, bool SILU_POST, bool FILM, bool DROP, bool CONSTQ, bool NT>
 __global__ void __launch_bounds__(256)
 gn_apply_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const double* __restrict__ sums,
                 const float* __restrict__ gamma, const float* __restrict__ beta, int c, long long vox,
                 long long vox_stat, int groups, float eps, const float* __restrict__ tbias, int tbias_stride,
-                const int* __restrict__ step_ptr, int n_total, const bf16_t* __restrict__ residual, long long per_block) {
+                const int* __restrict__ step_ptr, int n_total, const bf16_t* __restrict__ residual, long long per_block,
+                uint32_t thr, float inv_keep, const unsigned long long* __restrict__ seed_ptr, uint32_t layer_id) {
+    constexpr bool ADD_TB = TB && !FILM;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* s_scale = reinterpret_cast<float*>(smem_raw);
     float* s_shift = s_scale + c;
@@ -294,20 +271,26 @@ gn_apply_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const doub
     long long trow = nb;
     if (TB && step_ptr) trow += (long long)(*step_ptr) * n_total;
     for (int ch = tid; ch < c; ch += 256) {
-        const int g = ch / cpg;
-        const double m = sums[((long long)nb * groups + g) * 2 + 0] / cnt;
-        double var = sums[((long long)nb * groups + g) * 2 + 1] / cnt - m * m;
-        if (var < 0.0) var = 0.0;
-        const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+        const GnMeanRstd st = gn_mean_rstd(sums + ((long long)nb * groups + ch / cpg) * 2, cnt, eps);
+        const float rstd = (float)st.rstd;
         const float sc = gamma[ch] * rstd;
-        s_scale[ch] = sc;
-        s_shift[ch] = beta[ch] - (float)m * sc;
-        if (TB) s_tb[ch] = tbias[trow * tbias_stride + ch];
+        const float sh = beta[ch] - (float)st.mean * sc;
+        if (FILM) {
+            const float s1 = 1.0f + tbias[trow * tbias_stride + ch];
+            s_scale[ch] = sc * s1;
+            s_shift[ch] = sh * s1 + tbias[trow * tbias_stride + c + ch];
+        } else {
+            s_scale[ch] = sc;
+            s_shift[ch] = sh;
+            if (TB) s_tb[ch] = tbias[trow * tbias_stride + ch];
+        }
     }
     __syncthreads();
+    const unsigned long long seed = DROP ? *seed_ptr : 0ull;
     const int cpr = c >> 3;
     // per_block > 0: every block walks its own contiguous range of per_block chunks (stride 256); 0: grid-stride
     long long total = vox * cpr;
+    const unsigned long long chunk0 = (unsigned long long)nb * (unsigned long long)total;   // first chunk of this sample
     const bf16_t* xb = x + (long long)nb * vox * c;
     bf16_t* yb = y + (long long)nb * vox * c;
     const bf16_t* rb = RES ? residual + (long long)nb * vox * c : nullptr;
@@ -319,14 +302,9 @@ gn_apply_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const doub
     int q = (int)(e % cpr);   // 8-channel chunk index inside the voxel row
     float csc[8], csh[8], ctb[8];
     auto coef = [&](int qq, float* sc, float* sh, float* tb) {   // 16-byte LDS reads
-        *reinterpret_cast<float4*>(sc) = *reinterpret_cast<const float4*>(s_scale + qq * 8);
-        *reinterpret_cast<float4*>(sc + 4) = *reinterpret_cast<const float4*>(s_scale + qq * 8 + 4);
-        *reinterpret_cast<float4*>(sh) = *reinterpret_cast<const float4*>(s_shift + qq * 8);
-        *reinterpret_cast<float4*>(sh + 4) = *reinterpret_cast<const float4*>(s_shift + qq * 8 + 4);
-        if (TB) {
-            *reinterpret_cast<float4*>(tb) = *reinterpret_cast<const float4*>(s_tb + qq * 8);
-            *reinterpret_cast<float4*>(tb + 4) = *reinterpret_cast<const float4*>(s_tb + qq * 8 + 4);
-        }
+        gn_lds8(sc, s_scale, qq);
+        gn_lds8(sh, s_shift, qq);
+        if (ADD_TB) gn_lds8(tb, s_tb, qq);
     };
     if (CONSTQ) coef(q, csc, csh, ctb);
     // one dword = channels (2 j, 2 j + 1): the pair stays a 2-vector from the unpack to the single v_cvt_pk_bf16_f32
@@ -337,6 +315,8 @@ gn_apply_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const doub
         const float* sh = CONSTQ ? csh : lsh;
         const float* tb = CONSTQ ? ctb : ltb;
         const uint32_t xin[4] = {raw.x, raw.y, raw.z, raw.w}, rin[4] = {rraw.x, rraw.y, rraw.z, rraw.w};
+        uint32_t keep = 0xffu;
+        if (DROP) keep = ctsi_dropout_keep8(chunk0 + (unsigned long long)ee, layer_id, seed, thr);
         uint32_t o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -344,9 +324,13 @@ gn_apply_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const doub
             const f32x2_t s2 = {sc[2 * j], sc[2 * j + 1]}, h2 = {sh[2 * j], sh[2 * j + 1]};
             v = v * s2 + h2;
             if (SILU_PRE) v = silu2_f(v);
-            if (TB) v += f32x2_t{tb[2 * j], tb[2 * j + 1]};
+            if (ADD_TB) v += f32x2_t{tb[2 * j], tb[2 * j + 1]};
             if (RES) v += f32x2_t{__uint_as_float(rin[j] << 16), __uint_as_float(rin[j] & 0xffff0000u)};
             if (SILU_POST) v = silu2_f(v);
+            if (DROP) {
+                v.x = (keep >> (2 * j)) & 1u ? v.x * inv_keep : 0.0f;
+                v.y = (keep >> (2 * j + 1)) & 1u ? v.y * inv_keep : 0.0f;
+            }
             o[j] = pack_bf16x2_v(v);
         }
         gn_st<NT>(yb + ee * 8, make_uint4(o[0], o[1], o[2], o[3]));
@@ -373,15 +357,47 @@ gn_apply_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const doub
 }
 
 typedef void (*gn_apply_fn)(const bf16_t*, bf16_t*, const double*, const float*, const float*, int, long long, long long, int,
-                            float, const float*, int, const int*, int, const bf16_t*, long long);
+                            float, const float*, int, const int*, int, const bf16_t*, long long, uint32_t, float,
+                            const unsigned long long*, uint32_t);
+// idx: bit 0 SILU_PRE, 1 TB, 2 RES, 3 SILU_POST, 4 CONSTQ, 5 NT -- the 64 forms of ctsi_gn_apply
 template <int I>
 static gn_apply_fn gn_apply_pick(int idx) {
     if constexpr (I >= 64) {
         return nullptr;
     } else {
-        if (idx == I) return gn_apply_kernel<(I & 1) != 0, (I & 2) != 0, (I & 4) != 0, (I & 8) != 0, (I & 16) != 0, (I & 32) != 0>;
+        if (idx == I)
+            return gn_apply_kernel<(I & 1) != 0, (I & 2) != 0, (I & 4) != 0, (I & 8) != 0, false, false, (I & 16) != 0, (I & 32) != 0>;
         return gn_apply_pick<I + 1>(idx);
     }
+}
+// idx: bit 0 FILM, 1 DROP, 2 CONSTQ, 3 NT -- the middle pass; neither option: the instantiation ctsi_gn_apply(silu_pre, tbias) runs
+template <int I>
+static gn_apply_fn gn_apply_mod_pick(int idx) {
+    if constexpr (I >= 16) {
+        return nullptr;
+    } else {
+        if (idx == I) return gn_apply_kernel<true, true, false, false, (I & 1) != 0, (I & 2) != 0, (I & 4) != 0, (I & 8) != 0>;
+        return gn_apply_mod_pick<I + 1>(idx);
+    }
+}
+
+static int gn_apply_launch(const void* x, void* y, const double* sums, const float* gamma, const float* beta, int n, int c, int d,
+                           int h, int w, int d_stat, int groups, float eps, int silu_pre, const float* tbias, int tbias_stride,
+                           const int* step_ptr, const void* residual, int silu_post, const GnOptions& mod, void* stream) {
+    const long long vox = (long long)d * h * w;
+    const GnFwdGrid g = gn_fwd_grid(n, c, vox);
+    const size_t lds = (size_t)c * 3 * sizeof(float);
+    const gn_apply_fn fn =
+        mod.form()
+            ? gn_apply_mod_pick<0>(mod.form() | (g.constq ? 4 : 0) | (g.nt ? 8 : 0))
+            : gn_apply_pick<0>((silu_pre ? 1 : 0) | (tbias ? 2 : 0) | (residual ? 4 : 0) | (silu_post ? 8 : 0) |
+                               (g.constq ? 16 : 0) | (g.nt ? 32 : 0));
+    hipLaunchKernelGGL(fn, dim3((unsigned)g.blocks, n), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, sums,
+                       gamma, beta, c, vox, (long long)d_stat * h * w, groups, eps, tbias, tbias_stride, step_ptr, n,
+                       (const bf16_t*)residual, g.per_block, mod.thr, mod.inv_keep, mod.seed,
+                       mod.layer_id);
+    CTSI_LAUNCH_CHECK();
+    return CTSI_OK;
 }
 
 extern "C" int ctsi_gn_apply(const void* x, void* y, const double* sums, const float* gamma, const float* beta,
@@ -391,40 +407,68 @@ extern "C" int ctsi_gn_apply(const void* x, void* y, const double* sums, const f
     CTSI_CHECK_ARG(x && y && sums && gamma && beta, "ctsi_gn_apply: null argument");
     CTSI_CHECK_ARG(c % 8 == 0 && groups > 0 && c % groups == 0, "ctsi_gn_apply: bad c=%d groups=%d", c, groups);
     CTSI_CHECK_ARG(d_stat >= d, "ctsi_gn_apply: d_stat=%d < d=%d", d_stat, d);
-    const long long vox = (long long)d * h * w;
-    const long long total = vox * (c / 8);
-    long long blocks = (total + 256 * 8 - 1) / (256 * 8);
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    // a grid stride that is a multiple of the chunks per voxel row (c / 8) keeps every thread on one 8-channel chunk
-    const int cpr = c / 8;
-    int gq = cpr, g256 = 256;
-    while (g256) { const int t = gq % g256; gq = g256; g256 = t; }     // gq = gcd(cpr, 256)
-    const int need = cpr / gq;                                         // blocks must be a multiple of this
-    if (blocks >= need) blocks -= blocks % need;
-    bool constq = (blocks * 256) % cpr == 0;
-    // Contiguous ranges: every block takes ONE batch of 4 x 256 consecutive 16-byte chunks (16 KB) and the blocks are dispatched in
-    // address order, so the chip's working front moves linearly through the tensor.  Against 2048 grid-striding blocks (each
-    // thread's loads 8 MB apart) the decoder-size tensors go from 4.7-4.8 to 6.0-6.3 TB/s (3.2 GB at 128 channels x 48 x 512^2: 1345 ->
-    // 1069 us; with a residual 2044 -> 1554 us), the U-Net's 201 MB tensors from 6.5 to 6.7 TB/s.  Needs 256 % (c / 8) == 0 (a
-    // thread then stays on one 8-channel chunk); other channel counts keep the grid-stride form.  CTSI_GN_CONTIG=0 forces it.
-    long long per_block = 0;
-    {
-        static const char* cg = getenv("CTSI_GN_CONTIG");
-        if (!(cg && atoi(cg) == 0) && 256 % cpr == 0) {
-            per_block = 1024;
-            blocks = (total + per_block - 1) / per_block;
-            constq = true;
-        }
-    }
-    const size_t lds = (size_t)c * 3 * sizeof(float);
-    // tensors well beyond the 256 MB Infinity Cache (> 512 MB: measured threshold) are streamed with non-temporal accesses (CTSI_GN_NT=0 / 1 overrides)
-    static const char* nt_env = getenv("CTSI_GN_NT");
-    const bool nt = nt_env ? atoi(nt_env) != 0 : (long long)n * vox * c * 2 > (512ll << 20);
-    const int idx = (silu_pre ? 1 : 0) | (tbias ? 2 : 0) | (residual ? 4 : 0) | (silu_post ? 8 : 0) | (constq ? 16 : 0) | (nt ? 32 : 0);
-    hipLaunchKernelGGL(gn_apply_pick<0>(idx), dim3((unsigned)blocks, n), dim3(256), lds, (hipStream_t)stream,
-                       (const bf16_t*)x, (bf16_t*)y, sums, gamma, beta, c, vox, (long long)d_stat * h * w, groups, eps,
-                       tbias, tbias_stride, step_ptr, n, (const bf16_t*)residual, per_block);
+    return gn_apply_launch(x, y, sums, gamma, beta, n, c, d, h, w, d_stat, groups, eps, silu_pre, tbias, tbias_stride, step_ptr,
+                           residual, silu_post, GnOptions{}, stream);
+}
+
+extern "C" int ctsi_gn_apply_mod(const void* x, void* y, const double* sums, const float* gamma, const float* beta,
+                                 int n, int c, int d, int h, int w, int d_stat, int groups, float eps, int silu_pre,
+                                 const float* tbias, int tbias_stride, const int* step_ptr, const void* residual,
+                                 int silu_post, int film, int p_thr16, float inv_keep, const void* seed, int layer_id,
+                                 void* stream) {
+    CTSI_CHECK_ARG(x && y && sums && gamma && beta, "ctsi_gn_apply_mod: null argument");
+    CTSI_CHECK_ARG(c % 8 == 0 && c >= 8 && c <= 2048 && groups > 0 && c % groups == 0, "ctsi_gn_apply_mod: bad c=%d groups=%d", c, groups);
+    CTSI_CHECK_ARG(n > 0 && d > 0 && h > 0 && w > 0 && d_stat >= d, "ctsi_gn_apply_mod: bad sizes (d_stat=%d, d=%d)", d_stat, d);
+    CTSI_CHECK_ARG(silu_pre && tbias && !residual && !silu_post,
+                   "ctsi_gn_apply_mod: the ResBlock's middle pass only (silu_pre, a time row, no residual, no outer SiLU)");
+    CTSI_CHECK_ARG(tbias_stride >= (film ? 2 * c : c), "ctsi_gn_apply_mod: tbias_stride=%d shorter than the time row", tbias_stride);
+    CTSI_CHECK_ARG(p_thr16 >= 0 && p_thr16 < 65536, "ctsi_gn_apply_mod: p_thr16=%d outside [0, 65536)", p_thr16);
+    CTSI_CHECK_ARG(p_thr16 == 0 || seed, "ctsi_gn_apply_mod: dropout needs the seed buffer");
+    CTSI_CHECK_ARG(layer_id >= 0, "ctsi_gn_apply_mod: layer_id=%d", layer_id);
+    const GnOptions mod = {true, film ? 1 : 0, (uint32_t)p_thr16, inv_keep, (const unsigned long long*)seed, (uint32_t)layer_id};
+    return gn_apply_launch(x, y, sums, gamma, beta, n, c, d, h, w, d_stat, groups, eps, 1, tbias, tbias_stride, step_ptr, nullptr,
+                           0, mod, stream);
+}
+
+// ---- the dropout mask and the Philox function, for tests ------------------------------------------------------------------------
+// keep bytes (1 = kept) of the first `count` elements of a layer's logical NDHWC tensor
+__global__ void __launch_bounds__(256)
+dropout_mask_kernel(const unsigned long long* __restrict__ seed_ptr, uint32_t layer_id, uint32_t thr, long long count,
+                    unsigned char* __restrict__ out) {
+    const long long chunk = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (chunk * 8 >= count) return;
+    const uint32_t keep = ctsi_dropout_keep8((unsigned long long)chunk, layer_id, *seed_ptr, thr);
+    for (int j = 0; j < 8; ++j)
+        if (chunk * 8 + j < count) out[chunk * 8 + j] = (unsigned char)((keep >> j) & 1u);
+}
+
+extern "C" int ctsi_dropout_mask(const void* seed, int layer_id, int p_thr16, long long count, void* out_u8, void* stream) {
+    CTSI_CHECK_ARG(seed && out_u8, "ctsi_dropout_mask: null argument");
+    CTSI_CHECK_ARG(count > 0 && count <= (1ll << 40), "ctsi_dropout_mask: count=%lld", count);
+    CTSI_CHECK_ARG(p_thr16 >= 0 && p_thr16 < 65536 && layer_id >= 0, "ctsi_dropout_mask: p_thr16=%d layer_id=%d", p_thr16,
+                   layer_id);
+    const long long chunks = (count + 7) / 8;
+    hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned long long*)seed, (uint32_t)layer_id, (uint32_t)p_thr16, count, (unsigned char*)out_u8);
     CTSI_LAUNCH_CHECK();
+    return CTSI_OK;
+}
+
+extern "C" int ctsi_philox4x32_10_host(const uint32_t* ctr, const uint32_t* key, uint32_t* out) {
+    CTSI_CHECK_ARG(ctr && key && out, "ctsi_philox4x32_10_host: null argument");
+    ctsi_philox4x32_10(ctr, key, out);
+    return CTSI_OK;
+}
+
+// host twin of ctsi_dropout_mask (the same inline function), for machines without a GPU
+extern "C" int ctsi_dropout_mask_host(unsigned long long seed, int layer_id, int p_thr16, long long count, void* out_u8) {
+    CTSI_CHECK_ARG(out_u8 && count > 0, "ctsi_dropout_mask_host: bad argument");
+    CTSI_CHECK_ARG(p_thr16 >= 0 && p_thr16 < 65536 && layer_id >= 0, "ctsi_dropout_mask_host: p_thr16=%d layer_id=%d", p_thr16,
+                   layer_id);
+    unsigned char* out = (unsigned char*)out_u8;
+    for (long long chunk = 0; chunk * 8 < count; ++chunk) {
+        const uint32_t keep = ctsi_dropout_keep8((unsigned long long)chunk, (uint32_t)layer_id, seed, (uint32_t)p_thr16);
+        for (int j = 0; j < 8 && chunk * 8 + j < count; ++j) out[chunk * 8 + j] = (unsigned char)((keep >> j) & 1u);
+    }
     return CTSI_OK;
 }

@@ -1,4 +1,4 @@
-"""The ResBlock3D options of UNet3D(use_scale_shift_norm=, dropout=) on the engine (csrc/norm_mod.hip): the
+"""The ResBlock3D options of UNet3D(use_scale_shift_norm=, dropout=) on the engine (csrc/norm_act.hip, csrc/norm_bwd.hip): the
 launches that replace the default middle pass of a ResBlock -- the GroupNorm pass that produces conv2's input -- when a block
 asks for them, and the dropout state they read.  The default pass (ctsi_gn_apply / ctsi_gn_apply_f32 / ctsi_gn_bwd) is emitted
 by the engines themselves, as ever; `Program.gn_apply` and `TrainProgram.t_gn` come here only with `film` or `drop` set.
