@@ -758,6 +758,27 @@ int ctsi_graph_end_capture(void* stream, ctsi_graph** graph);
 int ctsi_graph_launch(ctsi_graph* graph, void* stream);
 void ctsi_graph_destroy(ctsi_graph* graph);
 
+/* Latent-space window fusion (csrc/window_fuse.hip): the overlapping windows of a stitched volume share
+ * one latent; per U-Net evaluation the network runs on all windows as one batch and these two passes move the data.
+ * Rows: the full tensors hold `batch` samples per guidance half; window row (g nw + k) batch + b is window k of sample b in
+ * half g, k = (kd nwh + kh) nww + kw over the product grid of per-axis window starts.  All tensors are NDHWC.
+ * ctsi_window_gather / _f32: dst row (g nw + k) batch + b <- the (td, lh, lw) window of src row b at starts[3k .. 3k+2]
+ *   (int32 device table of latent starts); channels [0, L) of c_total per voxel on either side, bf16 / fp32.  `halves` (1 | 2)
+ *   destination halves read the same `batch` source rows.  A pure copy, bit exact; the widest of 16- / 8- / 4- / 2-byte
+ *   accesses that divides L and both pitches and matches the pointers.  Every start must lie in [0, full - window]: the kernel does not check.
+ * ctsi_window_blend: full[g batch + b][v] = sum over (kd, kh, kw) of wd wh ww win[(g nw + k) batch + b][v - s_k], fp32, C
+ *   channels (a multiple of 4), in that fixed order with one fma per term: no accumulator tensor, no atomics.  tab_i: per axis
+ *   (d, h, w in turn; P = full size, K = kd | kh | kw = the largest number of windows over one position) int32 [P] counts,
+ *   [P][K] window indices along the axis, [P][K] positions inside that window; tab_w: per axis fp32 [P][K] weights, normalised
+ *   per axis to sum to 1 at every position (window_fuse.axis_table, which validates the windows; the kernel trusts the table).
+ * Null pointers / bad sizes return CTSI_ERR_INVALID before any launch.  Capture-safe: no allocation, no synchronisation. */
+int ctsi_window_gather(const void* src_bf16, void* dst_bf16, const int* starts, int batch, int halves, int nw, int D, int H,
+                       int W, int td, int lh, int lw, int L, int src_c_total, int dst_c_total, void* stream);
+int ctsi_window_gather_f32(const float* src, float* dst, const int* starts, int batch, int halves, int nw, int D, int H, int W,
+                           int td, int lh, int lw, int L, int src_c_total, int dst_c_total, void* stream);
+int ctsi_window_blend(const float* win, float* full, const int* tab_i, const float* tab_w, int batch, int halves, int nwd,
+                      int nwh, int nww, int D, int H, int W, int td, int lh, int lw, int C, int kd, int kh, int kw, void* stream);
+
 /* timing helpers used by bench.py (HIP events on the engine's own stream) ----------------- */
 typedef struct ctsi_event ctsi_event;
 int ctsi_event_create(ctsi_event** ev);

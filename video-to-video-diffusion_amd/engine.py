@@ -1408,6 +1408,16 @@ class UNetProgram(Program):
         element, fp32 entry).  Here the z half of the bf16 [z | cond] tensor."""
         return self.xin.ip, 2 * self.L, 2, False
 
+    def _zin_act(self) -> Act:
+        """The tensor of _sampler_zin() as an Act (what the update's audit record names)."""
+        return self.xin
+
+    def _add_input_fanout(self):
+        """What carries the input the update wrote to every network row that reads it: ctsi_cfg_mirror in a guided program,
+        nothing otherwise (window_fuse._WindowFused: the cut into the windows)."""
+        if self.guided:
+            self._add_guidance_mirror()
+
     def _uncond_zin(self) -> C.c_void_p:
         """Guided programs: where rows [n, 2n) of the slice of _sampler_zin start."""
         _, c_total, nbytes, _ = self._sampler_zin()
@@ -1508,11 +1518,10 @@ class UNetProgram(Program):
         else:
             self._emit(run_step, "sampler.step", nbytes=step_bytes,
                        audit=dict(kind="sampler_step", sampler=kind, z=self.z, eps=self.eps, hist=self.hist,
-                                  noise=self.noise if with_noise else None, zin=self.xin, coef=self.coef,
+                                  noise=self.noise if with_noise else None, zin=self._zin_act(), coef=self.coef,
                                   step_ptr=self.step_ptr, nonfinite=self.nonfinite if entry.nonfinite else None, n=n, L=L,
                                   **(dict(vraw=self.vraw) if entry.vraw else {})))
-        if self.guided:
-            self._add_guidance_mirror()
+        self._add_input_fanout()
         self._emit(run_adv, "sampler.advance", audit=dict(kind="sampler_advance", step_ptr=self.step_ptr))
         self.sampler_kind = (kind, with_noise)
         self.update_form = update_form

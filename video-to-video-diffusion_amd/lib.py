@@ -223,6 +223,9 @@ SIGNATURES = {
     "ctsi_ddpm_lv_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp], True),
     "ctsi_ddpm_lv_step_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp], True),
     "ctsi_ddpm_posterior_lv": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _vp], True),
+    "ctsi_window_gather": (_i, [_vp, _vp, _vp] + [_i] * 12 + [_vp], True),
+    "ctsi_window_gather_f32": (_i, [_vp, _vp, _vp] + [_i] * 12 + [_vp], True),
+    "ctsi_window_blend": (_i, [_vp, _vp, _vp, _vp] + [_i] * 15 + [_vp], True),
     "ctsi_hybrid_loss_workspace_doubles": (_sz, [_i], False),
     "ctsi_hybrid_loss_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp], True),
     "ctsi_hybrid_loss_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp],

@@ -28,6 +28,7 @@ from .engine_f32 import check_precision
 from .engine_x3 import ACT_BYTES, unet_program
 from .learned_sigma import check_learn_sigma_unsharded, check_pairing, check_var_type, respaced_ddpm_rows
 from .lib import CtsiError
+from .window_fuse import check_fusion, fused_program, stitch_geometry
 from .x0_form import check_eps_form_timesteps, check_update_form, x0_coef_rows, x0_step_launcher
 
 logger = logging.getLogger(__name__)
@@ -577,6 +578,46 @@ def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, 
         return res
 
 
+def _run_step_program(prog: UNetProgram, plan: StepPlan, ctx, shape, conditioning, z0, nb: int, *, noise_fn, progress,
+                      guidance: Optional[Tuple[float, float]], trajectory, eps_trajectory):
+    """The reverse loop on a step program (inside ctx.scope()): run_sampler's on the latent `shape`, run_sampler_fused's on the
+    full latent's with the windows' conditioning.  `nb`: network rows of one evaluation (timestep rows per evaluation);
+    `shape`: the state's, which the noise draws and both trajectories have.  Returns the final state, fp32 NCDHW."""
+    prog.load_latents(z0, conditioning)
+    prog.nonfinite.zero_()
+    nf_tail = prog.nonfinite.data_ptr() + prog.max_rows * 24
+    # sampler.py:268-275: checkpoint 1 sanitises the initial noise (identity on finite values), checkpoint 2 only
+    # reports on the conditioning; both are counted on device and logged after the loop
+    ctx.lib.count_nonfinite_f32(_ptr(prog.z), prog.z.numel(), 1, C.c_void_p(nf_tail), ctx.sptr)
+    cnd = conditioning.detach().to(ctx.device, torch.float32).contiguous()
+    ctx.lib.count_nonfinite_f32(_ptr(cnd), cnd.numel(), 0, C.c_void_p(nf_tail + 24), ctx.sptr)
+    cnd.record_stream(ctx.stream)
+    prog.set_schedule([t for t in plan.t for _ in range(nb)], plan.coef.to(ctx.device), plan.pred)
+    if guidance is not None:
+        prog.set_guidance(*guidance)     # a device write: the same captured graph serves every scale
+    if prog.graph is None:
+        # one eager warm-up step is not needed: capture records launches without executing them
+        prog.capture()
+        prog.step_ptr.zero_()
+
+    def load_noise(i):
+        if noise_fn is not None:
+            prog.noise.copy_(noise_fn(i, tuple(shape)).to(ctx.device, torch.float32))
+        else:
+            prog.noise.normal_()
+
+    for closes in _replay(plan, _progress(plan, progress), load_noise, prog.launch):
+        if trajectory is not None and closes:
+            trajectory.append(prog.z_ncdhw())
+        if eps_trajectory is not None:
+            eps_trajectory.append(prog.eps_ncdhw())
+    out = prog.z_ncdhw()
+    if plan.logs_nonfinite:     # (one host read: the loop itself never synchronises)
+        _log_nonfinite(prog.nonfinite, len(plan.t), prog.max_rows)
+    check_device_errors(ctx)
+    return out
+
+
 def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_desc: Sequence[int],
                 progress: bool, eta: float = 0.0, noise_fn=None, z_init: Optional[torch.Tensor] = None,
                 trajectory: Optional[list] = None, order: int = 2, eps_trajectory: Optional[list] = None,
@@ -663,39 +704,77 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
             return prog
 
         prog: UNetProgram = cached_program(unet, key, build)
-        prog.load_latents(z0, conditioning)
-        prog.nonfinite.zero_()
-        nf_tail = prog.nonfinite.data_ptr() + prog.max_rows * 24
-        # sampler.py:268-275: checkpoint 1 sanitises the initial noise (identity on finite values), checkpoint 2 only
-        # reports on the conditioning; both are counted on device and logged after the loop
-        ctx.lib.count_nonfinite_f32(_ptr(prog.z), prog.z.numel(), 1, C.c_void_p(nf_tail), ctx.sptr)
-        cnd = conditioning.detach().to(ctx.device, torch.float32).contiguous()
-        ctx.lib.count_nonfinite_f32(_ptr(cnd), cnd.numel(), 0, C.c_void_p(nf_tail + 24), ctx.sptr)
-        cnd.record_stream(ctx.stream)
-        prog.set_schedule([t for t in plan.t for _ in range(nb)], plan.coef.to(ctx.device), plan.pred)
-        if guided:
-            prog.set_guidance(s_cfg, phi_cfg)     # a device write: the same captured graph serves every scale
-        if prog.graph is None:
-            # one eager warm-up step is not needed: capture records launches without executing them
-            prog.capture()
-            prog.step_ptr.zero_()
+        return _run_step_program(prog, plan, ctx, shape, conditioning, z0, nb, noise_fn=noise_fn, progress=progress,
+                                 guidance=(s_cfg, phi_cfg) if guided else None, trajectory=trajectory,
+                                 eps_trajectory=eps_trajectory)
 
-        def load_noise(i):
-            if noise_fn is not None:
-                prog.noise.copy_(noise_fn(i, tuple(shape)).to(ctx.device, torch.float32))
-            else:
-                prog.noise.normal_()
 
-        for closes in _replay(plan, _progress(plan, progress), load_noise, prog.launch):
-            if trajectory is not None and closes:
-                trajectory.append(prog.z_ncdhw())
-            if eps_trajectory is not None:
-                eps_trajectory.append(prog.eps_ncdhw())
-        out = prog.z_ncdhw()
-        if plan.logs_nonfinite:     # (one host read: the loop itself never synchronises)
-            _log_nonfinite(prog.nonfinite, len(plan.t), prog.max_rows)
-        check_device_errors(ctx)
-        return out
+def check_fusable(diffusion, model, kind: str = "ddim", dp_group=None):
+    """What latent window fusion refuses, before anything is drawn or built (CtsiError, each naming the alternative)."""
+    if dp_group is not None and dp_group is not False:
+        raise CtsiError("fusion='latent' does not support window data parallelism (dp_group=): every window is a row of one "
+                        "network batch on one device; use fusion='pixel' to split the windows over ranks")
+    if not _is_engine_unet(model):
+        raise CtsiError("fusion='latent' needs the engine's UNet3D: the blend and the cut run inside its captured step; a "
+                        "generic model(z, t, c) callable can be stitched with fusion='pixel'")
+    comm = getattr(model, "depth_shard_comm", None)
+    if comm is not None and getattr(comm, "world", 1) > 1:
+        raise CtsiError("fusion='latent' does not support depth sharding (unet.depth_shard_comm): drop the communicator, or "
+                        "use fusion='pixel'")
+    learned = check_var_type(getattr(diffusion, "var_type", "fixed_small")) == "learned_range"
+    if getattr(model, "learn_sigma", False) or learned or kind == "ddpm_lv":
+        raise CtsiError("fusion='latent' does not support a learn_sigma model, var_type='learned_range' or the strided ancestral "
+                        "sampler ('ddpm_spaced'): use the full-length DDPMSampler on a fixed_small model, DDIM, DPM-Solver++ "
+                        "or Heun, or fusion='pixel'")
+
+
+def run_sampler_fused(diffusion, unet, full_shape, cond_windows, win_shape, starts, device, *, kind: str, t_desc: Sequence,
+                      eta: float = 0.0, noise_fn=None, order: int = 2, heun: Optional[HeunRows] = None,
+                      guidance_scale: float = 1.0, guidance_rescale: float = 0.0, trajectory: Optional[list] = None,
+                      eps_trajectory: Optional[list] = None, progress: bool = False):
+    """run_sampler with latent window fusion: ONE latent of `full_shape` (B, L, D, H, W) for the whole
+    volume; every U-Net evaluation runs on all windows -- `starts`: their latent (d, h, w) starts, a product grid in that
+    order; `win_shape` (td, lh, lw); `cond_windows` (nw B, L, td, lh, lw): their conditioning latents, window-major, never
+    blended -- as one batch (2 nw B rows when guided), the raw outputs are blended into a full-size prediction
+    (ctsi_window_blend) and everything run_sampler puts behind the network -- ctsi_pred_to_eps, the guidance (its rescale
+    statistics per full volume), the kind's update or ctsi_x0_step, the nonfinite counters -- runs unchanged at the full
+    shape; ctsi_window_gather then cuts the new network input back into the windows.  One captured hipGraph per step.
+    Noise: one draw of the full shape, noise_fn(-1, full_shape) / torch.randn for the start and noise_fn(i, full_shape) per
+    noisy step.  Kinds 'ddim', 'ddpm', 'dpmpp', 'heun'.  `trajectory` / `eps_trajectory` receive full-shape fp32 NCDHW tensors,
+    as in run_sampler.  Returns the full latent."""
+    s_cfg, phi_cfg = check_guidance(guidance_scale, guidance_rescale)
+    guided = s_cfg != 1.0
+    check_fusable(diffusion, unet, kind)
+    plan = _step_plan(diffusion, kind, t_desc, eta, order, heun)
+    check_attention_mode(unet.attention_mode)
+    check_pairing(diffusion, unet)
+    precision = check_precision(getattr(unet, "inference_precision", "bf16"))
+    ctx = Ctx.get(torch.device(device))
+    n, L, D, H, W = [int(v) for v in full_shape]
+    win = tuple(int(v) for v in win_shape)
+    starts = [tuple(int(v) for v in s) for s in starts]
+    nb_net = len(starts) * n * (2 if guided else 1)          # rows of one U-Net evaluation
+    max_rows = (diffusion.timesteps + 1) * nb_net
+    z0 = noise_fn(-1, tuple(full_shape)).to(ctx.device) if noise_fn is not None else torch.randn(tuple(full_shape),
+                                                                                                  device=ctx.device)
+    z0 = plan.initial_state(z0, noise_fn, full_shape, ctx.device)
+    with ctx.scope():
+        from .engine import cached_program
+        key = ("sampler-fused", ctx.device.index, n, D, H, W, win, tuple(starts), max_rows, guided,
+               phi_cfg > 0.0) + plan.key + (unet.attention_mode, precision) + plan.key_order
+
+        def build():
+            kw = dict(guided=True, rescale=phi_cfg > 0.0) if guided else {}
+            if plan.pred is not None or plan.x0:
+                kw["prediction"] = "v_prediction"
+            prog = fused_program(precision)(ctx, unet, n, (D, H, W), win, starts, max_rows, unet.attention_mode, **kw)
+            prog.add_sampler_step(plan.kind, plan.with_noise, **(dict(update_form="x0") if plan.x0 else {}))
+            return prog
+
+        prog = cached_program(unet, key, build)
+        return _run_step_program(prog, plan, ctx, full_shape, cond_windows, z0, nb_net, noise_fn=noise_fn, progress=progress,
+                                 guidance=(s_cfg, phi_cfg) if guided else None, trajectory=trajectory,
+                                 eps_trajectory=eps_trajectory)
 
 
 class _Sampler:
@@ -719,11 +798,19 @@ class _Sampler:
         return gaussian_weight(d, h, w)
 
     def _stitch(self, v_thick_full, vae, num_inference_steps, patch_size, target_patch_size, stride, device, progress,
-                window_batch, dp_group, batchable, **kw):
+                window_batch, dp_group, batchable, fusion="pixel", decode=None, **kw):
         """sample_with_stitching on `num_inference_steps` steps (`kw`: more sample() arguments).  Windows are batched
         (up to `window_batch`; None / 0: as many as the device memory holds, see _stitched) only when `batchable`, i.e.
-        when the sampler draws no noise after the initial latent."""
-        s_cfg, _ = check_guidance(kw.get("guidance_scale", 1.0), kw.get("guidance_rescale", 0.0))
+        when the sampler draws no noise after the initial latent.
+        `fusion` 'latent' (`decode` 'full' | 'windows'): _stitched_fused on the run `_fused_plan` describes; there
+        `window_batch` batches the window decode only."""
+        fusion, decode = check_fusion(fusion, decode)
+        s_cfg, phi_cfg = check_guidance(kw.get("guidance_scale", 1.0), kw.get("guidance_rescale", 0.0))
+        if fusion == "latent":
+            plan_kw = {k: v for k, v in kw.items() if k not in ("guidance_scale", "guidance_rescale")}
+            return _stitched_fused(self, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress,
+                                   self._fused_plan(num_inference_steps, **plan_kw), decode, window_batch, dp_group,
+                                   (s_cfg, phi_cfg))
 
         def sample(shp, cond, z_init=None):
             return self.sample(shp, cond, num_inference_steps, device, progress=False, z_init=z_init, **kw)
@@ -750,6 +837,10 @@ class DDPMSampler(_Sampler):
         t_desc = list(reversed(range(T))) if full else [int(t) for t in self._get_timesteps(int(num_inference_steps))]
         return ("ddpm" if full and clip_denoised and not learned else "ddpm_lv"), t_desc
 
+    def _fused_plan(self, num_inference_steps=None, clip_denoised=True) -> dict:
+        kind, chain = self.chain(num_inference_steps, clip_denoised)
+        return dict(kind=kind, t_desc=chain)
+
     def coef_rows(self, num_inference_steps=None, clip_denoised=True) -> torch.Tensor:
         """The update's coefficient rows for such a run (what the step program reads)."""
         kind, t_desc = self.chain(num_inference_steps, clip_denoised)
@@ -774,8 +865,15 @@ class DDPMSampler(_Sampler):
     def sample_with_stitching(self, v_thick_full, vae, patch_size=(8, 192, 192),
                               target_patch_size=(48, 192, 192), stride=(4, 96, 96), device='cuda',
                               progress=True, dp_group=None, guidance_scale=1.0, guidance_rescale=0.0,
-                              num_inference_steps=None, clip_denoised=True):
-        check_guidance(guidance_scale, guidance_rescale)
+                              num_inference_steps=None, clip_denoised=True, fusion='pixel', decode=None):
+        """`fusion`, `decode`: as in DDIMSampler.sample_with_stitching; fusion='latent' runs the full-length chain of a
+        fixed_small model only (the strided / learned-variance step 'ddpm_lv' is refused)."""
+        fusion, decode = check_fusion(fusion, decode)
+        s_cfg, phi_cfg = check_guidance(guidance_scale, guidance_rescale)
+        if fusion == "latent":
+            return _stitched_fused(self, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress,
+                                   self._fused_plan(num_inference_steps, clip_denoised=clip_denoised), decode, 0, dp_group,
+                                   (s_cfg, phi_cfg))
         kw = {} if num_inference_steps is None and clip_denoised else dict(num_inference_steps=num_inference_steps,
                                                                           clip_denoised=clip_denoised)
         return _stitched(self, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress,
@@ -799,7 +897,7 @@ class DDIMSampler(_Sampler):
     def sample_with_stitching(self, v_thick_full, vae, num_inference_steps=20, patch_size=(8, 192, 192),
                               target_patch_size=(48, 192, 192), stride=(4, 96, 96), device='cuda', eta=0.0,
                               progress=True, window_batch=None, dp_group=None, guidance_scale=1.0,
-                              guidance_rescale=0.0):
+                              guidance_rescale=0.0, fusion='pixel', decode=None):
         """`dp_group` (additive kwarg, default None = every window on this process, as in the reference): a
         torch.distributed process group (or True for the default group) over which the windows are split; every rank
         of the group must make the call with the SAME volume.
@@ -809,10 +907,20 @@ class DDIMSampler(_Sampler):
         memory holds (13 windows of 48 x 192 x 192 on a 288 GB part); 1: one by one, like the reference.  The initial noise of every window is still drawn
         with its own `torch.randn` call in window order, exactly as the reference's one-by-one loop draws it.
         `guidance_scale`, `guidance_rescale` (additive kwargs): classifier-free guidance of every window (run_sampler); a
-        guided window counts as two in the automatic `window_batch`."""
+        guided window counts as two in the automatic `window_batch`.
+        `fusion` (additive kwarg): 'pixel' (default) is the path described above, every window an independent sample whose
+        decoded pixels are blended.  'latent'  keeps ONE latent for the whole volume: every U-Net evaluation
+        runs on all windows as one batch and their outputs are blended in latent space before the sampler update, so the
+        windows share one trajectory and the result is one coherent sample; noise is drawn once at the full latent's shape.
+        `decode` (with fusion='latent' only): 'full' (default) decodes the fused latent in one piece; 'windows' decodes its
+        windows in batches of `window_batch` and blends the pixels, for a VAE that should only see training-size inputs.
+        fusion='latent' refuses (CtsiError) dp_group, depth sharding, a learn_sigma model and a generic model callable."""
         return self._stitch(v_thick_full, vae, num_inference_steps, patch_size, target_patch_size, stride, device,
-                            progress, window_batch, dp_group, float(eta) == 0.0, eta=eta,
+                            progress, window_batch, dp_group, float(eta) == 0.0, fusion, decode, eta=eta,
                             guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
+
+    def _fused_plan(self, num_inference_steps, eta=0.0) -> dict:
+        return dict(kind="ddim", t_desc=[int(t) for t in self._get_timesteps(num_inference_steps)], eta=float(eta))
 
 
 class DPMSolverSampler(_Sampler):
@@ -838,12 +946,16 @@ class DPMSolverSampler(_Sampler):
     @torch.no_grad()
     def sample_with_stitching(self, v_thick_full, vae, num_inference_steps=20, patch_size=(8, 192, 192),
                               target_patch_size=(48, 192, 192), stride=(4, 96, 96), device='cuda', progress=True,
-                              window_batch=None, dp_group=None, guidance_scale=1.0, guidance_rescale=0.0):
-        """DDIMSampler.sample_with_stitching without `eta`: the same windows, blend, `window_batch`, `dp_group` and
-        guidance behaviour (the solver is deterministic, so windows are always batchable)."""
+                              window_batch=None, dp_group=None, guidance_scale=1.0, guidance_rescale=0.0,
+                              fusion='pixel', decode=None):
+        """DDIMSampler.sample_with_stitching without `eta`: the same windows, blend, `window_batch`, `dp_group`, guidance,
+        `fusion` and `decode` behaviour (the solver is deterministic, so windows are always batchable)."""
         return self._stitch(v_thick_full, vae, num_inference_steps, patch_size, target_patch_size, stride, device,
-                            progress, window_batch, dp_group, True, guidance_scale=guidance_scale,
+                            progress, window_batch, dp_group, True, fusion, decode, guidance_scale=guidance_scale,
                             guidance_rescale=guidance_rescale)
+
+    def _fused_plan(self, num_inference_steps) -> dict:
+        return dict(kind="dpmpp", t_desc=[int(t) for t in self._get_timesteps(num_inference_steps)], order=self.order)
 
 
 class HeunSampler(_Sampler):
@@ -898,12 +1010,18 @@ class HeunSampler(_Sampler):
     @torch.no_grad()
     def sample_with_stitching(self, v_thick_full, vae, num_inference_steps=20, patch_size=(8, 192, 192),
                               target_patch_size=(48, 192, 192), stride=(4, 96, 96), device='cuda', progress=True,
-                              window_batch=None, dp_group=None, guidance_scale=1.0, guidance_rescale=0.0):
+                              window_batch=None, dp_group=None, guidance_scale=1.0, guidance_rescale=0.0,
+                              fusion='pixel', decode=None):
         """DDIMSampler.sample_with_stitching without `eta`: windows are batched when s_churn == 0 and run one by one
-        otherwise (each window then draws its own churn noise, as stochastic DDIM does)."""
+        otherwise (each window then draws its own churn noise, as stochastic DDIM does).  `fusion`, `decode`: as there (the
+        churn noise of a fused run is one draw of the full latent's shape per churning step)."""
         return self._stitch(v_thick_full, vae, num_inference_steps, patch_size, target_patch_size, stride, device,
-                            progress, window_batch, dp_group, self.s_churn == 0.0, guidance_scale=guidance_scale,
-                            guidance_rescale=guidance_rescale)
+                            progress, window_batch, dp_group, self.s_churn == 0.0, fusion, decode,
+                            guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
+
+    def _fused_plan(self, num_inference_steps) -> dict:
+        rows = self.coef_rows(num_inference_steps)
+        return dict(kind="heun", t_desc=list(rows.t), order=self.order, heun=rows)
 
 
 # generate() / generate_batch() sampler names -> how each samples a latent: (diffusion, model, shape, conditioning,
@@ -949,6 +1067,25 @@ def _window_partition(windows, dp_group, sampler):
     return [windows[i] for i in shard_units(len(windows), rank, world)], world, group
 
 
+def _auto_window_batch(ctx, vae, b, td, th, tw, nwin, guided=False) -> int:
+    """sample_with_stitching's window batch when the caller names none."""
+    # as many windows per batch as a fifth of the DEVICE memory holds: the VAE decoder is the largest program, ~2.5 KB of
+    # activations per output voxel (30 GB for a 48 x 512 x 512 volume, 4.4 GB per 48 x 192 x 192 window: 13 windows on a
+    # 288 GB part).  Measured on 25 windows: 13 per batch 1.69 s, all 25 at once 1.72 s, 5 per batch 1.98 s -- past a dozen
+    # windows the levels are full and more only costs memory.  The TOTAL memory (not the free memory of the moment) keeps
+    # the batch shape, and with it the cached programs, the same from call to call.
+    try:
+        total = torch.cuda.get_device_properties(ctx.device).total_memory
+    except Exception:
+        total = 64 << 30
+    per_window = 2500.0 * b * td * th * tw
+    # fp32 activations (the fp32 and bf16x3 modes): twice the bytes per voxel
+    per_window *= ACT_BYTES.get(getattr(vae, "inference_precision", "bf16"), 2) / 2.0
+    if guided:
+        per_window *= 2.0         # a guided window is two rows of the U-Net's batch
+    return max(1, min(nwin, int(0.2 * total / per_window)))
+
+
 def _stitched(sampler, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress, sample_fn,
               batched_fn=None, window_batch=1, dp_group=None, guided=False):
     """Sliding-window inference (sampler.py:63-172, 338-453): per window encode -> sample -> decode on the
@@ -991,21 +1128,7 @@ def _stitched(sampler, v_thick_full, vae, patch_size, target_patch_size, stride,
     if batched_fn is not None:
         group = int(window_batch)
         if group <= 0:
-            # as many windows per batch as a fifth of the DEVICE memory holds: the VAE decoder is the largest program, ~2.5 KB of
-            # activations per output voxel (30 GB for a 48 x 512 x 512 volume, 4.4 GB per 48 x 192 x 192 window: 13 windows on a
-            # 288 GB part).  Measured on 25 windows: 13 per batch 1.69 s, all 25 at once 1.72 s, 5 per batch 1.98 s -- past a dozen
-            # windows the levels are full and more only costs memory.  The TOTAL memory (not the free memory of the moment) keeps
-            # the batch shape, and with it the cached programs, the same from call to call.
-            try:
-                total = torch.cuda.get_device_properties(ctx.device).total_memory
-            except Exception:
-                total = 64 << 30
-            per_window = 2500.0 * b * td * th * tw
-            # fp32 activations (the fp32 and bf16x3 modes): twice the bytes per voxel
-            per_window *= ACT_BYTES.get(getattr(vae, "inference_precision", "bf16"), 2) / 2.0
-            if guided:
-                per_window *= 2.0         # a guided window is two rows of the U-Net's batch
-            group = max(1, min(len(mine), int(0.2 * total / per_window)))
+            group = _auto_window_batch(ctx, vae, b, td, th, tw, len(mine), guided)
     ngroups = max(1, -(-len(mine) // group))            # balanced groups: 25 windows, window_batch 8 -> 7 + 6 + 6 + 6
     bounds = [round(i * len(mine) / ngroups) for i in range(ngroups + 1)]
     for gi in range(ngroups):
@@ -1037,6 +1160,66 @@ def _stitched(sampler, v_thick_full, vae, patch_size, target_patch_size, stride,
         import torch.distributed as dist
         dist.all_reduce(acc, group=pg)
         dist.all_reduce(wsum, group=pg)
+    with ctx.scope():
+        lib.blend_normalize(_ptr(acc), _ptr(wsum), acc.numel(), sptr)
+    return acc
+
+
+def _stitched_fused(sampler, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress, plan_args, decode,
+                    window_batch=0, dp_group=None, guidance=(1.0, 0.0)):
+    """sample_with_stitching(fusion='latent'): the windows of _stitched, fused in latent space.  Every thick
+    window is encoded on its own, in window batches, and depth-upsampled exactly as _stitched does it; run_sampler_fused then
+    samples ONE latent of the whole target volume with `plan_args` (the sampler's kind, timesteps and settings).
+    `decode` 'full': one vae.decode of that latent; 'windows': its windows are decoded in batches of `window_batch` (None / 0:
+    automatic, as in _stitched) and the pixels blended with ctsi_blend_accumulate / ctsi_blend_normalize, for VAEs that
+    should only ever see training-size inputs.  All windows are one network batch: there is no chunking, and a volume whose
+    window batch does not fit raises torch's out-of-memory error."""
+    check_fusable(sampler.diffusion, sampler.model, plan_args["kind"], dp_group)
+    window_batch = int(window_batch or 0)
+    if decode == "full" and window_batch != 0:
+        raise CtsiError(f"window_batch={window_batch} with decode='full': the fused latent is decoded in one piece and all "
+                        "windows are one network batch; drop window_batch, or pass decode='windows' to decode window by window")
+    b, c, d_thick, hf, wf = v_thick_full.shape
+    pd, ph, pw = patch_size
+    td, th, tw = target_patch_size
+    if (th, tw) != (ph, pw):
+        raise CtsiError(f"sample_with_stitching: target patch (h, w)=({th},{tw}) must equal the thick patch "
+                        f"(h, w)=({ph},{pw}); only depth is interpolated")
+    geo = stitch_geometry(vae, v_thick_full.shape, patch_size, target_patch_size, stride)
+    ctx = Ctx.get(torch.device(device))
+    nwin = len(geo.pixel_windows)
+    auto = _auto_window_batch(ctx, vae, b, td, th, tw, nwin)
+    conds = []
+    for lo in range(0, nwin, auto):
+        wins = geo.pixel_windows[lo:lo + auto]
+        patch = torch.cat([v_thick_full[:, :, ds:ds + pd, hs:hs + ph, ws:ws + pw] for (ds, hs, ws) in wins], dim=0)
+        z_cond = vae.encode(patch.to(ctx.device).contiguous())
+        if td != pd:
+            with ctx.scope():
+                z_cond = trilinear_depth(ctx, z_cond, td)
+        conds.append(z_cond)
+    cond = conds[0] if len(conds) == 1 else torch.cat(conds, dim=0)
+    L = int(cond.shape[1])
+    z = run_sampler_fused(sampler.diffusion, sampler.model, (b, L) + geo.full, cond, geo.win, geo.starts, ctx.device,
+                          guidance_scale=guidance[0], guidance_rescale=guidance[1], progress=progress, **plan_args)
+    if decode == "full":
+        return vae.decode(z)
+    lib, sptr = ctx.lib, ctx.sptr
+    d_thin = geo.full[0]
+    acc = torch.zeros(b, c, d_thin, hf, wf, device=ctx.device)
+    wsum = torch.zeros(b, c, d_thin, hf, wf, device=ctx.device)
+    wd, wh, ww = (_axis_window(n).to(ctx.device) for n in (td, th, tw))
+    group = window_batch if window_batch > 0 else auto
+    f, (ld, lh, lw) = geo.factor, geo.win
+    for lo in range(0, nwin, group):
+        sts = geo.starts[lo:lo + group]
+        out = vae.decode(torch.cat([z[:, :, sd:sd + ld, sh:sh + lh, sw:sw + lw] for (sd, sh, sw) in sts], dim=0)
+                         .contiguous()).contiguous()
+        with ctx.scope():
+            for k, (sd, sh, sw) in enumerate(sts):
+                ok = out[k * b:(k + 1) * b]
+                lib.blend_accumulate(_ptr(acc), _ptr(wsum), _ptr(ok), _ptr(wd), _ptr(wh), _ptr(ww), b * c, td, th, tw,
+                                     d_thin, hf, wf, sd, sh * f, sw * f, sptr)
     with ctx.scope():
         lib.blend_normalize(_ptr(acc), _ptr(wsum), acc.numel(), sptr)
     return acc

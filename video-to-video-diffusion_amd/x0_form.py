@@ -146,5 +146,5 @@ def add_x0_step(prog, kind: str, with_noise: bool):
     nbytes = (4 + 4 + 4 + zin_bytes + (4 if with_noise else 0) + (8 if prog.hist is not None else 0)) * float(
         n * L * d * h * w)
     prog._emit(run_step, "sampler.step", nbytes=nbytes,
-               audit=dict(kind="x0_step", sampler=kind, z=prog.z, v=prog.eps, hist=prog.hist, noise=noise, zin=prog.xin,
+               audit=dict(kind="x0_step", sampler=kind, z=prog.z, v=prog.eps, hist=prog.hist, noise=noise, zin=prog._zin_act(),
                           coef=prog.coef, step_ptr=prog.step_ptr, nonfinite=prog.nonfinite, n=n, L=L))
