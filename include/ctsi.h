@@ -236,6 +236,18 @@ int ctsi_attn_core(const void* qkv_bf16, void* out_bf16, int n, int c, int d, in
 int ctsi_attn_core_bwd(const void* qkv_bf16, const void* da_bf16, void* dqkv_bf16, int n, int c, int d, int h, int w, int heads,
                        void* stream);
 
+/* In-plane (spatial) attention (SpatialAttention): A[i] = sum_j softmax_j(q_i.k_j / sqrt(hd)) v_j over the
+ * N = h * w positions of one (sample, depth slice, head), flash-attention style -- query blocks per workgroup, K / V tiles of 64
+ * keys streamed through LDS, online softmax; any N >= 1, no LDS limit on N.  qkv / out as for ctsi_attn_core; lse = fp32
+ * [n][d][heads][h*w], ln sum_j exp(s_ij) of the scaled scores, may be NULL (inference).  Head dimension c / heads in
+ * {8, 16, 32, 64, 128}; anything else is CTSI_ERR_INVALID.  csrc/attention_plane.hip. */
+int ctsi_attn_plane(const void* qkv_bf16, void* out_bf16, float* lse, int n, int c, int d, int h, int w, int heads, void* stream);
+/* its backward: dqkv (bf16, 3*c channels, every element written) from the saved qkv, the forward's out (A, as stored) and lse,
+ * and dA (bf16, c channels).  Two grids, no atomics: a query-block pass writes dQ, a key-block pass dK and dV; P is recomputed
+ * from lse, delta = rowsum(dA o A).  Bit-identical run to run. */
+int ctsi_attn_plane_bwd(const void* qkv_bf16, const void* out_bf16, const void* da_bf16, const float* lse,
+                        void* dqkv_bf16, int n, int c, int d, int h, int w, int heads, void* stream);
+
 /* time embedding (models/unet3d.py:18-48 and the per-block Linear of :88-91, 123-125) ------- *
  * temb = Linear2(SiLU(Linear1(sincos(t))));  tbias[r][o] = W_all[o] . SiLU(temb[r]) + b_all[o]
  * for the concatenation of every ResBlock's time_mlp.1 (`total_out` rows of W_all).

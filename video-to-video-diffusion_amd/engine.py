@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from .attention import ATTENTION_MODES, check_attention_mode, emit_softmax_attention
+from .spatial_attention import check_spatial_attention_supported, emit_spatial_attention
 from .learned_sigma import add_sigma_split, check_learn_sigma_unsharded
 from .lib import ConvDesc, ConvOut, CtsiError, get_lib
 from .prediction import add_pred_to_eps, check_prediction_type
@@ -1203,6 +1204,7 @@ class UNetProgram(Program):
                             "volume per rank and the rescale statistics would need a collective")
         check_resblock_options_unsharded(unet, shard is not None)
         check_learn_sigma_unsharded(unet, shard is not None)
+        check_spatial_attention_supported(unet, getattr(self, "precision", "bf16"), shard is not None)
         self.unet = unet
         self.learn_sigma = bool(getattr(unet, "learn_sigma", False))      # a 2L-channel head
         self.guided, self.rescale = bool(guided), bool(guided and rescale)
@@ -1273,6 +1275,8 @@ class UNetProgram(Program):
                                  k=(3, 4, 4), s=(2, 2), p=(1, 1, 1), cout=down.conv.out_channels)
         x = step(unet.mid_block1, x)
         x = step(unet.mid_attn, x)
+        if hasattr(unet, "mid_attn_spatial"):
+            x = step(unet.mid_attn_spatial, x)
         x = step(unet.mid_block2, x)
         for level_blocks, up in zip(unet.up_blocks, unet.up_samples):
             for j, block_list in enumerate(level_blocks):
@@ -1314,6 +1318,8 @@ class UNetProgram(Program):
                                       self.step_ptr)
         if kind == "TemporalAttention":
             return self.attention(layer, x, self.attention_mode)
+        if kind == "SpatialAttention":
+            return emit_spatial_attention(self, layer, x)[0]
         raise CtsiError(f"unsupported U-Net layer {kind}")
 
     # -- inputs / schedule --

@@ -106,6 +106,8 @@ SIGNATURES = {
     "ctsi_attn_softmax_rowsum": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], True),
     "ctsi_attn_core": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], True),
     "ctsi_attn_core_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_attn_plane": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_attn_plane_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], True),
     "ctsi_time_embed_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp], True),
     "ctsi_time_embed_fwd_tf": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp], True),
     "ctsi_trilinear_depth_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp], True),

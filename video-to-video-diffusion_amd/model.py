@@ -73,7 +73,9 @@ class VideoToVideoDiffusion(nn.Module):
                            use_scale_shift_norm=_config_bool(config, 'unet_use_scale_shift_norm', False),
                            dropout=config.get('unet_dropout', 0.0),
                            # additive key: a 2L-channel head whose second half is the learned variance
-                           learn_sigma=_config_bool(config, 'unet_learn_sigma', False))
+                           learn_sigma=_config_bool(config, 'unet_learn_sigma', False),
+                           # additive key: the levels that carry in-plane SpatialAttention blocks
+                           spatial_attention_levels=config.get('unet_spatial_attention_levels', ()))
         # additive key, top level like every U-Net key: how TemporalAttention is evaluated -- 'fast' (default) / 'exact': the
         # reference's einsum as written (a depth sum); 'softmax': true attention over depth (UNet3D's docstring)
         self.unet.attention_mode = check_attention_mode(config.get('unet_attention_mode', 'fast'))

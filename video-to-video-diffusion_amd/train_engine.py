@@ -28,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from .attention import check_attention_mode, emit_softmax_attention_train
+from .spatial_attention import check_spatial_attention_supported, emit_spatial_attention_train
 from .engine import Act, Ctx, Program, _ptr
 from .lib import CtsiError, WgradDesc
 from .norm_mod import DropoutState, emit_gn_bwd_mod
@@ -428,6 +429,8 @@ class UNetTrainProgram(TrainProgram):
                 x = self.t_conv("down", down.conv, x, None, k=(3, 4, 4), s=(2, 2))
         x = self._layer(unet.mid_block1, x, None)
         x = self._layer(unet.mid_attn, x, None)
+        if hasattr(unet, "mid_attn_spatial"):
+            x = self._layer(unet.mid_attn_spatial, x, None)
         x = self._layer(unet.mid_block2, x, None)
         for level_blocks, up in zip(unet.up_blocks, unet.up_samples):
             for j, block_list in enumerate(level_blocks):
@@ -516,6 +519,8 @@ class UNetTrainProgram(TrainProgram):
             y = self.t_resblock(layer, x, skip)
         elif kind == "TemporalAttention":
             y = self.t_attention_softmax(layer, x) if self.attention_mode == "softmax" else self.t_attention(layer, x)
+        elif kind == "SpatialAttention":
+            y = emit_spatial_attention_train(self, layer, x)
         else:
             raise CtsiError(f"unsupported U-Net layer {kind}")
         return y

@@ -16,6 +16,7 @@ from .engine_f32 import check_precision
 from .engine_x3 import unet_program
 from .lib import CtsiError
 from .norm_mod import check_dropout, dropout_threshold  # noqa: F401  (re-exported)
+from .spatial_attention import check_spatial_attention_supported
 
 _GROUP_CANDIDATES = (32, 16, 8, 4, 2, 1)
 
@@ -96,6 +97,41 @@ class TemporalAttention(_EngineOnly):
         self.proj_out = nn.Conv3d(channels, channels, kernel_size=1)
 
 
+class SpatialAttention(_EngineOnly):
+    """In-plane attention (ADM's attention block; with TemporalAttention, Video Diffusion Models' factorised space-time
+    attention): per sample and depth slice, over the N = h * w positions of the plane,
+        y = x + proj_out(A),  [q | k | v] = qkv(gn(x)),  A[i] = sum_j softmax_j(q_i . k_j / sqrt(hd)) v_j,
+    heads split inside each third as TemporalAttention does.  `proj_out` is zero-initialised (ADM's zero_module): a freshly
+    added block is the identity.  Evaluated by csrc/attention_plane.hip (spatial_attention.py), whatever the
+    owning UNet3D's `attention_mode` says."""
+
+    def __init__(self, channels, num_heads=4):
+        super().__init__()
+        self.num_heads = num_heads
+        self.channels = channels
+        self.head_dim = channels // num_heads
+        assert channels % num_heads == 0, "channels must be divisible by num_heads"
+        self.norm = nn.GroupNorm(_largest_group_count(channels), channels)
+        self.qkv = nn.Conv3d(channels, channels * 3, kernel_size=1)
+        self.proj_out = nn.Conv3d(channels, channels, kernel_size=1)
+        nn.init.zeros_(self.proj_out.weight)
+        nn.init.zeros_(self.proj_out.bias)
+
+
+def check_spatial_attention_levels(levels, num_levels: int):
+    """A sequence of distinct ints in range(num_levels) -> tuple; anything else (a bool, a float, a string, a repeated level, a
+    level out of range) is a ValueError."""
+    what = f"spatial_attention_levels must be a sequence of distinct ints in range({num_levels}), got {levels!r}"
+    if isinstance(levels, (str, bytes)) or not isinstance(levels, (list, tuple)):
+        raise ValueError(what)
+    out = []
+    for v in levels:
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < num_levels or v in out:
+            raise ValueError(what)
+        out.append(v)
+    return tuple(out)
+
+
 class Downsample3D(_EngineOnly):
     def __init__(self, in_channels, out_channels=None):
         super().__init__()
@@ -144,12 +180,23 @@ class UNet3D(nn.Module):
     channels v of Improved DDPM, read when the diffusion's attribute `var_type` is 'learned_range'.  Every sampler, guidance, the three
     inference precisions, stitching and training honour it; the deterministic samplers ignore the variance channels.  It needs
     the whole depth on one device (CtsiError with depth sharding).
+
+    Constructor argument `spatial_attention_levels` (default (): none): a SpatialAttention -- in-plane
+    attention over the h * w positions of every depth slice -- is appended to every down and up stage of the listed levels, after
+    the ResBlock3D and after the TemporalAttention where the stage has one, independently of `attention_levels`, and
+    `mid_attn_spatial` runs after `mid_attn` when the deepest level is listed.  Appending leaves every existing state-dict key
+    where it is, and the new `proj_out` is zero-initialised: a reference checkpoint loads with strict=False and evaluates exactly
+    as before until the new blocks are trained.  forward, every sampler, guidance, v-prediction, the x0 form, learn_sigma,
+    stitching, training and every attention_mode honour it; it needs the bf16 engine (CtsiError with inference_precision
+    'fp32' / 'bf16x3'), the whole depth on one device (CtsiError with depth sharding) and a head dimension in
+    {8, 16, 32, 64, 128}.
     """
 
     def __init__(self, latent_dim=4, model_channels=128, num_res_blocks=2, attention_levels=[1, 2],
                  channel_mult=(1, 2, 4, 4), num_heads=4, time_embed_dim=512, use_checkpoint=False,
-                 use_scale_shift_norm=False, dropout=0.0, learn_sigma=False):
+                 use_scale_shift_norm=False, dropout=0.0, learn_sigma=False, spatial_attention_levels=()):
         super().__init__()
+        self.spatial_attention_levels = check_spatial_attention_levels(spatial_attention_levels, len(channel_mult))
         if not isinstance(learn_sigma, bool):
             raise ValueError(f"learn_sigma must be True or False, got {learn_sigma!r}")
         self.learn_sigma = learn_sigma
@@ -169,10 +216,12 @@ class UNet3D(nn.Module):
         self.time_embed = TimeEmbedding(model_channels, time_embed_dim)
         self.conv_in = nn.Conv3d(latent_dim * 2, model_channels, kernel_size=3, padding=1)
 
-        def stage(cin, cout, with_attn):
+        def stage(cin, cout, with_attn, with_spatial):
             layers = [ResBlock3D(cin, cout, time_embed_dim, self.use_scale_shift_norm)]
             if with_attn:
                 layers.append(TemporalAttention(cout, num_heads))
+            if with_spatial:
+                layers.append(SpatialAttention(cout, num_heads))
             return nn.ModuleList(layers)
 
         self.down_blocks = nn.ModuleList()
@@ -182,13 +231,15 @@ class UNet3D(nn.Module):
             width = model_channels * mult
             blocks = nn.ModuleList()
             for _ in range(num_res_blocks):
-                blocks.append(stage(ch, width, level in attention_levels))
+                blocks.append(stage(ch, width, level in attention_levels, level in self.spatial_attention_levels))
                 ch = width
             self.down_blocks.append(blocks)
             self.down_samples.append(Downsample3D(ch, ch) if level < self.num_levels - 1 else nn.Identity())
 
         self.mid_block1 = ResBlock3D(ch, ch, time_embed_dim, self.use_scale_shift_norm)
         self.mid_attn = TemporalAttention(ch, num_heads)
+        if self.num_levels - 1 in self.spatial_attention_levels:
+            self.mid_attn_spatial = SpatialAttention(ch, num_heads)
         self.mid_block2 = ResBlock3D(ch, ch, time_embed_dim, self.use_scale_shift_norm)
 
         self.up_blocks = nn.ModuleList()
@@ -199,7 +250,8 @@ class UNet3D(nn.Module):
             blocks = nn.ModuleList()
             for i in range(num_res_blocks + 1):
                 cin = ch + model_channels * channel_mult[src_level] if i == 0 else ch
-                blocks.append(stage(cin, width, src_level in attention_levels))
+                blocks.append(stage(cin, width, src_level in attention_levels,
+                                    src_level in self.spatial_attention_levels))
                 ch = width
             self.up_blocks.append(blocks)
             self.up_samples.append(Upsample3D(ch) if level < self.num_levels - 1 else nn.Identity())
@@ -222,6 +274,7 @@ class UNet3D(nn.Module):
     def program(self, ctx: Ctx, n: int, d: int, h: int, w: int, max_rows: int) -> UNetProgram:
         precision = check_precision(self.inference_precision)
         check_attention_mode(self.attention_mode)
+        check_spatial_attention_supported(self, precision)
         key = ("unet", ctx.device.index, n, d, h, w, max_rows, self.attention_mode, precision)
         cls = unet_program(precision)
         return cached_program(self, key, lambda: cls(ctx, self, n, d, h, w, max_rows, self.attention_mode))
@@ -230,6 +283,7 @@ class UNet3D(nn.Module):
     def forward(self, x, t, c):
         check_precision(self.inference_precision)
         check_attention_mode(self.attention_mode)
+        check_spatial_attention_supported(self, self.inference_precision)
         if not (x.is_cuda and c.is_cuda):
             raise CtsiError("UNet3D.forward runs on the HIP engine: move the tensors to a ROCm device "
                             "(there is no CPU path; the oracle under oracle/ is test infrastructure only)")
