@@ -791,6 +791,31 @@ int ctsi_window_gather_f32(const float* src, float* dst, const int* starts, int 
 int ctsi_window_blend(const float* win, float* full, const int* tab_i, const float* tab_w, int batch, int halves, int nwd,
                       int nwh, int nww, int D, int H, int W, int td, int lh, int lw, int C, int kd, int kh, int kw, void* stream);
 
+/* Image-space loss terms of the diffusion stage (csrc/image_loss.hip): the training step's predicted clean
+ * latent as a second, differentiable output, and the loss-head backward that takes its gradient back in.
+ * ctsi_z0_pred: out (fp32 NCDHW (n, c, d, h, w)) = the clean latent the training step's prediction stands for.  z0, noise:
+ *   fp32 NCDHW; pred: the raw network output, fp32 NDHWC with c_stride >= c floats per voxel; sqrt_ac / sqrt_1mac: the
+ *   schedule tables q_sample reads, indexed by t[b]; active: int32 (n).  With z_t = sqrt_ac[t] z0 + sqrt_1mac[t] noise,
+ *     v_prediction == 0:  out = (z_t - sqrt_1mac[t] pred) / sqrt_ac[t]      (ctsi_ddpm_posterior's z_0: one fma, one division)
+ *     v_prediction != 0:  out = sqrt_ac[t] z_t - sqrt_1mac[t] pred          (no division)
+ *   Rows with active[b] == 0 are copies of z0 (bit for bit): nothing non-finite and no 1 / sqrt_ac blow-up at t -> T, whatever
+ *   pred holds there.  16-byte accesses when c, c_stride and d h w are multiples of 4 and every pointer is 16-byte aligned,
+ *   element-wise otherwise.
+ * ctsi_loss_bwd_z0: ctsi_mse_loss_bwd with the gradient g_z0 (fp32 NCDHW) of ctsi_z0_pred's output added in fp32 BEFORE the
+ *   one rounding to bf16:
+ *     dpred = bf16(2 norm[b] mask (pred - target) gscale[0] + active[b] coef[b] g_z0),   channels c .. c_stride-1 zero,
+ *   coef[b] = d out / d pred of the row: -sqrt_1mac[t_b] / sqrt_ac[t_b] (epsilon) or -sqrt_1mac[t_b] (v), formed by the caller.
+ *   pred: fp32 NDHWC with c floats per voxel, target: fp32 NCDHW, mask: fp32 (n, c, d) or NULL (it acts on the first term
+ *   only), gscale: NULL = 1.  g_z0 of a row with active[b] == 0 is not read.  g_z0 == 0 gives ctsi_mse_loss_bwd's bits.
+ * Null pointers / non-positive sizes / c_stride < c return CTSI_ERR_INVALID before any launch.  Capture-safe: no
+ * allocation, no synchronisation. */
+int ctsi_z0_pred(const float* z0, const float* noise, const float* pred, int c_stride, const float* sqrt_ac,
+                 const float* sqrt_1mac, const int* t, const int* active, int v_prediction, int n, int c, int d, int h, int w,
+                 float* out, void* stream);
+int ctsi_loss_bwd_z0(const float* pred, const float* target, const float* mask, const float* norm, const float* gscale,
+                     const float* g_z0, const int* active, const float* coef, int n, int c, int d, int h, int w, void* dpred,
+                     int c_stride, void* stream);
+
 /* timing helpers used by bench.py (HIP events on the engine's own stream) ----------------- */
 typedef struct ctsi_event ctsi_event;
 int ctsi_event_create(ctsi_event** ev);

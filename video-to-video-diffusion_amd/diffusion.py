@@ -404,7 +404,11 @@ class GaussianDiffusion(nn.Module):
         The 64-bit seed is drawn from torch's default CPU generator AFTER t and noise, and only when the threshold
         floor(dropout * 65536) is > 0 -- so dropout = 0 consumes exactly the random numbers it always did; the plain attribute
         `model.dropout_seed` (an int; None, the default, draws) injects it instead, the test hook beside `t=` / `noise=` (an
-        attribute because this signature is pinned).  `model.eval()` turns dropout off."""
+        attribute because this signature is pinned).  `model.eval()` turns dropout off.
+
+        `training_loss_and_prediction` runs this body too: its request for the predicted clean latent is the
+        private per-call attribute `_pred_request` (an attribute for the same reason), taken off the object first thing."""
+        pred_request = self.__dict__.pop("_pred_request", None)
         p_drop = float(cond_drop_prob)
         if not 0.0 <= p_drop <= 1.0:
             raise ValueError(f"cond_drop_prob must lie in [0, 1], got {cond_drop_prob!r}")
@@ -475,7 +479,12 @@ class GaussianDiffusion(nn.Module):
                 prog.set_dropout(drop_p, dropout_seed)
             if learned:
                 prog.set_vb_norm(norm_vb)
-        loss = train_step(prog, z_0.detach().float(), c.detach().float(), t, noise.float(), norm, m)
+        if pred_request is not None:      # the same forward launches, then ctsi_z0_pred; two differentiable outputs
+            from .train_engine import train_step_pred
+            loss, pred_request["z0_pred"] = train_step_pred(prog, z_0.detach().float(), c.detach().float(), t, noise.float(),
+                                                            norm, m, pred_request["active"])
+        else:
+            loss = train_step(prog, z_0.detach().float(), c.detach().float(), t, noise.float(), norm, m)
         loss_dict = {'mse': loss.item()}
         if learned:       # the program's loss_out = {total, mse, vb, ...}: 'mse' keeps its meaning, 'vb' = lambda L_vb (bits)
             parts = prog.loss_out[1:3].tolist()
@@ -521,3 +530,29 @@ class GaussianDiffusion(nn.Module):
                 print(f"Warning: MS-SSIM calculation failed: {e}. Using MSE-only loss.")
         loss_dict['total'] = loss.item() if learned else loss_dict['mse']
         return loss, loss_dict
+
+    def training_loss_and_prediction(self, model, z_0, c, mask=None, t=None, noise=None, cond_drop_prob=0.0, cond_keep=None,
+                                     active=None):
+        """training_loss that also returns the clean latent its prediction stands for, with a gradient (additive; DESIGN
+        section 27): (loss, loss_dict, z0_pred).  It IS training_loss -- the same body, the same draws from torch's generators
+        in the same order, the same program, the same loss bits -- followed by one ctsi_z0_pred launch on the training
+        program's own buffers: epsilon (z_t - sqrt(1 - abar_t) eps^) / sqrt(abar_t), v sqrt(abar_t) z_t - sqrt(1 - abar_t) v^,
+        fp32, z_0's shape.  The gradient of z0_pred enters the U-Net backward through ctsi_loss_bwd_z0, added to the loss
+        gradient in fp32 before the one rounding to bf16.  `active` (bool, (B,); None = every row): the rows that take part;
+        the others come back as z_0 itself and carry no gradient (the epsilon form's d z0^ / d eps^ = -sqrt(1 / abar_t - 1)
+        is unbounded as t -> T: callers gate on the SNR, see VideoToVideoDiffusion.image_loss_min_snr).  The loss `mask` acts
+        on the MSE term only.  A learn_sigma model raises CtsiError: the hybrid loss has a backward kernel of its own."""
+        if self._learned() or bool(getattr(model, "learn_sigma", False)):
+            raise CtsiError("training_loss_and_prediction does not support learn_sigma models (var_type='learned_range'): the "
+                            "hybrid loss has its own backward kernel, which takes no gradient of the predicted latent")
+        if active is not None and (not torch.is_tensor(active) or active.dtype != torch.bool
+                                   or tuple(active.shape) != (z_0.shape[0],)):
+            raise ValueError(f"active must be a bool tensor of shape ({z_0.shape[0]},)")
+        request = dict(active=active)
+        self.__dict__["_pred_request"] = request
+        try:
+            loss, loss_dict = self.training_loss(model, z_0, c, mask=mask, t=t, noise=noise, cond_drop_prob=cond_drop_prob,
+                                                 cond_keep=cond_keep)
+        finally:
+            self.__dict__.pop("_pred_request", None)
+        return loss, loss_dict, request["z0_pred"]

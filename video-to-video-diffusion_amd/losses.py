@@ -362,3 +362,15 @@ class CombinedLoss(nn.Module):
         self.step += 1
         loss_dict['total'] = total_loss.item()
         return total_loss, loss_dict
+
+
+def auxiliary_due(c) -> bool:
+    """Whether `c(pred, target, diffusion_loss)` would evaluate an auxiliary term at its current `step`: CombinedLoss.forward's
+    own two conditions, read without advancing the step.  The diffusion stage (VideoToVideoDiffusion.image_loss, DESIGN section
+    27) asks before it builds `pred`: a decode with its backward tape is not worth building for a step that drops it.  Any
+    other callable is always due."""
+    if not isinstance(c, CombinedLoss):
+        return True
+    step = int(c.step)
+    return bool((c.lambda_perceptual > 0 and step % c.perceptual_every_n_steps == 0) or
+                (c.lambda_ssim > 0 and step % c.ssim_every_n_steps == 0))

@@ -3,6 +3,7 @@ construction, `generate`, checkpoint layout.  Inference runs entirely on the HIP
 from __future__ import annotations
 
 import logging
+import math
 
 import torch
 import torch.nn as nn
@@ -27,7 +28,56 @@ def _config_bool(config, key, default):
     return v
 
 
+def check_image_loss_min_snr(v) -> float:
+    """`image_loss_min_snr` must be a finite number > 0 (ValueError otherwise): 1 / sqrt(min_snr) bounds the factor
+    sqrt(1 / abar_t - 1) by which the epsilon form turns a gradient of the predicted latent into one of the prediction."""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0:
+        raise ValueError(f"image_loss_min_snr must be a finite number > 0, got {v!r}")
+    return float(v)
+
+
+def image_loss_rows(diffusion, t: torch.Tensor, min_snr: float) -> torch.Tensor:
+    """The rows of a batch that take part in the image-space loss terms: abar_t / (1 - abar_t) >= min_snr, decided in float64
+    on `alphas_cumprod` without the division (bool, t's shape and device)."""
+    ab = diffusion.alphas_cumprod.detach().double().to(t.device)[t.long()]
+    return ab >= check_image_loss_min_snr(min_snr) * (1.0 - ab)
+
+
+def image_loss_from_config(config):
+    """(image_loss, image_loss_min_snr) of a config.  The reference's `losses:` section is honoured only when it carries the
+    additive key `apply_image_losses: true` (a real bool); without the key the section is ignored, as it always was."""
+    sec = config.get('losses', None)
+    if not isinstance(sec, dict) or not _config_bool(sec, 'apply_image_losses', False):
+        return None, 1.0
+    from .losses import CombinedLoss
+    for key in ('perceptual_every_n_steps', 'ssim_every_n_steps'):
+        v = sec.get(key, 10)
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"losses.{key} must be an integer >= 1, got {v!r}")
+    lam = {}
+    for key in ('lambda_perceptual', 'lambda_ssim'):
+        v = sec.get(key, 0.1)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"losses.{key} must be a finite number >= 0, got {v!r}")
+        lam[key] = float(v)
+    loss = CombinedLoss(lam['lambda_perceptual'] if _config_bool(sec, 'use_perceptual_loss', False) else 0.0,
+                        lam['lambda_ssim'] if _config_bool(sec, 'use_ms_ssim_loss', False) else 0.0,
+                        sec.get('perceptual_every_n_steps', 10), sec.get('ssim_every_n_steps', 10))
+    return loss, check_image_loss_min_snr(sec.get('image_loss_min_snr', 1.0))
+
+
 class VideoToVideoDiffusion(nn.Module):
+    def __setattr__(self, name, value):
+        # `image_loss` stays OUT of the module tree even when it is an nn.Module (a CombinedLoss): the model's parameters, its
+        # state dict and its checkpoints keep their layout, and a VGG-19 inside the loss is not saved with every checkpoint
+        if name == "image_loss":
+            if value is not None and not callable(value):
+                raise ValueError(f"image_loss must be None or a callable (pred, target, diffusion_loss, "
+                                 f"compute_auxiliary=True) -> (total, dict), got {type(value).__name__}")
+            self.__dict__["image_loss"] = value
+            return
+        super().__setattr__(name, value)
+
     def __init__(self, config, load_pretrained=False):
         super().__init__()
         pre = config.get('pretrained', {})
@@ -106,6 +156,10 @@ class VideoToVideoDiffusion(nn.Module):
             raise ValueError(f"cond_drop_prob must lie in [0, 1], got {config.get('cond_drop_prob')!r}")
         # additive key: the arithmetic of generate() / the samplers / encode / decode ('bf16' default, 'fp32' or 'bf16x3')
         self.set_inference_precision(config.get('hardware', {}).get('inference_precision', 'bf16'))
+        # image-space loss terms of `forward`, plain attributes: `image_loss` -- None (default) or a callable
+        # with CombinedLoss.forward's signature -- and the SNR gate of the rows that take part.  From the config only when its
+        # `losses:` section says `apply_image_losses: true`.
+        self.image_loss, self.image_loss_min_snr = image_loss_from_config(config)
 
     def set_inference_precision(self, precision):
         """'bf16' (default), 'fp32' or 'bf16x3' (fp32 tensors, split-bf16 MFMA convolutions: engine_x3.py): sets `unet.inference_precision` and `vae.inference_precision`, i.e. the arithmetic
@@ -154,10 +208,38 @@ class VideoToVideoDiffusion(nn.Module):
                                            mode='nearest').squeeze(-1).squeeze(-1)
             else:
                 z_cond, z_mask = z_in, mask
+        if self.image_loss is not None:
+            return self._forward_image_loss(v_gt, z_gt, z_cond, z_mask, t, noise, cond_keep)
         loss, loss_dict = self.diffusion.training_loss(self.unet, z_gt, z_cond, mask=z_mask, vae=self.vae, v_gt=v_gt,
                                                        use_ssim=False, ssim_weight=0.0, t=t, noise=noise,
                                                        cond_drop_prob=self.cond_drop_prob, cond_keep=cond_keep)
         return loss, {'loss': loss.item(), **loss_dict}
+
+    def _forward_image_loss(self, v_gt, z_gt, z_cond, z_mask, t, noise, cond_keep):
+        """`forward` with `image_loss` set: the diffusion loss and the predicted clean latent of the rows
+        whose SNR passes `image_loss_min_snr` (training_loss_and_prediction), those rows decoded through the frozen VAE with a
+        data-gradient tape (vae.decode_with_grad), then `total, d = image_loss(pred, v_gt[rows], loss)`.  Returns
+        (total, {**the plain metrics, **d, 'image_rows': k}).  Only the k active rows are decoded.  The term is skipped --
+        `image_loss(None, None, loss, compute_auxiliary=False)`, no prediction, no decode -- when no row is active or when a
+        CombinedLoss has no auxiliary term due at its current step (losses.auxiliary_due).  Under torch.no_grad() the term is
+        evaluated through the plain decode and nothing is kept.  The loss `mask` acts on the MSE term only: the image term
+        compares whole decoded rows.  t is drawn here, where training_loss would draw it (first, from the same generator)."""
+        from .losses import auxiliary_due
+        fn, kw = self.image_loss, dict(cond_drop_prob=self.cond_drop_prob, cond_keep=cond_keep)
+        if t is None:
+            t = torch.randint(0, self.diffusion.timesteps, (z_gt.shape[0],), device=z_gt.device, dtype=torch.long)
+        rows = image_loss_rows(self.diffusion, t, self.image_loss_min_snr)
+        k = int(rows.sum().item())
+        if k == 0 or not auxiliary_due(fn):
+            loss, loss_dict = self.diffusion.training_loss(self.unet, z_gt, z_cond, mask=z_mask, t=t, noise=noise, **kw)
+            total, d = fn(None, None, loss, compute_auxiliary=False)
+            return total, {'loss': loss.item(), **loss_dict, **d, 'image_rows': k}
+        loss, loss_dict, z0_pred = self.diffusion.training_loss_and_prediction(self.unet, z_gt, z_cond, mask=z_mask, t=t,
+                                                                               noise=noise, active=rows, **kw)
+        idx = rows.nonzero().flatten()
+        pred = self.vae.decode_with_grad(z0_pred.index_select(0, idx))
+        total, d = fn(pred, v_gt.index_select(0, idx).float(), loss)
+        return total, {'loss': loss.item(), **loss_dict, **d, 'image_rows': k}
 
     @torch.no_grad()
     def generate(self, v_in, sampler, num_inference_steps=20, guidance_scale=1.0, target_depth=None,

@@ -17,6 +17,8 @@ the backward launches, built by replaying a tape of the forward layers in revers
 
 `train_step` wraps both passes in a torch.autograd.Function over the U-Net parameters, so `loss.backward()`,
 GradScaler, gradient accumulation, clip_grad_norm_ and any torch optimizer work as with the reference.
+`train_step_pred` is the same step with the predicted clean latent as a second differentiable output
+(ctsi_z0_pred after the forward list; its gradient enters the loss launch through ctsi_loss_bwd_z0).
 """
 from __future__ import annotations
 
@@ -41,6 +43,7 @@ class TrainProgram(Program):
     GroupNorm forward wrappers that record their backward on a tape, and the backward launches themselves."""
     tbias = None       # time-bias rows of the U-Net (programs without a time embedding leave these unset)
     total_out = 0
+    data_only = False  # True: a backward of data gradients only (vae_train_engine.VAEDecodeGradProgram): no parameter buffers
 
     def _ws_ptr(self, key):
         return C.c_void_p(self._ws[key].data_ptr())
@@ -124,7 +127,7 @@ class TrainProgram(Program):
         T = k[0] * k[1] * k[2]
         cin = x1.c + (0 if x2 is None else x2.c)
         cw_out = wparam.shape[1] if transposed else wparam.shape[0]
-        if gw is None:
+        if gw is None and not self.data_only:
             pad = g.c if (not transposed and g.c > wparam.shape[0]) else None
             gw = self.grad_buf(wparam, rows_pad=pad)
         if gb is None and bparam is not None:
@@ -462,7 +465,17 @@ class UNetTrainProgram(TrainProgram):
         self.generation = 0   # bumped by every run_forward (see there)
 
         # ---- backward: loss, then the tape in reverse, then the time embedding ---------------------------------
+        # the predicted clean latent as a second output (train_step_pred): buffers made on first use, the
+        # gradient that came back through it enters the loss launch below
+        self.z0_hat = self.g_z0 = self.active = self.coef = None
+        self.use_gz0 = False
+
         def run_loss_bwd():
+            if prog.use_gz0:      # ctsi_mse_loss_bwd's expression + active coef g_z0, rounded once
+                lib.loss_bwd_z0(_ptr(prog.eps), _ptr(prog.target), _ptr(prog.mask) if prog.use_mask else None,
+                                _ptr(prog.norm), _ptr(prog.gscale), _ptr(prog.g_z0), _ptr(prog.active), _ptr(prog.coef),
+                                n, L, d, h, w, prog.d_eps.ip, prog.Lp, sptr)
+                return
             lib.mse_loss_bwd(_ptr(prog.eps), _ptr(prog.target), _ptr(prog.mask) if prog.use_mask else None,
                              _ptr(prog.norm), _ptr(prog.gscale), n, L, d, h, w, prog.d_eps.ip, prog.Lp, sptr)
 
@@ -703,14 +716,51 @@ class UNetTrainProgram(TrainProgram):
             op()
         return self.loss_out[0].clone()
 
-    def run_backward(self, grad_out: torch.Tensor, generation: Optional[int] = None) -> List[torch.Tensor]:
+    def run_z0_pred(self, active: Optional[torch.Tensor]) -> torch.Tensor:
+        """After run_forward: the clean latent its prediction stands for (one ctsi_z0_pred launch on the program's own z0, noise,
+        t_rows, schedule tables and raw prediction), fp32 NCDHW.  `active` (bool, (n,); None = every row): the other rows come
+        back as z0 itself and take no gradient.  Also stores the rows' d z0^ / d pred for the backward.  (Not for learn_sigma
+        programs, whose `eps` holds 2L channels: train_step_pred refuses them.)"""
+        n, L = self.n, self.L
+        if self.z0_hat is None:
+            self.z0_hat = self.persistent((n, L, self.d, self.h, self.w), torch.float32)
+            self.g_z0 = self.persistent((n, L, self.d, self.h, self.w), torch.float32, zero=True)
+            self.active = self.persistent((n,), torch.int32, zero=True)
+            self.coef = self.persistent((n,), torch.float32, zero=True)
+        dev = self.ctx.device
+        act = torch.ones(n, dtype=torch.bool, device=dev) if active is None else active.to(device=dev, dtype=torch.bool)
+        if tuple(act.shape) != (n,):
+            raise ValueError(f"active must be a bool tensor of shape ({n},), got {tuple(act.shape)}")
+        self.active.copy_(act.to(torch.int32))
+        # coef[b] = d z0^ / d pred, float64 from the two tables the kernel reads, rounded once: -sqrt(1 / abar - 1) | -sqrt(1 - abar)
+        t = self.t_rows.long()
+        a, s = self.sqrt_ac.double()[t], self.sqrt_1mac.double()[t]
+        coef = -s if self.prediction == "v_prediction" else -s / torch.where(act, a, torch.ones_like(a))
+        self.coef.copy_(torch.where(act, coef, torch.zeros_like(coef)).float())
+        self.lib.z0_pred(_ptr(self.z0), _ptr(self.noise), _ptr(self.eps), self.Lo, _ptr(self.sqrt_ac), _ptr(self.sqrt_1mac),
+                         _ptr(self.t_rows), _ptr(self.active), int(self.prediction == "v_prediction"), n, L, self.d, self.h,
+                         self.w, _ptr(self.z0_hat), self.ctx.sptr)
+        return self.z0_hat.clone()
+
+    def run_backward(self, grad_out: Optional[torch.Tensor], generation: Optional[int] = None,
+                     grad_z0: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+        """`grad_z0` (train_step_pred): the gradient of run_z0_pred's result; the loss launch then is ctsi_loss_bwd_z0.
+        `grad_out` None: the loss itself took no gradient (gscale 0)."""
         if generation is not None and generation != self.generation:
             raise CtsiError(
                 "backward of a training forward whose saved activations were overwritten: another forward of the same "
                 f"shape ran on this program in between (tape generation {generation}, now {self.generation}).  Call "
                 "backward() before the next forward of that shape, or evaluate the second batch under torch.no_grad() "
                 "through model.generate / unet(x, t, c), which do not touch the training tape.")
-        self.gscale.copy_(grad_out.reshape(1).to(torch.float32))
+        if grad_out is None:
+            self.gscale.zero_()
+        else:
+            self.gscale.copy_(grad_out.reshape(1).to(torch.float32))
+        self.use_gz0 = grad_z0 is not None
+        if grad_z0 is not None:
+            if self.g_z0 is None:
+                raise CtsiError("internal: a gradient of the predicted latent without a run_z0_pred")
+            self.g_z0.copy_(grad_z0.reshape(self.g_z0.shape))
         for op in self.ops[self.n_fwd:]:
             op()
         out = []
@@ -770,3 +820,37 @@ class _TrainStep(torch.autograd.Function):
 
 def train_step(prog: UNetTrainProgram, z0, cond, t, noise, norm, mask=None) -> torch.Tensor:
     return _TrainStep.apply(prog, z0, cond, t, noise, norm, mask, *prog.params)
+
+
+class _TrainStepPred(torch.autograd.Function):
+    """(loss, z0_pred) of one batch: _TrainStep with the predicted clean latent as a second differentiable output.  Either
+    gradient may be absent in the backward; one generation check covers both outputs."""
+
+    @staticmethod
+    def forward(fctx, prog: UNetTrainProgram, z0, cond, t, noise, norm, mask, active, *params):
+        with prog.ctx.scope():
+            loss = prog.run_forward(z0, cond, t, noise, norm, mask)
+            z0_pred = prog.run_z0_pred(active)
+        fctx.prog = prog
+        fctx.generation = prog.generation
+        fctx.set_materialize_grads(False)
+        return loss, z0_pred
+
+    @staticmethod
+    def backward(fctx, grad_loss, grad_z0):
+        prog = fctx.prog
+        if grad_loss is None and grad_z0 is None:
+            return (None,) * (8 + len(prog.params))
+        with prog.ctx.scope():
+            grads = _clone_grads(prog.run_backward(grad_loss, fctx.generation, grad_z0))
+        return (None,) * 8 + tuple(grads)
+
+
+def train_step_pred(prog: UNetTrainProgram, z0, cond, t, noise, norm, mask=None, active=None):
+    """train_step that also returns the clean latent the prediction stands for (fp32 NCDHW, ctsi_z0_pred), with a gradient:
+    `active` (bool, (n,); None = all) names the rows that take part -- the others are returned as z0 and get no gradient.
+    learn_sigma programs raise CtsiError."""
+    if prog.learn_sigma:
+        raise CtsiError("train_step_pred does not support learn_sigma programs: the hybrid loss has its own backward kernel, "
+                        "which takes no gradient of the predicted latent")
+    return _TrainStepPred.apply(prog, z0, cond, t, noise, norm, mask, active, *prog.params)

@@ -165,6 +165,27 @@ class SliceInterpolationVAE(nn.Module):
                 prog = cached_program(self, key, lambda: cls(ctx, self, n, d, h, w))
             return prog(z)
 
+    def decode_with_grad(self, z):
+        """decode(z) that is differentiable in `z`: in grad mode with `z.requires_grad` the result carries an
+        autograd node whose backward (vae_train_engine.VAEDecodeGradProgram: data gradients only, on the HIP engine) returns
+        dL/dz.  The VAE is treated as frozen: no parameter receives a gradient, and the parameters' requires_grad flags are
+        neither read nor changed.  Always the bf16 programs, like every training path; the value is bit for bit
+        `_decode(z, "bf16")`, which is also what the call falls through to when z needs no gradient.  One program per
+        (n, d, h, w) holds the activations of its latest forward: a second call of the same shape before the first one's
+        backward makes that backward raise CtsiError.  Needs a latent_dim that is a multiple of 8."""
+        if not (torch.is_tensor(z) and torch.is_grad_enabled() and z.requires_grad):
+            return self._decode(z, "bf16")
+        from .vae_train_engine import VAEDecodeGradProgram, check_decode_grad_geometry, vae_decode_grad_step
+        check_decode_grad_geometry(self, z)
+        n, _, d, h, w = z.shape
+        ctx = Ctx.get(z.device)
+        with ctx.scope():
+            # kept on the decoder module: one program per number of decoded rows must not push the encode / decode programs of
+            # a training step out of this module's cache (engine.PROGRAM_CACHE_SIZE entries per module)
+            key = ("dec-grad", ctx.device.index, n, d, h, w, float(self.scaling_factor))
+            prog = cached_program(self.decoder, key, lambda: VAEDecodeGradProgram(ctx, self, n, d, h, w))
+        return vae_decode_grad_step(prog, z)
+
     def encode_with_posterior(self, x):
         """(mu, logvar) = channel halves of the unscaled encoder output (vae.py:262-287)."""
         z = self.encode(x) / self.scaling_factor

@@ -17,6 +17,9 @@ gradient takes 1 / sf through ctsi_wgrad's scale.
 
 `vae_train_step` wraps both passes in a torch.autograd.Function over the VAE parameters (like train_engine._TrainStep), so
 GradScaler, gradient accumulation, clip_grad_norm_ and any torch optimizer work unchanged.  The input gets no gradient.
+
+`VAEDecodeGradProgram` is the opposite cut of the same tape: the decoder alone, differentiated with respect
+to its INPUT and nothing else (`SliceInterpolationVAE.decode_with_grad`), for image-space loss terms of the diffusion stage.
 """
 from __future__ import annotations
 
@@ -167,8 +170,9 @@ class VAETrainProgram(TrainProgram):
     # ---- layers --------------------------------------------------------------------------------------------------------------
     def v_conv(self, name, m, x1: Act, *, weight_fn=None, bias_fn=None, cin_w=None, k=(3, 3, 3), s=(1, 1),
                transposed=False, want_stats=False, bias_from_gn=False, need_dx=True, f32_out=None, f32_strides=None, act=0,
-               gy: Optional[Act] = None, w_scale=1.0, stem=False, thin_head=False):
-        """One forward conv (the call engine.VAE*Program makes for this layer) and its backward on the tape."""
+               gy: Optional[Act] = None, w_scale=1.0, stem=False, thin_head=False, dgrad_weight_fn=None):
+        """One forward conv (the call engine.VAE*Program makes for this layer) and its backward on the tape.  In a `data_only`
+        program the backward is the data gradient alone (`dgrad_weight_fn`: the weight it uses, when not the layer's own)."""
         p = (1, 1, 1) if k != (1, 1, 1) else (0, 0, 0)
         cout = m.out_channels
         out, st = self.conv(name, weight_fn or (lambda: m.weight), bias_fn or (lambda: m.bias), x1, None,
@@ -187,8 +191,9 @@ class VAETrainProgram(TrainProgram):
             g = gy if gy is not None else out.grad
             if g is None:
                 raise CtsiError(f"internal: no gradient reached the output of {name}")
-            self._conv_bwd(name, m.weight, None if bias_from_gn else m.bias, x1, None, g, transposed, k, s, p, cout,
-                           need_dx and not stem, w_scale=w_scale, gw_cin=gw_cin, emit_wgrad=not thin)
+            self._conv_bwd(name, m.weight, None if (bias_from_gn or self.data_only) else m.bias, x1, None, g, transposed, k, s,
+                           p, cout, need_dx and not stem, w_scale=w_scale, gw_cin=gw_cin,
+                           emit_wgrad=not thin and not self.data_only, w_src=dgrad_weight_fn)
             if thin:
                 self._thin_wgrad(name, m.weight, g, x1, head=not stem)
             if gy is None:
@@ -228,15 +233,20 @@ class VAETrainProgram(TrainProgram):
         c, st = self.v_conv(name, m.conv, x, cin_w=cin_w, k=k, s=s, transposed=transposed, want_stats=True,
                             bias_from_gn=True, stem=stem)
         slot = self.gn_finalize(c, m.norm.num_groups, st)
-        return self.t_gn(c, slot, m.norm, silu_pre=True, conv_bias=m.conv.bias)
+        return self.t_gn(c, slot, m.norm, silu_pre=True, conv_bias=self._gn_bias(m.conv))
+
+    def _gn_bias(self, conv):
+        """The conv bias whose gradient the following GroupNorm backward sums (none in a data-gradient-only program)."""
+        return None if self.data_only else conv.bias
 
     def resblock(self, m, x: Act) -> Act:
         c1, st = self.v_conv("rb.conv1", m.conv1.conv, x, want_stats=True, bias_from_gn=True)
         slot = self.gn_finalize(c1, m.conv1.norm.num_groups, st)
-        h1 = self.t_gn(c1, slot, m.conv1.norm, silu_pre=True, conv_bias=m.conv1.conv.bias)
+        h1 = self.t_gn(c1, slot, m.conv1.norm, silu_pre=True, conv_bias=self._gn_bias(m.conv1.conv))
         c2, st = self.v_conv("rb.conv2", m.conv2[0], h1, want_stats=True, bias_from_gn=True)
         slot = self.gn_finalize(c2, m.conv2[1].num_groups, st)
-        return self.t_gn(c2, slot, m.conv2[1], silu_pre=False, residual=x, silu_post=True, conv_bias=m.conv2[0].bias)
+        return self.t_gn(c2, slot, m.conv2[1], silu_pre=False, residual=x, silu_post=True,
+                         conv_bias=self._gn_bias(m.conv2[0]))
 
     def block(self, m, x: Act) -> Act:
         kind = type(m).__name__
@@ -319,3 +329,159 @@ class _VAETrainStep(torch.autograd.Function):
 
 def vae_train_step(prog: VAETrainProgram, x: torch.Tensor):
     return _VAETrainStep.apply(prog, x, *prog.params)
+
+
+# ==== a differentiable decode of a FROZEN decoder =====================================================
+def check_decode_grad_geometry(vae, z: torch.Tensor):
+    """Raise CtsiError for latents the data-gradient program cannot differentiate (never a silently wrong backward)."""
+    if not z.is_cuda:
+        raise CtsiError("decode_with_grad runs on the HIP engine: move the latent to a ROCm device (there is no CPU path)")
+    if z.dim() != 5:
+        raise ValueError(f"decode expects a (B, C, T, H, W) tensor, got shape {tuple(z.shape)}")
+    if z.shape[1] != vae.latent_dim:
+        raise ValueError(f"decode expects {vae.latent_dim} latent channels, got {z.shape[1]}")
+    if vae.latent_dim % 8:
+        raise CtsiError(f"decode_with_grad needs latent_dim a multiple of 8 (got {vae.latent_dim})")
+    for p in vae.decoder.parameters():
+        if not p.is_cuda or p.device != z.device:
+            raise CtsiError("decode_with_grad runs on the HIP engine: the decoder's parameters must live on the latent's ROCm "
+                            "device")
+
+
+class VAEDecodeGradProgram(VAETrainProgram):
+    """decode(z) with the gradient for z and for nothing else: the decoder half of VAETrainProgram -- the launches of
+    engine.VAEDecodeProgram at that shape, every activation kept, `recon` bit for bit `vae._decode(z, "bf16")` -- and a tape of
+    DATA gradients only: ctsi_vae_head_grad mode 0 at the tanh head, the data-gradient conv of every layer (no weight gradient,
+    no bias sum), ctsi_gn_bwd for dx (its dgamma / dbeta land in scratch nobody reads), and at the seam one layout pass back to
+    fp32 NCDHW.  Scale folding: the forward packs W_p / sf into post_quant_conv; the data gradient uses the same W_p / sf, so
+    the seam's grad_z already is dL/dz.  The decoder's parameters get no gradient and their requires_grad flags are not looked
+    at.  The weights are frozen as far as this program is concerned, so it shares packed weight images with the inference
+    programs (a changed parameter is still picked up: Program.ensure_fresh)."""
+    data_only = True
+
+    def __init__(self, ctx: Ctx, vae, n: int, d: int, h: int, w: int):
+        TrainProgram.__init__(self, ctx)
+        self.vae = vae
+        self.n, self.d, self.h, self.w = n, d, h, w          # (h, w: the LATENT plane)
+        dec = vae.decoder
+        self.sf = sf = float(vae.scaling_factor)
+        self.tape = []
+        self.grads: Dict[int, torch.Tensor] = {}
+        self._need = dict(wgrad=16, gn=16, chsum=16, thin=16)
+        self._ws: Dict[str, Optional[torch.Tensor]] = dict(wgrad=None, gn=None, chsum=None, thin=None)
+        self.params = list(dec.parameters())
+        self.track_module(dec)
+        norms = [m for m in dec.modules() if isinstance(m, torch.nn.GroupNorm)]
+        # (the arena holds nothing but the dgamma / dbeta rows ctsi_gn_bwd insists on writing)
+        self._garena = self.persistent((sum(2 * ((m.num_channels + 63) // 64 * 64) for m in norms),), torch.float32, zero=True)
+        self._garena_used = 0
+        self.use_thin = False
+        lib, sptr, prog = self.lib, ctx.sptr, self
+        L = self.L = vae.latent_dim
+        self.hl, self.wl = h, w
+        vox_l = d * h * w
+        self.zin = Act(self.persistent((n * vox_l * L,), torch.bfloat16, zero=True), n, L, d, h, w)
+        self.g_z = self.persistent((n, L, d, h, w), torch.float32)
+        self.zero_gn_op()
+
+        def seam_bwd():       # runs after post_quant's data gradient wrote zin.grad = (W_p / sf)^T du = dL/dz, bf16 NDHWC
+            zg = prog.zin.grad
+
+            def run_gz():
+                lib.ndhwc_bf16_to_ncdhw_f32(zg.ip, _ptr(prog.g_z), n, L, d, h, w, sptr)
+
+            prog._emit(run_gz, "seam.grad_z")      # (a layout turn and a widening cast: exact, no audit record)
+            prog.release(zg)
+            prog.zin.grad = None
+
+        self.tape.append(seam_bwd)
+        pq = dec.post_quant_conv
+        pq_w = lambda: pq.weight * (1.0 / sf)
+        u = self.v_conv("dec.post_quant", pq, self.zin, weight_fn=pq_w, k=(1, 1, 1), cin_w=L, dgrad_weight_fn=pq_w)
+        x = self.conv_gn_act("dec.conv_in", dec.conv_in, u)
+        for m in dec.mid:
+            x = self.block(m, x)
+        x = self.block(dec.up2_upsample, x)
+        for m in dec.up2_res:
+            x = self.block(m, x)
+        x = self.block(dec.up3_upsample, x)
+        for m in dec.up3_res:
+            x = self.block(m, x)
+        co = self.co = dec.conv_out.out_channels
+        ho, wo = self.ho, self.wo = x.h, x.w
+        vox = d * ho * wo
+        self.recon = self.persistent((n, co, d, ho, wo), torch.float32)
+        self.d_head = Act(self.persistent((n * vox * _pad8(co),), torch.bfloat16, zero=True), n, _pad8(co), d, ho, wo)
+        self.v_conv("dec.conv_out", dec.conv_out, x, f32_out=self.recon, f32_strides=(co * vox, vox, ho * wo, wo, 1), act=1,
+                    gy=self.d_head)
+        self.n_fwd = len(self.ops)
+        self.generation = 0
+
+        # ---- backward: head, then the tape in reverse ----------------------------------------------------------------------
+        self.g_recon = self.persistent(tuple(self.recon.shape), torch.float32, zero=True)
+        hp = self.d_head
+
+        def run_head():
+            lib.vae_head_grad(_ptr(prog.g_recon), _ptr(prog.recon), n, co, d, ho, wo, 1.0, 0, hp.ip, hp.c, sptr)
+
+        self._emit(run_head, "head.grad", audit=dict(kind="head_grad", mode=0, g=self.g_recon, y=self.recon, scale=1.0, out=hp,
+                                                     active=None))
+        for fn in reversed(self.tape):
+            fn()
+        self.finalize_layout()
+        for key, need in self._need.items():
+            self._ws[key] = torch.empty(need, dtype=torch.uint8, device=ctx.device)
+
+    def needs_rebuild(self) -> bool:
+        cur = list(self.vae.decoder.parameters())
+        return len(cur) != len(self.params) or any(a is not b for a, b in zip(cur, self.params))
+
+    def run_forward(self, z: torch.Tensor) -> torch.Tensor:
+        """Forward launches; overwrites the saved activations (the generation counter makes a backward of an earlier forward
+        of this shape fail loudly)."""
+        self.ensure_fresh()
+        self.generation += 1
+        zz = z.detach().to(device=self.ctx.device, dtype=torch.float32).contiguous()
+        self.lib.ncdhw_f32_to_ndhwc_bf16(_ptr(zz), self.zin.ip, self.n, self.L, self.d, self.h, self.w, self.L, 0, self.ctx.sptr)
+        zz.record_stream(self.ctx.stream)
+        for op in self.ops[:self.n_fwd]:
+            op()
+        recon = self.recon.clone()
+        self.check_errors()
+        return recon
+
+    def run_backward(self, grad_recon: torch.Tensor, generation: Optional[int] = None) -> torch.Tensor:
+        if generation is not None and generation != self.generation:
+            raise CtsiError(
+                "backward of a differentiable decode whose saved activations were overwritten: another decode_with_grad of the "
+                f"same shape ran on this program in between (tape generation {generation}, now {self.generation}).  Call "
+                "backward() before the next decode_with_grad of that shape, or decode the second latent under torch.no_grad().")
+        self.g_recon.copy_(grad_recon.reshape(self.g_recon.shape))
+        for op in self.ops[self.n_fwd:]:
+            op()
+        self.check_errors()
+        return self.g_z.clone()
+
+
+class _VAEDecodeGrad(torch.autograd.Function):
+    """recon = decode(z); backward runs the data-gradient launches and returns dL/dz.  No parameter is an input."""
+
+    @staticmethod
+    def forward(fctx, prog: VAEDecodeGradProgram, z):
+        with prog.ctx.scope():
+            recon = prog.run_forward(z)
+        fctx.prog = prog
+        fctx.generation = prog.generation
+        fctx.z_dtype = z.dtype
+        return recon
+
+    @staticmethod
+    def backward(fctx, grad_recon):
+        prog = fctx.prog
+        with prog.ctx.scope():
+            g_z = prog.run_backward(grad_recon, fctx.generation)
+        return None, g_z.to(fctx.z_dtype)
+
+
+def vae_decode_grad_step(prog: VAEDecodeGradProgram, z: torch.Tensor) -> torch.Tensor:
+    return _VAEDecodeGrad.apply(prog, z)
