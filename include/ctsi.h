@@ -825,6 +825,32 @@ int ctsi_stream_wait_event(void* stream, ctsi_event* ev);
 int ctsi_event_elapsed_ms(ctsi_event* start, ctsi_event* stop, float* ms);
 void ctsi_event_destroy(ctsi_event* ev);
 
+/* Data consistency along depth (csrc/depth_consistency.hip).  x is a thin fp32 NCDHW volume of d_out
+ * slices, y the acquired thick one of d_in slices; planes = N C, hw = H W, a column is the depth vector at one (plane,
+ * position).  W [d_in][d_out] fp32 is the slice profile (rows sum to 1), P [d_out][d_in] fp32 = W^T (W W^T)^-1; band /
+ * band_w [d_in][2] and band_p [d_out][2] (int32) hold the first and last non-zero column of each row of W and of P.
+ * ctsi_depth_measure: y_out = W x.  ctsi_depth_measure_adj: g_x = scale W^T g_y (accumulate == 0) or g_x += ... (!= 0).
+ * ctsi_depth_project: in place, `iters` times x <- x + P (y - W x) with x <- clamp(x, clamp_lo, clamp_hi) between
+ *   iterations; after the last iteration the clamp is applied only when clamp_mode == 2.  clamp_mode 0: no clamp; 1: clamp
+ *   between iterations, ending on a projection (exactly consistent, may leave the range); 2: ending on a clamp (in range,
+ *   approximately consistent).  One block stages a tile of whole columns in LDS: x is read once and written once whatever
+ *   iters is.  partials (may be NULL): 5 fp64 values per slot, ctsi_depth_project_blocks(planes, hw) slots (one per 32
+ *   positions of a plane: the count does not depend on the depths), every slot written by one block.
+ * ctsi_depth_project_finalize: one block per plane folds its slots in index order into stats[5 plane ..] = { sum r^2 before,
+ *   sum r^2 after, max |r| before, max |r| after, number of clamped voxels (every clamp application counts) }, r = y - W x
+ *   evaluated in fp64 on the kernel's fp32 input / output values.  No atomics: the same bits on every run.
+ * Limits d_in <= 64, d_out <= 512.  Null pointers, non-positive sizes, iters < 1, clamp_lo > clamp_hi, a bad clamp_mode and
+ * depths over the limits return CTSI_ERR_INVALID before any launch.  Capture-safe: no allocation, no synchronisation. */
+int ctsi_depth_measure(const float* x, const float* W, const int* band, float* y_out, int planes, int d_in, int d_out,
+                       int hw, void* stream);
+int ctsi_depth_measure_adj(const float* g_y, const float* W, const int* band, float* g_x, float scale, int accumulate,
+                           int planes, int d_in, int d_out, int hw, void* stream);
+int ctsi_depth_project(float* x, const float* y, const float* W, const float* P, const int* band_w, const int* band_p,
+                       int iters, float clamp_lo, float clamp_hi, int clamp_mode, double* partials, int planes, int d_in,
+                       int d_out, int hw, void* stream);
+int ctsi_depth_project_blocks(int planes, int hw);
+int ctsi_depth_project_finalize(const double* partials, double* stats, int planes, int hw, int d_in, void* stream);
+
 /* depth-sharding collectives (RCCL over xGMI, one process per GPU) --------------------------- *
  * a volume's depth is cut into `world` slabs; before a depth-3 conv a slab needs one boundary
  * slice of each depth neighbour (models/unet3d.py:56,96,204-207,218-221; models/vae.py:27,65-69,86-90), GroupNorm needs

@@ -6,3 +6,4 @@ _m = importlib.import_module("video-to-video-diffusion_amd.metrics")
 calculate_psnr = _m.calculate_psnr
 calculate_ssim = _m.calculate_ssim
 calculate_video_metrics = _m.calculate_video_metrics
+measurement_residual = _m.measurement_residual

@@ -234,6 +234,11 @@ SIGNATURES = {
                              True),
     "ctsi_z0_pred": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp], True),
     "ctsi_loss_bwd_z0": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp], True),
+    "ctsi_depth_measure": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], True),
+    "ctsi_depth_measure_adj": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_depth_project": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _i, _vp, _i, _i, _i, _i, _vp], True),
+    "ctsi_depth_project_blocks": (_i, [_i, _i], False),
+    "ctsi_depth_project_finalize": (_i, [_vp, _vp, _i, _i, _i, _vp], True),
     "ctsi_graph_begin_capture": (_i, [_vp], True),
     "ctsi_graph_end_capture": (_i, [_vp, C.POINTER(_vp)], True),
     "ctsi_graph_launch": (_i, [_vp, _vp], True),

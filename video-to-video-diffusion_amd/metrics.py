@@ -83,3 +83,17 @@ def calculate_video_metrics(video1, video2, max_val=1.0) -> Dict[str, object]:
     return {'psnr': float(np.mean(psnr_values)) if psnr_values else 0.0,
             'ssim': float(np.mean(ssim_values)) if ssim_values else 0.0,
             'psnr_per_frame': psnr_values, 'ssim_per_frame': ssim_values}
+
+
+def measurement_residual(volume, thick, profile) -> Dict[str, List[float]]:
+    """How far a thin volume is from reproducing the thick acquisition: W volume (consistency.SliceProfile.measure, on the
+    device) against `thick`, per thick slice over (B, C, H, W).  {'rmse': [d_in floats], 'psnr': [d_in floats]}, PSNR in dB at
+    data range 2.0 (volumes in [-1, 1]), inf for a slice that is reproduced exactly."""
+    v, y = _as_device_f32(volume), _as_device_f32(thick)
+    if v.dim() != 5 or y.dim() != 5 or v.shape[2] != profile.d_out or y.shape[2] != profile.d_in \
+            or v.shape[:2] != y.shape[:2] or v.shape[3:] != y.shape[3:]:
+        raise ValueError(f"expected (B,C,{profile.d_out},H,W) and (B,C,{profile.d_in},H,W) tensors, got {tuple(v.shape)} "
+                         f"and {tuple(y.shape)}")
+    st = _slice_stats(profile.measure(v).detach(), y, 1, 2.0)
+    rmse = [math.sqrt(max(float(r[0]), 0.0)) for r in st]
+    return {'rmse': rmse, 'psnr': [20.0 * math.log10(2.0 / e) if e > 0.0 else float("inf") for e in rmse]}

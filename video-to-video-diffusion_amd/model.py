@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .consistency import check_data_consistency, data_consistency_from_config, refuse_depth_sharding
 from .diffusion import GaussianDiffusion
 from .engine import Ctx, check_attention_mode, nan_to_num_, trilinear_depth
 from .engine_f32 import check_precision
@@ -75,6 +76,10 @@ class VideoToVideoDiffusion(nn.Module):
                 raise ValueError(f"image_loss must be None or a callable (pred, target, diffusion_loss, "
                                  f"compute_auxiliary=True) -> (total, dict), got {type(value).__name__}")
             self.__dict__["image_loss"] = value
+            return
+        # `data_consistency` is a plain attribute too: never a submodule, never in the state dict
+        if name == "data_consistency":
+            self.__dict__["data_consistency"] = check_data_consistency(value)
             return
         super().__setattr__(name, value)
 
@@ -160,6 +165,10 @@ class VideoToVideoDiffusion(nn.Module):
         # with CombinedLoss.forward's signature -- and the SNR gate of the rows that take part.  From the config only when its
         # `losses:` section says `apply_image_losses: true`.
         self.image_loss, self.image_loss_min_snr = image_loss_from_config(config)
+        # data consistency of generate(), a plain attribute: None (default) or a consistency.DataConsistency.
+        # From the config only when its additive `data_consistency:` section says `enabled: true`.
+        self.data_consistency = data_consistency_from_config(config)
+        self._consistency_warned = False
 
     def set_inference_precision(self, precision):
         """'bf16' (default), 'fp32' or 'bf16x3' (fp32 tensors, split-bf16 MFMA convolutions: engine_x3.py): sets `unet.inference_precision` and `vae.inference_precision`, i.e. the arithmetic
@@ -259,7 +268,10 @@ class VideoToVideoDiffusion(nn.Module):
         (sampler.DPMSolverSampler), e.g. 20 steps in place of DDIM-50, and 'heun' (additive): EDM Heun with
         `num_inference_steps` steps on Karras sigmas, 2 N - 1 U-Net evaluations (sampler.HeunSampler).
         `precision` (additive, default None = the models' `inference_precision` attributes): 'bf16', 'fp32' or 'bf16x3' for this
-        call only; the attributes are restored afterwards."""
+        call only; the attributes are restored afterwards.
+        With `self.data_consistency` set (a consistency.DataConsistency; default None: the launches and bits of a model without it) and a
+        `target_depth` that changes the depth, the decoded, sanitised volume is projected onto the sanitised `v_in` as the last
+        device step; when the depth does not change the attribute has no effect and one warning says so."""
         check_guidance(guidance_scale, guidance_rescale)
         if precision is not None:
             check_precision(precision)
@@ -272,6 +284,12 @@ class VideoToVideoDiffusion(nn.Module):
                 self.unet.inference_precision, self.vae.inference_precision = saved
         if sampler not in SAMPLERS:
             raise ValueError(f"Unknown sampler: {sampler}")
+        dc = self.data_consistency
+        if dc is not None:      # what the projection refuses is refused before any work
+            refuse_depth_sharding(self.unet, self.vae)
+            if target_depth is not None and int(target_depth) < int(v_in.shape[2]):
+                raise ValueError(f"data_consistency: target_depth={int(target_depth)} is below the {int(v_in.shape[2])} input "
+                                 f"slices; a slice profile maps thin slices onto fewer thick ones")
         if not v_in.is_cuda:
             raise CtsiError("generate runs on the HIP engine: move the input to a ROCm device")
         device = v_in.device
@@ -296,6 +314,13 @@ class VideoToVideoDiffusion(nn.Module):
         v_out = self.vae.decode(z_0)
         with ctx.scope():
             nan_to_num_(ctx, v_out)
+        if dc is not None:
+            if v_out.shape[2] != v_in.shape[2]:
+                dc.project_(v_out, v_in)
+            elif not self._consistency_warned:
+                self._consistency_warned = True
+                logger.warning("data_consistency is set but generate() keeps the depth (%d slices): there is nothing to "
+                               "project, the attribute has no effect", int(v_in.shape[2]))
         return v_out
 
     def save_checkpoint(self, path, optimizer=None, scheduler=None, scaler=None, epoch=None, global_step=None,

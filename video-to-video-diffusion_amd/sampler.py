@@ -22,6 +22,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .consistency import check_data_consistency, refuse_depth_sharding
 from .engine import (Ctx, UNetProgram, _ptr, check_attention_mode, check_device_errors,
                      check_resblock_options_unsharded, nan_to_num_, sampler_step_launcher, sampler_step_row, trilinear_depth)
 from .engine_f32 import check_precision
@@ -784,6 +785,9 @@ class _Sampler:
         self.diffusion = diffusion
         self.model = model
         self.timesteps = diffusion.timesteps
+        # plain attribute: None or a consistency.DataConsistency; sample_with_stitching then projects the
+        # full blended volume onto `v_thick_full` once (blending overlapping windows does not keep per-window consistency)
+        self.data_consistency = None
 
     def _get_timesteps(self, num_inference_steps):
         """arange(0, T, T // N) plus T-1 when the stride misses it, descending — N+1 entries whenever
@@ -1086,6 +1090,31 @@ def _auto_window_batch(ctx, vae, b, td, th, tw, nwin, guided=False) -> int:
     return max(1, min(nwin, int(0.2 * total / per_window)))
 
 
+def _stitch_consistency(sampler, vae, patch_size, target_patch_size):
+    """The sampler's `data_consistency` attribute, checked before anything is sampled: ValueError for a wrong type or a target
+    patch shallower than the thick one, CtsiError under depth sharding."""
+    dc = check_data_consistency(getattr(sampler, "data_consistency", None))
+    if dc is not None:
+        refuse_depth_sharding(getattr(sampler, "model", None), vae)
+        if target_patch_size[0] < patch_size[0]:
+            raise ValueError(f"data_consistency: target patch depth {target_patch_size[0]} is below the thick patch depth "
+                             f"{patch_size[0]}; a slice profile maps thin slices onto fewer thick ones")
+    return dc
+
+
+def _consistent(sampler, dc, volume: torch.Tensor, v_thick_full: torch.Tensor) -> torch.Tensor:
+    """The full stitched volume projected once onto the thick volume, with the profile of the full depths."""
+    if dc is None:
+        return volume
+    if volume.shape[2] == v_thick_full.shape[2]:
+        if not getattr(sampler, "_consistency_warned", False):      # once per sampler object, as generate() does per model
+            sampler._consistency_warned = True
+            logger.warning("data_consistency is set but the stitched volume keeps the depth (%d slices): there is nothing "
+                           "to project, the attribute has no effect", int(volume.shape[2]))
+        return volume
+    return dc.project_(volume.contiguous(), v_thick_full.float())
+
+
 def _stitched(sampler, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress, sample_fn,
               batched_fn=None, window_batch=1, dp_group=None, guided=False):
     """Sliding-window inference (sampler.py:63-172, 338-453): per window encode -> sample -> decode on the
@@ -1104,6 +1133,7 @@ def _stitched(sampler, v_thick_full, vae, patch_size, target_patch_size, stride,
     windows are data-parallel units (parallel.shard_units): every rank of the group must call with the same volume,
     blends its share, and the accumulators are all-reduced over that group before normalisation.  It cannot be
     combined with depth sharding (`unet.depth_shard_comm`): there every rank must run the same window."""
+    dc = _stitch_consistency(sampler, vae, patch_size, target_patch_size)
     b, c, d_thick, hf, wf = v_thick_full.shape
     pd, ph, pw = patch_size
     td, th, tw = target_patch_size
@@ -1162,7 +1192,7 @@ def _stitched(sampler, v_thick_full, vae, patch_size, target_patch_size, stride,
         dist.all_reduce(wsum, group=pg)
     with ctx.scope():
         lib.blend_normalize(_ptr(acc), _ptr(wsum), acc.numel(), sptr)
-    return acc
+    return _consistent(sampler, dc, acc, v_thick_full)
 
 
 def _stitched_fused(sampler, v_thick_full, vae, patch_size, target_patch_size, stride, device, progress, plan_args, decode,
@@ -1175,6 +1205,7 @@ def _stitched_fused(sampler, v_thick_full, vae, patch_size, target_patch_size, s
     should only ever see training-size inputs.  All windows are one network batch: there is no chunking, and a volume whose
     window batch does not fit raises torch's out-of-memory error."""
     check_fusable(sampler.diffusion, sampler.model, plan_args["kind"], dp_group)
+    dc = _stitch_consistency(sampler, vae, patch_size, target_patch_size)
     window_batch = int(window_batch or 0)
     if decode == "full" and window_batch != 0:
         raise CtsiError(f"window_batch={window_batch} with decode='full': the fused latent is decoded in one piece and all "
@@ -1203,7 +1234,7 @@ def _stitched_fused(sampler, v_thick_full, vae, patch_size, target_patch_size, s
     z = run_sampler_fused(sampler.diffusion, sampler.model, (b, L) + geo.full, cond, geo.win, geo.starts, ctx.device,
                           guidance_scale=guidance[0], guidance_rescale=guidance[1], progress=progress, **plan_args)
     if decode == "full":
-        return vae.decode(z)
+        return _consistent(sampler, dc, vae.decode(z), v_thick_full)
     lib, sptr = ctx.lib, ctx.sptr
     d_thin = geo.full[0]
     acc = torch.zeros(b, c, d_thin, hf, wf, device=ctx.device)
@@ -1222,7 +1253,7 @@ def _stitched_fused(sampler, v_thick_full, vae, patch_size, target_patch_size, s
                                      d_thin, hf, wf, sd, sh * f, sw * f, sptr)
     with ctx.scope():
         lib.blend_normalize(_ptr(acc), _ptr(wsum), acc.numel(), sptr)
-    return acc
+    return _consistent(sampler, dc, acc, v_thick_full)
 
 
 class EDMSampler:
