@@ -851,6 +851,32 @@ int ctsi_depth_project(float* x, const float* y, const float* W, const float* P,
 int ctsi_depth_project_blocks(int planes, int hw);
 int ctsi_depth_project_finalize(const double* partials, double* stats, int planes, int hw, int d_in, void* stream);
 
+/* Ensemble statistics (csrc/ensemble.hip): per-voxel mean and spread over the members of an ensemble of
+ * fp32 volumes, kept as a running state so that memory does not grow with the number of members.
+ * ctsi_ensemble_accumulate: x holds `rows` members of `count` contiguous values each; (mean, m2) [count] is the state over the
+ *   `seen` members folded in before.  Per element the state is read once, the sequential Welford recurrence runs over the
+ *   rows in order (k = seen + r + 1, d = x - mean, mean += d / k, m2 += d (x - mean), every operation rounded on its own) and
+ *   the state is written once.  seen == 0: the state is NOT read (no memset before the first call) and member 1 sets
+ *   mean = x, m2 = 0.  Any split of the members over calls gives the same bits.  Traffic (rows + 4) * 4 bytes per element,
+ *   (rows + 2) * 4 on the first call.  16-byte accesses when x, its rows, mean and m2 reach a 16-byte boundary after the same
+ *   number of leading elements, else 8-byte or scalar ones.
+ * ctsi_ensemble_finalize: std = sqrt(max(m2, 0) / (members - (unbiased != 0))), exactly 0 when members == 1, written to a buffer
+ *   of its own (the state stays valid: more members may follow), and stats[planes][3] (fp64) = { sum std, sum std^2, max std }
+ *   over each plane of `plane` consecutive voxels.  partials: 4 fp64 values per slot, ctsi_ensemble_blocks(planes, plane)
+ *   slots (one per 4096 voxels of a plane; 0 for sizes that are invalid), every slot written by one block; a second launch
+ *   folds each plane's slots in index order.
+ * ctsi_ensemble_calibration: stats[planes][4] (fp64) = { sum (mean - target)^2, sum std^2, #(|mean - target| <= std),
+ *   #(|mean - target| <= 2 std) } per plane, decided in fp64 on the fp32 values; partials as above.
+ * Null pointers, pointers that are not 4-byte aligned, rows < 1, count < 1, seen < 0, seen + rows > INT_MAX, members < 1,
+ * planes < 1 and plane < 1 return CTSI_ERR_INVALID before any launch.  Capture-safe: no allocation, no synchronisation, no
+ * atomics; the same bits on every run. */
+int ctsi_ensemble_accumulate(const float* x, int rows, long long count, int seen, float* mean, float* m2, void* stream);
+int ctsi_ensemble_blocks(int planes, long long plane);
+int ctsi_ensemble_finalize(const float* m2, float* std_out, int members, int unbiased, int planes, long long plane,
+                           double* partials, double* stats, void* stream);
+int ctsi_ensemble_calibration(const float* mean, const float* std_in, const float* target, int planes, long long plane,
+                              double* partials, double* stats, void* stream);
+
 /* depth-sharding collectives (RCCL over xGMI, one process per GPU) --------------------------- *
  * a volume's depth is cut into `world` slabs; before a depth-3 conv a slab needs one boundary
  * slice of each depth neighbour (models/unet3d.py:56,96,204-207,218-221; models/vae.py:27,65-69,86-90), GroupNorm needs

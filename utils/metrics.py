@@ -7,3 +7,4 @@ calculate_psnr = _m.calculate_psnr
 calculate_ssim = _m.calculate_ssim
 calculate_video_metrics = _m.calculate_video_metrics
 measurement_residual = _m.measurement_residual
+ensemble_calibration = _m.ensemble_calibration

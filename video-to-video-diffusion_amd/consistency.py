@@ -279,8 +279,12 @@ def data_consistency_from_config(config) -> Optional[DataConsistency]:
                            clamp=tuple(clamp) if isinstance(clamp, list) else clamp, final=sec.get("final", "project"))
 
 
-def refuse_depth_sharding(*modules):
-    """Data consistency refuses depth-sharded generation: a column spans ranks."""
+def refuse_depth_sharding(*modules, feature=None):
+    """Data consistency refuses depth-sharded generation: a column spans ranks.  `feature` names another caller that needs
+    whole volumes on one rank (generate_ensemble) in the message."""
     if any(getattr(m, "depth_shard_comm", None) is not None for m in modules if m is not None):
+        if feature is not None:
+            raise CtsiError(f"{feature} does not support depth sharding (depth_shard_comm): each rank holds a depth slab, "
+                            f"not a volume; drop the communicator")
         raise CtsiError("data_consistency does not support depth sharding (depth_shard_comm): a depth column spans ranks and "
                         "the projection needs whole columns; drop the communicator or set data_consistency = None")

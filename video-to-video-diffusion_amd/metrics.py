@@ -97,3 +97,40 @@ def measurement_residual(volume, thick, profile) -> Dict[str, List[float]]:
     st = _slice_stats(profile.measure(v).detach(), y, 1, 2.0)
     rmse = [math.sqrt(max(float(r[0]), 0.0)) for r in st]
     return {'rmse': rmse, 'psnr': [20.0 * math.log10(2.0 / e) if e > 0.0 else float("inf") for e in rmse]}
+
+
+def ensemble_calibration(mean, std, target) -> Dict[str, object]:
+    """Can the std map of an ensemble (ensemble.EnsembleResult) be trusted?  (N, C, D, H, W) tensors `mean`, `std` and the
+    ground truth `target`; one HIP pass (ctsi_ensemble_calibration) gives per output slice the squared error, the predicted
+    variance and how many voxels lie within one and two std of the truth.  Returns, overall and per slice over (N, C, H, W),
+    {'rmse', 'rms_std', 'spread_skill' (rms_std / rmse; inf when the error is 0 and the spread is not, nan when both are 0),
+    'coverage_1sigma', 'coverage_2sigma'} and the same five as lists of D floats under 'per_slice'.  A calibrated Gaussian
+    ensemble gives about 1, 0.68 and 0.95."""
+    for name, t in (("mean", mean), ("std", std), ("target", target)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 5:
+            raise ValueError(f"ensemble_calibration: {name} must be a (N, C, D, H, W) tensor")
+    if not (tuple(mean.shape) == tuple(std.shape) == tuple(target.shape)) or mean.numel() == 0:
+        raise ValueError(f"ensemble_calibration: shapes differ or are empty: mean {tuple(mean.shape)}, std {tuple(std.shape)}, "
+                         f"target {tuple(target.shape)}")
+    m, s, t = _as_device_f32(mean), _as_device_f32(std), _as_device_f32(target)
+    n, c, d, h, w = m.shape
+    planes, plane = n * c * d, h * w
+    ctx = Ctx.get(m.device)
+    with ctx.scope():
+        partials = torch.empty(ctx.lib.ensemble_blocks(planes, plane) * 4, dtype=torch.float64, device=m.device)
+        table = torch.empty((planes, 4), dtype=torch.float64, device=m.device)
+        ctx.lib.ensemble_calibration(_ptr(m), _ptr(s), _ptr(t), planes, plane, _ptr(partials), _ptr(table), ctx.sptr)
+    for x in (m, s, t):
+        x.record_stream(ctx.stream)
+    per = table.cpu().numpy().reshape(n * c, d, 4).sum(axis=0)        # (d, 4), float64
+
+    def summary(row, voxels):
+        rmse, rms_std = math.sqrt(row[0] / voxels), math.sqrt(row[1] / voxels)
+        skill = rms_std / rmse if rmse > 0.0 else (float("inf") if rms_std > 0.0 else float("nan"))
+        return rmse, rms_std, skill, float(row[2] / voxels), float(row[3] / voxels)
+
+    keys = ('rmse', 'rms_std', 'spread_skill', 'coverage_1sigma', 'coverage_2sigma')
+    out = dict(zip(keys, summary(per.sum(axis=0), float(n * c * d * plane))))
+    rows = [summary(per[j], float(n * c * plane)) for j in range(d)]
+    out['per_slice'] = {k: [r[i] for r in rows] for i, k in enumerate(keys)}
+    return out

@@ -294,6 +294,24 @@ class VideoToVideoDiffusion(nn.Module):
             raise CtsiError("generate runs on the HIP engine: move the input to a ROCm device")
         device = v_in.device
         ctx = Ctx.get(device)
+        v_in, z_cond = self._encode_conditioning(ctx, v_in, target_depth)
+        latent_shape = tuple(z_cond.shape)
+        if noise_fn is None:
+            torch.randn(latent_shape, device=device)  # model.py:303 draws (and discards) one latent
+        z_0 = SAMPLERS[sampler](self.diffusion, self.unet, latent_shape, z_cond, num_inference_steps, device,
+                                noise_fn=noise_fn, guidance_scale=guidance_scale,
+                                guidance_rescale=guidance_rescale)
+        v_out = self._decode_sanitised(ctx, z_0)
+        if dc is not None:
+            if v_out.shape[2] != v_in.shape[2]:
+                dc.project_(v_out, v_in)
+            else:
+                self._warn_consistency_without_depth_change(v_in)
+        return v_out
+
+    def _encode_conditioning(self, ctx, v_in, target_depth):
+        """The head of generate() and generate_ensemble(): (sanitised fp32 v_in, conditioning latent) -- VAE encode, then the
+        trilinear depth upsample when `target_depth` is given, with the nan_to_num guards on the device."""
         v_in = torch.nan_to_num(v_in.float(), nan=0.0)
         z_in = self.vae.encode(v_in)
         with ctx.scope():
@@ -303,25 +321,50 @@ class VideoToVideoDiffusion(nn.Module):
                 nan_to_num_(ctx, z_cond)
             else:
                 z_cond = z_in
-        latent_shape = tuple(z_cond.shape)
-        if noise_fn is None:
-            torch.randn(latent_shape, device=device)  # model.py:303 draws (and discards) one latent
-        z_0 = SAMPLERS[sampler](self.diffusion, self.unet, latent_shape, z_cond, num_inference_steps, device,
-                                noise_fn=noise_fn, guidance_scale=guidance_scale,
-                                guidance_rescale=guidance_rescale)
+        return v_in, z_cond
+
+    def _decode_sanitised(self, ctx, z_0):
+        """The tail of generate() and generate_ensemble(): nan_to_num on the sampled latent (in place), VAE decode, nan_to_num."""
         with ctx.scope():
             nan_to_num_(ctx, z_0)
         v_out = self.vae.decode(z_0)
         with ctx.scope():
             nan_to_num_(ctx, v_out)
-        if dc is not None:
-            if v_out.shape[2] != v_in.shape[2]:
-                dc.project_(v_out, v_in)
-            elif not self._consistency_warned:
-                self._consistency_warned = True
-                logger.warning("data_consistency is set but generate() keeps the depth (%d slices): there is nothing to "
-                               "project, the attribute has no effect", int(v_in.shape[2]))
         return v_out
+
+    def _warn_consistency_without_depth_change(self, v_in):
+        if not self._consistency_warned:
+            self._consistency_warned = True
+            logger.warning("data_consistency is set but generate() keeps the depth (%d slices): there is nothing to "
+                           "project, the attribute has no effect", int(v_in.shape[2]))
+
+    @torch.no_grad()
+    def generate_ensemble(self, v_in, sampler, num_inference_steps=20, num_members=8, guidance_scale=1.0, target_depth=None,
+                          member_noise_fn=None, precision=None, guidance_rescale=0.0, member_batch=None, keep_members=False):
+        """`num_members` draws of generate() folded into per-voxel statistics: an ensemble.EnsembleResult
+        with the mean (the MMSE estimate), the standard deviation (unbiased; 0 for one member), the per-slice uncertainty
+        profile `slice_std` and, with `keep_members=True`, the decoded members (K, N, C, D, H, W).
+
+        `v_in` is sanitised and encoded and the conditioning is depth-upsampled ONCE.  The members are sampled `member_batch` at
+        a time as rows of one sampler call -- shape (m N, L, d, h, w), the conditioning rows repeated, member-major (row
+        k N + b) -- so guidance, v-prediction, the x0 form, learn_sigma, every sampler and the three precisions are the
+        existing batch path.  They are decoded in groups; each group is sanitised, projected when `self.data_consistency` is
+        set and the depth changes (a mean of consistent members is consistent), and folded into the running statistics by
+        one streaming pass (ensemble.EnsembleAccumulator), so memory does not grow with `num_members`.  The default
+        `member_batch` and the decode group follow sample_with_stitching's memory rule on the TOTAL device memory.
+
+        Noise: `member_noise_fn(k, i, shape)` returns member k's noise of shape (N, L, d, h, w), i = -1 for the initial draw
+        as with `noise_fn`; the result then depends on `member_batch` only through the batch-size dependence of the network
+        arithmetic.  Without it the draws come from torch's generator, once per batch of members after one drawn-and-discarded
+        latent: with `num_members=1` that is generate()'s RNG stream (one seed, the same bits); for more members the default
+        RNG makes the result depend on `member_batch`.
+
+        Checked before any work: `num_members` an int >= 1, `member_batch` None or an int >= 1 (ValueError), guidance,
+        precision and the sampler name as in generate(), a CPU input (CtsiError), depth sharding (CtsiError: each rank holds
+        a slab, not a volume)."""
+        from .ensemble import generate_ensemble
+        return generate_ensemble(self, v_in, sampler, num_inference_steps, num_members, guidance_scale, target_depth,
+                                 member_noise_fn, precision, guidance_rescale, member_batch, keep_members)
 
     def save_checkpoint(self, path, optimizer=None, scheduler=None, scaler=None, epoch=None, global_step=None,
                         current_phase=None, best_loss=None, **kwargs):
