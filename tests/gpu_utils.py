@@ -1,8 +1,11 @@
 """Helpers for the `-m gpu` tests: drive single libctsi ops through engine.Program."""
 import ctypes as C
 import importlib
+import os
 
 import torch
+
+from tests import fwd_audit as A
 
 E = importlib.import_module("video-to-video-diffusion_amd.engine")
 _ptr = E._ptr
@@ -30,9 +33,35 @@ def from_act(prog, a):
     return out
 
 
+_CONV64 = {}          # float64 conv references, shared by the kernel forms of one case (fwd_audit._conv64_shared)
+
+
+def audit_label(what=""):
+    """The running test's id (pytest sets PYTEST_CURRENT_TEST) [+ what]: the label of the printed audit rows."""
+    test = os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0].split("::", 1)[-1]
+    return f"{test} {what}".strip()
+
+
+def audit_program(prog, what=""):
+    """Run `prog` (laid out, inputs loaded) launch by launch under fwd_audit.audit_forward and require every row `ok` and every
+    launch accounted for.  Returns (rows, tol): `tol` is the per-element tolerance of the last bf16 conv output (fp32 NCDHW on
+    the cpu, None if there is none) -- two forms of one problem lie within tol_a + tol_b of each other."""
+    rows, missing = A.audit_forward(prog, keep_tol=True, conv_cache=_CONV64)
+    kernels = "+".join(m[2] for m, r in zip(prog.op_meta, prog.op_audit) if r is not None and r.get("kind") == "conv_fwd")
+    A.require_ok(audit_label(what or kernels), rows, missing)
+    tols = [r.pop("tol") for r in rows if "tol" in r]
+    return rows, (tols[-1].permute(0, 4, 1, 2, 3).contiguous().cpu() if tols else None)
+
+
+def within_tolerances(y, y2, tol, tol2):
+    """|y - y2| <= tol + tol2 per element: both lie within their tolerance of the same float64 reference."""
+    return bool(((y.double() - y2.double()).abs() <= tol + tol2).all())
+
+
 def run_conv(x1, x2, weight, bias, *, transposed=False, k=(3, 3, 3), s=(1, 1), p=(1, 1, 1), f32=False, act=0,
-             c1_pad=None, cin_w=None, want_stats=False, groups=None):
-    """Returns (y fp32 NCDHW on cpu, sums or None)."""
+             c1_pad=None, cin_w=None, want_stats=False, groups=None, audit=False):
+    """Returns (y fp32 NCDHW on cpu, sums or None).  `audit`: the program runs launch by launch under the forward audit
+    (`audit_program`), every row must be `ok`; returns (y, sums, tol) with tol as `audit_program` returns it."""
     c = ctx()
     with c.scope():
         prog = E.Program(c)
@@ -62,10 +91,15 @@ def run_conv(x1, x2, weight, bias, *, transposed=False, k=(3, 3, 3), s=(1, 1), p
             if want_stats:
                 slot = prog.gn_finalize(out_act, groups, st)
         prog.finalize_layout()
-        prog.run()
+        if audit:
+            _, tol = audit_program(prog)
+        else:
+            prog.run()
         res = y.clone() if f32 else from_act(prog, out_act)
         sums = None
         if slot is not None:
             sums = prog._gn_sums[slot:slot + out_act.n * groups * 2].clone().reshape(out_act.n, groups, 2)
     torch.cuda.synchronize()
+    if audit:
+        return res.cpu(), (sums.cpu() if sums is not None else None), tol
     return res.cpu(), (sums.cpu() if sums is not None else None)

@@ -1,7 +1,11 @@
 """GPU: every libctsi kernel family against the CPU oracle (torch.nn.functional fp32 on the same
 bf16-rounded operands).  Integer-free floating-point path: tolerances are stated per test.
 
- conv / convT      rel-L2 <= 3e-3   (fp32 accumulate of bf16 products; output rounded to bf16, 2^-9)
+ conv / convT      rel-L2 <= 3e-3   (fp32 accumulate of bf16 products; output rounded to bf16, 2^-9), and every conv launch
+                   under the forward audit (tests/fwd_audit.py through gpu_utils.run_conv(audit=True) / audit_program): each
+                   element within one bf16 ulp of float64 from the launch's own operands, the GroupNorm column sums and fp32
+                   outputs at F32_REL_L2 / F32_MAX_REL; two kernel forms of one problem within the sum of their per-element
+                   tolerances (tests/test_host_conv_op_audit.py shows what the first bound alone lets through)
  GroupNorm chain   rel-L2 <= 6e-3   (bf16 in, fp32 statistics, bf16 out)
  fp32-only ops     rel-L2 <= 1e-5   (time embedding, trilinear, sampler updates)
 """
@@ -80,7 +84,7 @@ def test_conv_family(G, name, c1, c2, cout, dims, kind):
         ref = F.conv_transpose3d(x, wt, b, stride=(1, 2, 2), padding=(1, 1, 1))
         kw = dict(k=(3, 4, 4), s=(2, 2), transposed=True)
     groups = 8 if cout % 8 == 0 and cout >= 8 else 1
-    y, sums = G.run_conv(x1, x2, wt, b, want_stats=True, groups=groups, **kw)
+    y, sums, _ = G.run_conv(x1, x2, wt, b, want_stats=True, groups=groups, audit=True, **kw)
     assert tuple(y.shape) == tuple(ref.shape)
     assert rel_l2(y, ref) < CONV_TOL, name
     assert float((y - ref).abs().max()) < 2e-2 * float(ref.abs().max())
@@ -98,14 +102,14 @@ def test_conv_tile_variants(G, tile, monkeypatch):
     x2 = bf16_round(formula_input((1, 64, 5, 12, 10), 2))
     wt = bf16_round(_w((256, 192, 3, 3, 3), 3))
     b = formula_input((256,), 4) * 0.1
-    y, sums = G.run_conv(x1, x2, wt, b, want_stats=True, groups=32)
+    y, sums, _ = G.run_conv(x1, x2, wt, b, want_stats=True, groups=32, audit=True)
     ref = F.conv3d(torch.cat([x1, x2], 1), wt, b, padding=1)
     assert rel_l2(y, ref) < CONV_TOL
     rg = ref.reshape(1, 32, -1).double()
     assert torch.allclose(sums[..., 0], rg.sum(-1), rtol=1e-3, atol=0.5)
     assert torch.allclose(sums[..., 1], (rg * rg).sum(-1), rtol=2e-3)
     wt_t = bf16_round(_w((128, 256, 3, 4, 4), 5, transposed=True))
-    yt, _ = G.run_conv(x1, None, wt_t, None, transposed=True, k=(3, 4, 4), s=(2, 2))
+    yt, _, _ = G.run_conv(x1, None, wt_t, None, transposed=True, k=(3, 4, 4), s=(2, 2), audit=True)
     assert rel_l2(yt, F.conv_transpose3d(x1, wt_t, None, stride=(1, 2, 2), padding=(1, 1, 1))) < CONV_TOL
 
 
@@ -159,15 +163,16 @@ def test_conv3_halo_tile_kernel(G, monkeypatch, name, c1, c2, cout, dims, tile):
     groups = 8
     for key, val in halo3_tile_env(tile).items():
         monkeypatch.setenv(key, val)
-    y, sums = G.run_conv(x1, x2, wt, b, want_stats=True, groups=groups)
+    y, sums, tol = G.run_conv(x1, x2, wt, b, want_stats=True, groups=groups, audit=True)
     assert rel_l2(y, ref) < CONV_TOL, name
     rg = ref.reshape(n, groups, -1).double()
     assert torch.allclose(sums[..., 0], rg.sum(-1), rtol=1e-3, atol=1e-2 * math.sqrt(rg.shape[-1]))
     assert torch.allclose(sums[..., 1], (rg * rg).sum(-1), rtol=2e-3)
     monkeypatch.delenv("CTSI_CONV_FORCE_HALO3")
     monkeypatch.setenv("CTSI_CONV_NO_HALO3", "1")
-    y2, _ = G.run_conv(x1, x2, wt, b)
+    y2, _, tol2 = G.run_conv(x1, x2, wt, b, audit=True)
     assert float((y - y2).abs().max()) <= 2.0 ** -7 * float(ref.abs().max())
+    assert G.within_tolerances(y, y2, tol, tol2)
 
 
 NARROW_CASES = [
@@ -205,14 +210,15 @@ def test_conv3_halo_k32_narrow_plane_tiles(G, monkeypatch, name, c1, c2, cout, d
         lib.conv_plan_config(plan, C.byref(pbm), C.byref(pbn), C.byref(mode))
         lib.conv_plan_destroy(plan)
         assert (pbm.value, mode.value) == (bm, 9), (pbm.value, mode.value)
-    y, sums = G.run_conv(x1, x2, wt, b, want_stats=True, groups=groups)
+    y, sums, tol = G.run_conv(x1, x2, wt, b, want_stats=True, groups=groups, audit=True)
     assert rel_l2(y, ref) < CONV_TOL, name
     rg = ref.reshape(n, groups, -1).double()
     assert torch.allclose(sums[..., 0], rg.sum(-1), rtol=1e-3, atol=1e-2 * math.sqrt(rg.shape[-1]))
     assert torch.allclose(sums[..., 1], (rg * rg).sum(-1), rtol=2e-3)
     monkeypatch.setenv("CTSI_CONV_K32_NARROW", "0")
-    y2, _ = G.run_conv(x1, x2, wt, b)
+    y2, _, tol2 = G.run_conv(x1, x2, wt, b, audit=True)
     assert float((y - y2).abs().max()) <= 2.0 ** -7 * float(ref.abs().max())
+    assert G.within_tolerances(y, y2, tol, tol2)
 
 
 @pytest.mark.parametrize("c1,c2,cout,dims", [(256, 0, 256, (2, 6, 8, 24)), (512, 0, 512, (2, 16, 12, 12)), (128, 128, 72, (1, 11, 10, 12))],
@@ -242,7 +248,7 @@ def test_narrow_plane_tiles_split_k(G, monkeypatch, c1, c2, cout, dims):
     lib.conv_plan_destroy(plan)
     assert (pbm.value, mode.value) == (384, 9) and ws > 0
     groups = 8
-    y, sums = G.run_conv(x1, x2, wt, b, want_stats=True, groups=groups)
+    y, sums, tol = G.run_conv(x1, x2, wt, b, want_stats=True, groups=groups, audit=True)
     assert rel_l2(y, ref) < CONV_TOL
     rg = ref.reshape(n, groups, -1).double()
     assert torch.allclose(sums[..., 0], rg.sum(-1), rtol=1e-3, atol=1e-2 * math.sqrt(rg.shape[-1]))
@@ -250,8 +256,9 @@ def test_narrow_plane_tiles_split_k(G, monkeypatch, c1, c2, cout, dims):
     y_again, sums_again = G.run_conv(x1, x2, wt, b, want_stats=True, groups=groups)
     assert torch.equal(y, y_again) and torch.equal(sums, sums_again)
     monkeypatch.setenv("CTSI_CONV_K32_NARROW_SK", "0")
-    y1, _ = G.run_conv(x1, x2, wt, b)
+    y1, _, tol1 = G.run_conv(x1, x2, wt, b, audit=True)
     assert float((y - y1).abs().max()) <= 2.0 ** -7 * float(ref.abs().max())
+    assert G.within_tolerances(y, y1, tol, tol1)
 
 
 @pytest.mark.parametrize("kind,cin,cout,dims", [("up", 128, 128, (1, 8, 8, 24)), ("up", 256, 128, (2, 16, 8, 12)),
@@ -272,11 +279,12 @@ def test_narrow_plane_tiles_transposed_and_strided_forms(G, monkeypatch, kind, c
         ref = F.conv3d(x, wt, b, stride=(1, 2, 2), padding=(1, 1, 1))
         kw = dict(k=(3, 4, 4), s=(2, 2))
     monkeypatch.setenv("CTSI_CONV_FORCE_HALO3", "1")
-    y, _ = G.run_conv(x, None, wt, b, **kw)
+    y, _, tol = G.run_conv(x, None, wt, b, audit=True, **kw)
     assert rel_l2(y, ref) < CONV_TOL
     monkeypatch.setenv("CTSI_CONV_K32_NARROW", "0")
-    y2, _ = G.run_conv(x, None, wt, b, **kw)
+    y2, _, tol2 = G.run_conv(x, None, wt, b, audit=True, **kw)
     assert float((y - y2).abs().max()) <= 2.0 ** -7 * float(ref.abs().max())
+    assert G.within_tolerances(y, y2, tol, tol2)
 
 
 @pytest.mark.parametrize("cout,dims", [(128, (1, 4, 16, 64)), (128, (2, 5, 11, 37)), (72, (1, 3, 9, 33)), (256, (1, 2, 8, 32))],
@@ -302,14 +310,15 @@ def test_one_channel_stem_conv(G, monkeypatch, cout, dims):
     lib.conv_plan_config(plan, C.byref(bm), C.byref(bn), C.byref(mode))
     lib.conv_plan_destroy(plan)
     assert mode.value == 11
-    y, sums = G.run_conv(x, None, wt, b, c1_pad=8, cin_w=1, want_stats=True, groups=groups)
+    y, sums, tol = G.run_conv(x, None, wt, b, c1_pad=8, cin_w=1, want_stats=True, groups=groups, audit=True)
     assert rel_l2(y, ref) < CONV_TOL
     rg = ref.reshape(n, groups, -1).double()
     assert torch.allclose(sums[..., 0], rg.sum(-1), rtol=1e-3, atol=1e-2 * math.sqrt(rg.shape[-1]))
     assert torch.allclose(sums[..., 1], (rg * rg).sum(-1), rtol=2e-3)
     monkeypatch.setenv("CTSI_CONV_NO_STEM", "1")
-    y2, _ = G.run_conv(x, None, wt, b, c1_pad=8, cin_w=1)
+    y2, _, tol2 = G.run_conv(x, None, wt, b, c1_pad=8, cin_w=1, audit=True)
     assert float((y - y2).abs().max()) <= 2.0 ** -7 * float(ref.abs().max())
+    assert G.within_tolerances(y, y2, tol, tol2)
 
 
 DOWN_CASES = [
@@ -355,7 +364,7 @@ def test_downsample_conv_on_halo_tile_kernel(G, monkeypatch, name, cin, cout, di
     lib.conv_plan_destroy(plan)
     assert mode.value == 9 and bm.value == (384 if "k3" in tile else 512)
     assert (ws > 0) == (tile == "16k3s" and cin % 32 == 0)
-    y, sums = G.run_conv(x, None, wt, b, k=(3, 4, 4), s=(2, 2), want_stats=True, groups=groups)
+    y, sums, tol = G.run_conv(x, None, wt, b, k=(3, 4, 4), s=(2, 2), want_stats=True, groups=groups, audit=True)
     assert tuple(y.shape) == tuple(ref.shape)
     assert rel_l2(y, ref) < CONV_TOL, name
     rg = ref.reshape(n, groups, -1).double()
@@ -363,8 +372,9 @@ def test_downsample_conv_on_halo_tile_kernel(G, monkeypatch, name, cin, cout, di
     assert torch.allclose(sums[..., 1], (rg * rg).sum(-1), rtol=2e-3)
     monkeypatch.delenv("CTSI_CONV_FORCE_HALO3")
     monkeypatch.setenv("CTSI_CONV_K32D", "0")
-    y2, _ = G.run_conv(x, None, wt, b, k=(3, 4, 4), s=(2, 2))
+    y2, _, tol2 = G.run_conv(x, None, wt, b, k=(3, 4, 4), s=(2, 2), audit=True)
     assert float((y - y2).abs().max()) <= 2.0 ** -7 * float(ref.abs().max())
+    assert G.within_tolerances(y, y2, tol, tol2)
     # exactness properties: a one-hot kernel tap copies the strided input; an all-ones kernel sums its window
     if tile == "32k" and cin <= 128:
         w1 = torch.zeros((cout, cin, 3, 4, 4))
@@ -372,7 +382,7 @@ def test_downsample_conv_on_halo_tile_kernel(G, monkeypatch, name, cin, cout, di
             w1[co, co, 1, 2, 1] = 1.0          # out[d, y, x] = in[d, 2y + 1, 2x]
         monkeypatch.delenv("CTSI_CONV_K32D")
         monkeypatch.setenv("CTSI_CONV_FORCE_HALO3", "1")
-        y3, _ = G.run_conv(x, None, w1, None, k=(3, 4, 4), s=(2, 2))
+        y3, _, _ = G.run_conv(x, None, w1, None, k=(3, 4, 4), s=(2, 2), audit=True)
         m = min(cout, cin)
         assert torch.equal(y3[:, :m], x[:, :m, :, 1::2, 0::2])
 
@@ -415,6 +425,7 @@ def test_gather_kernel_split_k(G, monkeypatch, name, c1, c2, cout, dims, k, forc
         slot = prog.gn_finalize(y, 8, st)
         prog.finalize_layout()
         assert prog.op_meta[0][2].endswith("s"), prog.op_meta[0][2]          # the split-K form was selected
+        _, tol = G.audit_program(prog)          # launch by launch against float64 (tests/fwd_audit.py); the runs below start afresh
         outs = []
         for _ in range(3):
             prog.run()
@@ -432,8 +443,9 @@ def test_gather_kernel_split_k(G, monkeypatch, name, c1, c2, cout, dims, k, forc
     assert torch.allclose(sums[..., 0], rg.sum(-1), rtol=1e-3, atol=1e-2 * math.sqrt(rg.shape[-1]))
     assert torch.allclose(sums[..., 1], (rg * rg).sum(-1), rtol=2e-3)
     monkeypatch.setenv("CTSI_CONV_GSPLIT", "0")
-    y0, _ = G.run_conv(x1, x2, wt, b, k=(k, k, k), p=(k // 2,) * 3)
+    y0, _, tol0 = G.run_conv(x1, x2, wt, b, k=(k, k, k), p=(k // 2,) * 3, audit=True)
     assert float((outs[0][0].cpu() - y0).abs().max()) <= 2.0 ** -7 * float(ref.abs().max())
+    assert G.within_tolerances(outs[0][0].cpu(), y0, tol, tol0)
     E.check_device_errors(c)
 
 
@@ -466,6 +478,7 @@ def test_split_k_conv_is_bit_stable_and_matches(G, monkeypatch):
         y, st = prog.conv("c", lambda: wt, lambda: b, a, None, cout=cout, want_stats=True)
         slot = prog.gn_finalize(y, 8, st)
         prog.finalize_layout()
+        G.audit_program(prog)                   # launch by launch against float64 (tests/fwd_audit.py); the runs below start afresh
         outs = []
         for _ in range(4):
             prog.run()
@@ -541,15 +554,16 @@ def test_conv_transpose_halo_tile_kernel(G, monkeypatch, name, cin, cout, dims, 
     lib.conv_plan_config(plan, None, None, C.byref(mode))
     lib.conv_plan_destroy(plan)
     assert mode.value == 9                                   # the halo-tile kernel, not the gather kernel
-    y, sums = G.run_conv(x, None, wt, b, transposed=True, k=(3, 4, 4), s=(2, 2), want_stats=True, groups=groups)
+    y, sums, tol = G.run_conv(x, None, wt, b, transposed=True, k=(3, 4, 4), s=(2, 2), want_stats=True, groups=groups, audit=True)
     assert tuple(y.shape) == tuple(ref.shape)
     assert rel_l2(y, ref) < CONV_TOL, name
     rg = ref.reshape(n, groups, -1).double()
     assert torch.allclose(sums[..., 0], rg.sum(-1), rtol=1e-3, atol=1e-2 * math.sqrt(rg.shape[-1]))
     assert torch.allclose(sums[..., 1], (rg * rg).sum(-1), rtol=2e-3)
     monkeypatch.setenv("CTSI_CONV_K32T", "0")
-    y2, _ = G.run_conv(x, None, wt, b, transposed=True, k=(3, 4, 4), s=(2, 2))
+    y2, _, tol2 = G.run_conv(x, None, wt, b, transposed=True, k=(3, 4, 4), s=(2, 2), audit=True)
     assert float((y - y2).abs().max()) <= 2.0 ** -7 * float(ref.abs().max())
+    assert G.within_tolerances(y, y2, tol, tol2)
 
 
 def test_conv_fp32_strided_output_tanh_and_padded_input(G):
@@ -557,16 +571,16 @@ def test_conv_fp32_strided_output_tanh_and_padded_input(G):
     x = bf16_round(formula_input((1, 128, 3, 6, 5), 5))
     wt = bf16_round(_w((1, 128, 3, 3, 3), 6))
     b = torch.tensor([0.05])
-    y, _ = G.run_conv(x, None, wt, b, f32=True, act=1)
+    y, _, _ = G.run_conv(x, None, wt, b, f32=True, act=1, audit=True)
     assert rel_l2(y, torch.tanh(F.conv3d(x, wt, b, padding=1))) < 2e-5 + 1e-4
     # U-Net head: 128 -> 8, fp32 out, no activation
     wt8 = bf16_round(_w((8, 128, 3, 3, 3), 7))
-    y, _ = G.run_conv(x, None, wt8, None, f32=True)
+    y, _, _ = G.run_conv(x, None, wt8, None, f32=True, audit=True)
     assert rel_l2(y, F.conv3d(x, wt8, None, padding=1)) < 1e-4
     # VAE encoder stem: 1-channel volume stored with 8 channels, weight has a single input channel
     x1 = bf16_round(formula_input((2, 1, 3, 9, 7), 8))
     w1 = bf16_round(_w((32, 1, 3, 3, 3), 9))
-    y, _ = G.run_conv(x1, None, w1, None, c1_pad=8, cin_w=1)
+    y, _, _ = G.run_conv(x1, None, w1, None, c1_pad=8, cin_w=1, audit=True)
     assert rel_l2(y, F.conv3d(x1, w1, None, padding=1)) < CONV_TOL
 
 
@@ -593,7 +607,7 @@ def test_conv3_head_kernel(G, monkeypatch, name, cin, cout, dims, f32, act):
         ref = torch.tanh(ref)
     monkeypatch.setenv("CTSI_CONV_FORCE_HALO3", "1")
     groups = 1 if cout < 8 else cout // 4
-    y, sums = G.run_conv(x, None, wt, b, f32=f32, act=act, want_stats=not f32, groups=groups)
+    y, sums, tol = G.run_conv(x, None, wt, b, f32=f32, act=act, want_stats=not f32, groups=groups, audit=True)
     assert tuple(y.shape) == tuple(ref.shape)
     assert rel_l2(y, ref) < (2e-4 if f32 else CONV_TOL), name
     if not f32:
@@ -602,8 +616,10 @@ def test_conv3_head_kernel(G, monkeypatch, name, cin, cout, dims, f32, act):
         assert torch.allclose(sums[..., 1], (rg * rg).sum(-1), rtol=2e-3)
     monkeypatch.delenv("CTSI_CONV_FORCE_HALO3")
     monkeypatch.setenv("CTSI_CONV_NO_HEAD3", "1")
-    y2, _ = G.run_conv(x, None, wt, b, f32=f32, act=act)
+    y2, _, tol2 = G.run_conv(x, None, wt, b, f32=f32, act=act, audit=True)
     assert float((y - y2).abs().max()) <= (1e-4 if f32 else 2.0 ** -7) * float(ref.abs().max())
+    if not f32:       # (fp32 outputs: the line above is already tighter than two F32_MAX_REL class bounds)
+        assert G.within_tolerances(y, y2, tol, tol2)
 
 
 HEAD2_CASES = [
@@ -630,13 +646,15 @@ def test_conv3_head2_kernel(G, monkeypatch, name, cout, dims, f32, act):
     if act:
         ref = torch.tanh(ref)
     monkeypatch.setenv("CTSI_CONV_FORCE_HALO3", "1")
-    y, _ = G.run_conv(x, None, wt, b, f32=f32, act=act)
+    y, _, tol = G.run_conv(x, None, wt, b, f32=f32, act=act, audit=True)
     assert tuple(y.shape) == tuple(ref.shape)
     e = rel_l2(y, ref)
     assert e < (2e-4 if f32 else CONV_TOL), (name, e)
     monkeypatch.setenv("CTSI_CONV_NO_HEAD2", "1")
-    y1, _ = G.run_conv(x, None, wt, b, f32=f32, act=act)
+    y1, _, tol1 = G.run_conv(x, None, wt, b, f32=f32, act=act, audit=True)
     assert float((y - y1).abs().max()) <= (1e-4 if f32 else 2.0 ** -7) * float(ref.abs().max())
+    if not f32:       # (fp32 outputs: the line above is already tighter than two F32_MAX_REL class bounds)
+        assert G.within_tolerances(y, y1, tol, tol1)
     monkeypatch.delenv("CTSI_CONV_NO_HEAD2")
     if f32 and n == 1:
         for tap in range(27):          # out[co] = x[channel 5 + co] shifted by the tap: exact in fp32
@@ -670,11 +688,147 @@ def test_k32_tile_orders(G, monkeypatch, form, order):
         kw = dict(k=(3, 4, 4), s=(2, 2))
     b = formula_input((cout,), 87) * 0.1
     monkeypatch.setenv("CTSI_CONV_TILE_ORDER", "0")
-    y0, s0 = G.run_conv(x, None, wt, b, want_stats=True, groups=8, **kw)
+    y0, s0, _ = G.run_conv(x, None, wt, b, want_stats=True, groups=8, audit=True, **kw)
     monkeypatch.setenv("CTSI_CONV_TILE_ORDER", order)
-    y1, s1 = G.run_conv(x, None, wt, b, want_stats=True, groups=8, **kw)
+    y1, s1, _ = G.run_conv(x, None, wt, b, want_stats=True, groups=8, audit=True, **kw)
     assert torch.equal(y0, y1)
     assert torch.allclose(s0, s1, rtol=1e-12, atol=1e-9)
+
+
+# ---- edge shapes the sweeps above do not reach -------------------------------------------------------------------------------
+# Ordinary supported shapes (depth shards and thick patches are this thin), a few thousand voxels at the most; dims are the
+# INPUT's (n, d, h, w).  Planes stay clear of multiples of 12, so no narrow 4x4x24 / 8x4x12 tile competes with a forced form.
+EDGE_CASES = [
+    # name, kind, c1, c2, cout, (n, d, h, w)
+    ("k3_depth1", "k3", 64, 0, 64, (1, 1, 8, 16)),                      # both depth halos of every tile are padding
+    ("k3_depth2", "k3", 64, 0, 64, (1, 2, 6, 16)),
+    ("k3_plane_3x5", "k3", 64, 0, 64, (1, 4, 3, 5)),                    # smaller than one tile in both directions
+    ("k3_w17", "k3", 64, 0, 64, (1, 3, 4, 17)),                         # one column past a 16-wide tile
+    ("k3_w25", "k3", 64, 0, 72, (1, 2, 4, 25)),
+    ("k3_w33", "k3", 64, 0, 64, (1, 2, 5, 33)),                         # one column past a 32-wide tile
+    ("k3_batch3_ragged_all_axes_cin128", "k3", 128, 0, 64, (3, 5, 7, 19)),      # (Cin % 128 == 0: the split-K forms accept it)
+    ("k3_8+24_cout8", "k3", 8, 24, 8, (2, 3, 5, 9)),                    # sources no halo-tile form takes: every form falls back
+    ("k3_8+24_cout72", "k3", 8, 24, 72, (2, 3, 5, 9)),
+    ("down_depth1", "down", 64, 0, 64, (1, 1, 16, 32)),
+    ("down_out_plane_3x5", "down", 64, 0, 64, (1, 4, 6, 10)),
+    ("down_out_w17", "down", 64, 0, 64, (1, 3, 8, 34)),
+    ("down_batch3_ragged_all_axes", "down", 32, 0, 72, (3, 5, 14, 38)),
+    ("down_cout8", "down", 32, 0, 8, (1, 2, 10, 18)),
+    ("convT_depth1", "up", 64, 0, 64, (1, 1, 8, 16)),
+    ("convT_depth2_plane_3x5", "up", 64, 0, 64, (1, 2, 3, 5)),
+    ("convT_w17", "up", 64, 0, 64, (1, 3, 4, 17)),
+    ("convT_w33", "up", 32, 0, 72, (1, 2, 5, 33)),
+    ("convT_batch3_ragged_all_axes", "up", 64, 0, 64, (3, 5, 7, 19)),
+    ("convT_cout8", "up", 32, 0, 8, (1, 2, 5, 9)),
+]
+_EDGE_FORMS = {"k3": HALO3_TILES, "down": DOWN_TILES, "up": CONVT_TILES}
+_EDGE_KW = {"k3": dict(), "down": dict(k=(3, 4, 4), s=(2, 2)), "up": dict(k=(3, 4, 4), s=(2, 2), transposed=True)}
+EDGE_RUNS = [(c, f) for c in EDGE_CASES for f in ["own"] + _EDGE_FORMS[c[1]]]
+_EDGE = {}
+
+
+def edge_form_expectation(kind, form, c1, c2, cout):
+    """What ctsi_conv_plan_config / ctsi_conv_plan_form must report when `form` is forced on a case: (modes, tile or None, split-K
+    or None).  Either the form itself, or -- where the form does not take the channels -- the fall-back csrc/conv_plan.hip
+    documents (choose_k3_form, choose_k32_strided_form), so that a form that refuses cannot pass as if it had run."""
+    cin = c1 + c2
+    c16 = c1 % 16 == 0 and c2 % 16 == 0
+    couts = cout >= 64 and cout % 8 == 0
+    if kind != "k3":
+        if not (c2 == 0 and c16 and couts):
+            return {0, 1, 2}, None, None                                    # the gather kernel
+        if kind == "up":
+            return {9}, {"16": (4, 8, 16), "32": (4, 4, 32), "16x384": (3, 8, 16), "32x384": (3, 4, 32)}[form], 0
+        tile = {"32k": (4, 4, 32), "16k": (4, 8, 16), "32k3": (3, 4, 32), "16k3": (3, 8, 16), "16k3s": (3, 8, 16)}[form]
+        return {9}, tile, 2 if form == "16k3s" and cin % 32 == 0 else 0
+    c32 = c1 % 32 == 0 and c2 % 32 == 0 and not (cin <= 32 and cin & (cin - 1) == 0)
+    if not ((c32 or c16) and couts):
+        return {0, 1, 2, 8}, None, None                                     # the gather kernel (or the <= 16-cout head kernel)
+    sk_ok = cin % 128 == 0 and c16
+    k32 = {"32k": ((4, 4, 32), 0), "16k": ((4, 8, 16), 0), "32k3": ((3, 4, 32), 0), "16k3": ((3, 8, 16), 1)}
+    if form in k32:
+        return {9}, k32[form][0], k32[form][1]
+    if form in ("16k3s", "32ks") and sk_ok:
+        return {9}, (3, 8, 16) if form == "16k3s" else (4, 4, 32), 2
+    if not c32:
+        return {9}, None, 0                                                  # 16-channel sources: a 512-voxel k32 tile, unsplit
+    # the 32x32x16-MFMA kernel's tiles; the split-K forms without Cin % 128 == 0 fall back to the tile their other overrides pick
+    tile = {"16h": (4, 4, 16), "16h3": (3, 4, 16), "32": (4, 2, 32), "32ks": (4, 2, 32)}.get(form)
+    return {4}, tile, 0
+
+
+def _plan_report(transposed, k, s, n, c1, c2, cout, d, h, w):
+    import ctypes as C
+    L = importlib.import_module("video-to-video-diffusion_amd.lib")
+    lib, plan, mode, form = L.get_lib(), C.c_void_p(), C.c_int(), (C.c_int * 8)()
+    lib.conv_plan_create(C.byref(plan), C.byref(L.ConvDesc(int(transposed), k[0], k[1], k[2], s[0], s[1], 1, 1, 1, n, c1, c2, cout, d, h, w, 0)))
+    lib.conv_plan_config(plan, None, None, C.byref(mode))
+    lib.conv_plan_form(plan, form)
+    lib.conv_plan_destroy(plan)
+    return mode.value, tuple(form[:3]), form[3]
+
+
+def _edge_case(name, kind, c1, c2, cout, dims):
+    """operands and the fp32 torch reference of a case: computed once, shared by its forms"""
+    if name not in _EDGE:
+        n, d, h, w = dims
+        x1 = bf16_round(formula_input((n, c1, d, h, w), 1))
+        x2 = bf16_round(formula_input((n, c2, d, h, w), 2)) if c2 else None
+        x = torch.cat([x1, x2], 1) if c2 else x1
+        b = formula_input((cout,), 4) * 0.1
+        if kind == "k3":
+            wt = bf16_round(_w((cout, c1 + c2, 3, 3, 3), 3))
+            ref = F.conv3d(x, wt, b, padding=1)
+        elif kind == "down":
+            wt = bf16_round(_w((cout, c1, 3, 4, 4), 3))
+            ref = F.conv3d(x, wt, b, stride=(1, 2, 2), padding=(1, 1, 1))
+        else:
+            wt = bf16_round(_w((c1, cout, 3, 4, 4), 3, transposed=True))
+            ref = F.conv_transpose3d(x, wt, b, stride=(1, 2, 2), padding=(1, 1, 1))
+        _EDGE[name] = dict(x1=x1, x2=x2, wt=wt, b=b, ref=ref)
+    return _EDGE[name]
+
+
+@pytest.mark.parametrize("case,form", EDGE_RUNS, ids=[f"{c[0]}-{f}" for c, f in EDGE_RUNS])
+def test_conv_edge_shapes(G, monkeypatch, case, form):
+    """Thin volumes, planes smaller than a tile or one column past it, batch 3 with every axis ragged, 8 / 72 output channels
+    and 8 + 24-channel sources: on the plan's own choice and on every forced tile form of the case's kind.  What the forced
+    plan reports is asserted (the form, or its documented fall-back); every launch runs under the forward audit (one bf16
+    ulp per element and the GroupNorm column sums against float64, tests/fwd_audit.py); a forced form and the plan's own
+    choice lie within the sum of their per-element tolerances."""
+    name, kind, c1, c2, cout, dims = case
+    n, d, h, w = dims
+    c = _edge_case(*case)
+    kw = _EDGE_KW[kind]
+    groups = 8 if cout % 8 == 0 and cout >= 8 else 1
+    assert n * d * h * w * (4 if kind == "up" else 1) <= 8192
+    if form != "own":
+        env = {"k3": halo3_tile_env, "down": down_tile_env, "up": convt_tile_env}[kind](form)
+        for key, val in env.items():
+            monkeypatch.setenv(key, val)
+        modes, tile, ksplit = edge_form_expectation(kind, form, c1, c2, cout)
+        got = _plan_report(kind == "up", kw.get("k", (3, 3, 3)), kw.get("s", (1, 1)), n, c1, c2, cout, d, h, w)
+        print(f"[{name} {form}] plan: mode {got[0]} tile {got[1]} split-K {got[2]}")
+        assert got[0] in modes, (got, modes)
+        assert tile is None or got[1] == tile, (got, tile)
+        assert ksplit is None or got[2] == ksplit, (got, ksplit)
+    y, sums, tol = G.run_conv(c["x1"], c["x2"], c["wt"], c["b"], want_stats=True, groups=groups, audit=True, **kw)
+    assert tuple(y.shape) == tuple(c["ref"].shape)
+    assert rel_l2(y, c["ref"]) < CONV_TOL
+    rg = c["ref"].reshape(n, groups, -1).double()
+    assert torch.allclose(sums[..., 0], rg.sum(-1), rtol=1e-3, atol=1e-2 * math.sqrt(rg.shape[-1]))
+    assert torch.allclose(sums[..., 1], (rg * rg).sum(-1), rtol=2e-3)
+    if form == "own":
+        c["own"] = (y, tol)
+        return
+    if "own" not in c:          # (this case's own-plan run was deselected)
+        for key in env:
+            monkeypatch.delenv(key)
+        y0, _, tol0 = G.run_conv(c["x1"], c["x2"], c["wt"], c["b"], audit=True, **kw)
+        c["own"] = (y0, tol0)
+    y0, tol0 = c["own"]
+    assert float((y - y0).abs().max()) <= 2.0 ** -7 * float(c["ref"].abs().max())
+    assert G.within_tolerances(y, y0, tol, tol0)
 
 
 def test_conv_linearity_and_zero_padding_property(G):
@@ -1010,19 +1164,20 @@ def test_residual_tail_streaming_kernel(G, monkeypatch, name, c1, c2, cout, dims
                              fuse_gn=(ah, slot, gnm, silu))
             kernels = [m[2] for m in prog.op_meta if m[0] == "res1x1+gn"]
             prog.finalize_layout()
-            prog.run()
+            _, tol = G.audit_program(prog)      # gn.colsum, gn.finalize and the fused tail, each against float64 from its own operands
             out = G.from_act(prog, y).cpu()
         torch.cuda.synchronize()
-        return out, kernels
+        return out, kernels, tol
 
-    out, kernels = run(True)
+    out, kernels, tol = run(True)
     ref = F.group_norm(hh, 32, gnm.weight.detach(), gnm.bias.detach(), 1e-5) + \
         F.conv3d(torch.cat([x1, x2], 1) if x2 is not None else x1, wt, bias)
     if silu:
         ref = F.silu(ref)
     assert rel_l2(out, ref) < 6e-3, name
-    gather, _ = run(False)
+    gather, _, tol_g = run(False)
     assert rel_l2(out, gather) < 6e-3, name                       # (the gather kernel rounds the conv result to bf16 before the add)
+    assert G.within_tolerances(out, gather, tol, tol_g)          # (that rounding is in tol_g: fwd_audit.FUSE_R_ULPS)
     assert kernels and all(k_.endswith("m10") for k_ in kernels), kernels       # the streaming kernel is what ran
 
 

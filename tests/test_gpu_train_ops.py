@@ -1,7 +1,9 @@
 """GPU: the training-path kernels (weight gradient, data gradient through the forward kernels, GroupNorm backward,
 loss, q_sample, small Linear backward) against torch autograd in fp32 on the same bf16-rounded operands.
 
- wgrad / dgrad     rel-L2 <= 3e-3   (fp32 accumulate of bf16 products)
+ wgrad / dgrad     rel-L2 <= 3e-3   (fp32 accumulate of bf16 products), and against float64 from the same operands: the weight
+                   gradient in the f32 class (F32_REL_L2 / F32_MAX_REL of tests/train_audit.py, every forced form), the data
+                   gradient's conv launch under the forward audit (tests/fwd_audit.py: one bf16 ulp per element)
  GroupNorm bwd     rel-L2 <= 8e-3   (bf16 in / out, fp32 statistics; g is rounded to bf16 between the two passes)
  fp32-only ops     rel-L2 <= 1e-5
 """
@@ -15,9 +17,11 @@ import torch
 import torch.nn.functional as F
 
 from tests.helpers import bf16_round, formula_input, rel_l2
+from tests.train_audit import cmp_f32
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+_DW64 = {}            # float64 weight gradients, shared by the tests and forced forms of one case
 
 
 @pytest.fixture(scope="module")
@@ -50,6 +54,29 @@ def _wgrad(G, r, g, k, s, p, n_taps_shape, out_shape, stride_rgt, c_off_elems=0,
                     stride_rgt[1], stride_rgt[2], 1.0, c.sptr)
     torch.cuda.synchronize()
     return dw
+
+
+def _dw64(key, x, dy, wshape, k, s, p, transposed=False):
+    """float64 autograd weight gradient from the same bf16-rounded operands (on the device, MIOpen off), computed once per `key`"""
+    if key not in _DW64:
+        with torch.backends.cudnn.flags(enabled=False):
+            xd, gd = x.detach().to(DEV, torch.float64), dy.to(DEV, torch.float64)
+            wz = torch.zeros(wshape, dtype=torch.float64, device=DEV, requires_grad=True)
+            fn = F.conv_transpose3d if transposed else F.conv3d
+            (g,) = torch.autograd.grad(fn(xd, wz, None, stride=(1,) + tuple(s), padding=tuple(p)), wz, gd)
+        _DW64[key] = g.cpu()
+    return _DW64[key]
+
+
+def _dw_f32_class(label, dw, ref64):
+    """The weight gradient is an fp32 accumulation of exact bf16 products: F32_REL_L2 / F32_MAX_REL (1e-4 / 1e-3) against float64,
+    the bounds tests/train_audit.py holds the same kernels to at the programs' shapes.  Every entry was written (no NaN left)."""
+    got = dw.detach().cpu()
+    assert torch.isfinite(got).all(), label
+    res = cmp_f32(got, ref64)
+    print(f"[conv-op-audit] {label} | wgrad | dW {'x'.join(str(v) for v in got.shape)} | f32 | rel-L2 {res['rel_l2']:.3e} | "
+          f"max/max|ref| {res['max_rel']:.3e} | worst/tol - | {'ok' if res['ok'] else 'FAIL'}")
+    assert res["ok"], (label, res)
 
 
 WG_CASES = [
@@ -95,6 +122,7 @@ def test_wgrad_and_dgrad_vs_autograd(G, name, cin, cout, dims, kind):
     else:              # R = dy, G = layer input; weight (cout, cin, T)
         dw = _wgrad(G, dy, x.detach(), k, s, p, T, tuple(wt.shape), (cin * T, T, 1))
     e_w = rel_l2(dw.cpu(), wt.grad)
+    _dw_f32_class(f"wgrad[{name}]", dw, _dw64(("wg", name), x, dy, tuple(wt.shape), k, s, p, kind == "up"))
     # ---- data gradient through the forward conv kernels ----
     c = G.ctx()
     if kind in ("k3", "k1"):
@@ -103,11 +131,11 @@ def test_wgrad_and_dgrad_vs_autograd(G, name, cin, cout, dims, kind):
         with c.scope():
             c.lib.weight_dgrad_layout(G._ptr(wsrc), G._ptr(wd), cout, cin, T, 0, cin, c.sptr)
         torch.cuda.synchronize()
-        dx, _ = G.run_conv(dy, None, wd.cpu(), None, k=k, s=s, p=p)
+        dx, _, _ = G.run_conv(dy, None, wd.cpu(), None, k=k, s=s, p=p, audit=True)
     elif kind == "down":   # data gradient of the strided conv = ConvTranspose3d with the same weight tensor
-        dx, _ = G.run_conv(dy, None, wt.detach(), None, transposed=True, k=k, s=s, p=p)
+        dx, _, _ = G.run_conv(dy, None, wt.detach(), None, transposed=True, k=k, s=s, p=p, audit=True)
     else:                  # data gradient of the ConvTranspose3d = strided Conv3d with the same weight tensor
-        dx, _ = G.run_conv(dy, None, wt.detach(), None, k=k, s=s, p=p)
+        dx, _, _ = G.run_conv(dy, None, wt.detach(), None, k=k, s=s, p=p, audit=True)
     e_x = rel_l2(dx, x.grad)
     print(f"{name}: wgrad rel-L2 {e_w:.2e}, dgrad rel-L2 {e_x:.2e}")
     assert tuple(dx.shape) == tuple(x.shape)
@@ -140,6 +168,7 @@ def test_wgrad_tap_sharing_kernel(G, monkeypatch, name, cin, cout, dims, k):
     monkeypatch.setenv("CTSI_WGRAD_HALO", "0")          # (the halo-tile kernel would take the well-fitting 3x3x3 cases)
     dw = _wgrad(G, dy, x.detach(), kk, (1, 1), pp, T, tuple(wt.shape), (cin * T, T, 1))
     assert rel_l2(dw.cpu(), wt.grad) <= 3e-3, name
+    _dw_f32_class(f"wgrad-s1[{name}]", dw, _dw64(("s1", name), x, dy, tuple(wt.shape), kk, (1, 1), pp))
     dw2 = _wgrad(G, dy, x.detach(), kk, (1, 1), pp, T, tuple(wt.shape), (cin * T, T, 1))
     assert torch.equal(dw, dw2)
 
@@ -181,13 +210,18 @@ def test_wgrad_halo_tile_kernel(G, monkeypatch, name, cin, cout, dims, code):
     e = rel_l2(dw.cpu(), wt.grad)
     print(f"{name}: halo-tile wgrad rel-L2 {e:.2e} (S = {S.value})")
     assert torch.isfinite(dw).all() and e <= 3e-3, name
+    ref64 = _dw64(("halo", name), x, dy, tuple(wt.shape), (3, 3, 3), (1, 1), (1, 1, 1))
+    _dw_f32_class(f"wgrad-halo[{name}] S={S.value}", dw, ref64)
     assert torch.equal(dw, _wgrad(*args))
     monkeypatch.setenv("CTSI_WGRAD_REDUCE_T", "0")         # the one-thread-per-output reduce pass: same sums, other order
-    assert rel_l2(dw.cpu(), _wgrad(*args).cpu()) <= 1e-6
+    dw_t0 = _wgrad(*args)
+    assert rel_l2(dw.cpu(), dw_t0.cpu()) <= 1e-6
+    _dw_f32_class(f"wgrad-halo[{name}] reduce_t=0", dw_t0, ref64)
     monkeypatch.delenv("CTSI_WGRAD_REDUCE_T")
     monkeypatch.setenv("CTSI_WGRAD_HALO", "0")
     dw_old = _wgrad(*args)
     assert rel_l2(dw.cpu(), dw_old.cpu()) <= 1e-3          # same products, other summation order
+    _dw_f32_class(f"wgrad-halo[{name}] halo=0", dw_old, ref64)
     # exactness: dY = one-hot in (voxel, cout) picks X's 27 neighbours of that voxel -- incl. the zero padding at a face
     monkeypatch.delenv("CTSI_WGRAD_HALO")
     dy1 = torch.zeros_like(dy)
@@ -230,6 +264,9 @@ def test_wgrad_mfma_16x16x32_form(G, monkeypatch, name, cin, cout, dims, kind):
             res.append(_wgrad(G, dy, x.detach(), k, s, p, T, tuple(wt.shape), (cin * T, T, 1)))
     assert rel_l2(res[1].cpu(), wt.grad) <= 3e-3, name
     assert rel_l2(res[1].cpu(), res[0].cpu()) <= 1e-5
+    ref64 = _dw64(("wg", name), x, dy, tuple(wt.shape), k, s, p, kind == "up")
+    for shape16 in (0, 1):
+        _dw_f32_class(f"wgrad-shape16={shape16}[{name}]", res[shape16], ref64)
 
 
 def test_wgrad_two_sources_and_split_k(G):
@@ -246,8 +283,13 @@ def test_wgrad_two_sources_and_split_k(G):
     T, cin = 27, c1 + c2
     dw = torch.full(tuple(wt.shape), float("nan"), dtype=torch.float32, device=DEV)
     _wgrad(G, dy, x1, (3, 3, 3), (1, 1), (1, 1, 1), T, None, (cin * T, T, 1), 0, dw)
+    # the first call wrote its own input-channel slice of every row and nothing else: the rest is still the NaN pre-fill
+    assert torch.isfinite(dw[:, :c1]).all() and torch.isnan(dw[:, c1:]).all()
+    first = dw[:, :c1].clone()
     _wgrad(G, dy, x2, (3, 3, 3), (1, 1), (1, 1, 1), T, None, (cin * T, T, 1), c1 * T, dw)
+    assert torch.equal(dw[:, :c1], first)                  # ... and the second call left that slice alone
     assert rel_l2(dw.cpu(), wt.grad) <= 3e-3
+    _dw_f32_class("wgrad[two_sources_split_k]", dw, _dw64(("two", 0), xx, dy, tuple(wt.shape), (3, 3, 3), (1, 1), (1, 1, 1)))
     dw2 = torch.empty_like(dw)
     _wgrad(G, dy, x1, (3, 3, 3), (1, 1), (1, 1, 1), T, None, (cin * T, T, 1), 0, dw2)
     _wgrad(G, dy, x2, (3, 3, 3), (1, 1), (1, 1, 1), T, None, (cin * T, T, 1), c1 * T, dw2)

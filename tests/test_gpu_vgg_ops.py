@@ -1,7 +1,9 @@
 """GPU: the single ops of the VGG perceptual loss (csrc/vgg_loss.hip and the (1, 3, 3) conv plans) against torch.
 
 The convolutions are judged as tests/test_gpu_ops.py judges its conv forms (test_downsample_conv_on_halo_tile_kernel): rel-L2
-against the fp32 torch convolution on the same bf16 operands below CONV_TOL = 3e-3.  The elementwise passes compute in fp32
+against the fp32 torch convolution on the same bf16 operands below CONV_TOL = 3e-3, and -- every launch, the ReLU form too --
+by the forward audit (tests/fwd_audit.py): one bf16 ulp per element against float64 from the launch's own operands; two kernels
+on one problem within the sum of their per-element tolerances.  The elementwise passes compute in fp32
 from bf16 operands that the test chooses exactly representable, so selections (max pooling, its routing, ReLU, the input
 transform) are held to bit equality and sums to the rounding of their output format."""
 import ctypes as C
@@ -99,28 +101,31 @@ def test_planar_conv_forward_and_dgrad(G, monkeypatch, case, tile):
     monkeypatch.setenv("CTSI_CONV_PLANAR", "0" if tile == "gather" else tile)
     planar, dims = _planned(G, cin, cout, images, h, w)
     assert (planar, dims) == (True, TILES[tile]) if tile != "gather" else not planar
-    y, _ = G.run_conv(c["x"], None, c["wt"].unsqueeze(2), c["b"], k=K, p=P)
+    y, _, tol_y = G.run_conv(c["x"], None, c["wt"].unsqueeze(2), c["b"], k=K, p=P, audit=True)
     assert tuple(y.shape) == (1, cout, images, h, w)
     wd = _dgrad_weights(G, c["wt"])
-    dx, _ = G.run_conv(c["g"], None, wd, None, k=K, p=P)
+    dx, _, tol_dx = G.run_conv(c["g"], None, wd, None, k=K, p=P, audit=True)
     e_y, e_dx = rel_l2(_images(y), c["ref"]), rel_l2(_images(dx), c["ref_dx"])
     print(f"[{name} {tile}] forward rel-L2 {e_y:.3e}  dgrad rel-L2 {e_dx:.3e}")
     assert e_y < CONV_TOL and e_dx < CONV_TOL
     if tile == "gather":
-        c["gather"] = (y, dx)
+        c["gather"] = (y, dx, tol_y, tol_dx)
         return
     # the ReLU epilogue clamps the fp32 accumulators before the one rounding to bf16: exactly relu of the plain output
-    yr, _ = G.run_conv(c["x"], None, c["wt"].unsqueeze(2), c["b"], k=K, p=P, act=2)
+    yr, _, _ = G.run_conv(c["x"], None, c["wt"].unsqueeze(2), c["b"], k=K, p=P, act=2, audit=True)
     assert torch.equal(yr, torch.relu(y)) and float((y < 0).float().mean()) > 0.2
-    dxr, _ = G.run_conv(c["g"], None, wd, None, k=K, p=P, act=2)
+    dxr, _, _ = G.run_conv(c["g"], None, wd, None, k=K, p=P, act=2, audit=True)
     assert torch.equal(dxr, torch.relu(dx))
     # against the gather kernel (another summation order): test_downsample_conv_on_halo_tile_kernel's bound
     if "gather" not in c:          # (this case's gather run was deselected)
         monkeypatch.setenv("CTSI_CONV_PLANAR", "0")
-        c["gather"] = (G.run_conv(c["x"], None, c["wt"].unsqueeze(2), c["b"], k=K, p=P)[0], G.run_conv(c["g"], None, wd, None, k=K, p=P)[0])
-    y2, dx2 = c["gather"]
+        gy = G.run_conv(c["x"], None, c["wt"].unsqueeze(2), c["b"], k=K, p=P, audit=True)
+        gdx = G.run_conv(c["g"], None, wd, None, k=K, p=P, audit=True)
+        c["gather"] = (gy[0], gdx[0], gy[2], gdx[2])
+    y2, dx2, tol_y2, tol_dx2 = c["gather"]
     assert float((y - y2).abs().max()) <= 2.0 ** -7 * float(c["ref"].abs().max())
     assert float((dx - dx2).abs().max()) <= 2.0 ** -7 * float(c["ref_dx"].abs().max())
+    assert G.within_tolerances(y, y2, tol_y, tol_y2) and G.within_tolerances(dx, dx2, tol_dx, tol_dx2)
 
 
 def test_relu_epilogue_is_refused_on_the_gather_kernel(G, monkeypatch):
@@ -137,12 +142,12 @@ def test_stem_conv_and_its_dgrad(G):
     x3 = bf16_round(formula_input((1, 3, images, h, w), 1))
     wt = bf16_round(_w((64, 3, 3, 3), 3))
     b = formula_input((64,), 4) * 0.1
-    y, _ = G.run_conv(x3, None, wt.unsqueeze(2), b, k=K, p=P, c1_pad=8, cin_w=3)
+    y, _, _ = G.run_conv(x3, None, wt.unsqueeze(2), b, k=K, p=P, c1_pad=8, cin_w=3, audit=True)
     assert rel_l2(_images(y), F.conv2d(_images(x3), wt, b, padding=1)) < CONV_TOL
     g = bf16_round(formula_input((1, 64, images, h, w), 5))
     wd = torch.zeros(8, 64, 1, 3, 3)
     wd[:3, :, 0] = wt.flip(2, 3).transpose(0, 1)
-    dx, _ = G.run_conv(g, None, wd, None, k=K, p=P)
+    dx, _, _ = G.run_conv(g, None, wd, None, k=K, p=P, audit=True)
     assert tuple(dx.shape) == (1, 8, images, h, w) and float(dx[:, 3:].abs().max()) == 0.0
     assert rel_l2(_images(dx[:, :3]), F.conv_transpose2d(_images(g), wt, padding=1)) < CONV_TOL
 
