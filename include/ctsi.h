@@ -763,6 +763,33 @@ int ctsi_feat_loss_finalize(const double* partials, const long long* counts, int
 int ctsi_feat_grad_relu_bwd(const void* g_in, const void* y, const void* target, void* g_out, long long count, float coef,
                             int kind, int relu, const float* grad_loss, void* stream);
 
+/* LPIPS perceptual distance (csrc/lpips.hip): what lpips 0.1.x (net = 'vgg') adds to a VGG-16 stack that
+ * runs on the entries above.  Features are bf16 channels-last [image][positions][c]; a ROW is the c channels of one position,
+ * c / 8 lanes of one 16-byte load: c is 64, 128, 256 or 512.  eps = 1e-10.
+ * ctsi_lpips_prep: image n of x (fp32 NCHW, c = 1 or 3; c = 1: the grey value in all three channels) -> the 8-channel bf16
+ *   image, channel k < 3 = (v - shift_k) / scale_k (shift = -0.030, -0.088, -0.188; scale = 0.458, 0.448, 0.450), v = x or, with
+ *   normalize, 2 x - 1; channels 3-7 zero.  ctsi_lpips_prep_bwd: grad (fp32, the shape of x) from the 8-channel image gradient
+ *   g: g_k / scale_k (twice that with normalize), c = 1: the sum of the three.
+ * ctsi_lpips_dist_fwd: one tap.  u = y / (|y| + eps), v = target / (|target| + eps) per row (|.| the row's 2-norm);
+ *   partials[i * ctsi_lpips_blocks() + b] <- fixed-order fp64 partial sums of sum_c w_c (u_c - v_c)^2 over the rows of image i
+ *   (0 for a block without rows).  w: c device floats.  Each feature element is read once; nothing else is written.
+ * ctsi_lpips_finalize: partials of `taps` (<= 16) taps stored as [tap][image][ctsi_lpips_blocks()]; out[i] = sum over taps of
+ *   (image i's sum) / positions[tap], tap_means[tap] = the mean over the images of that quotient; one launch.
+ * ctsi_lpips_grad_relu_bwd: g_out = (g_in + grad_out[image] / positions * d) * [y > 0] with r = 2 w (u - v) and
+ *   d = r / (a + eps) - y (y . r) / (a (a + eps)^2), a = |y|; a row with a = 0 gets exact zeros, never a NaN or Inf.  The row
+ *   norms are recomputed, not stored by the forward.  g_in may be NULL; g_out may alias g_in.  grad_out: `images` device floats.
+ * No entry allocates, synchronises or keeps state; no float atomics: every result is bit-identical run to run.  Bad
+ * arguments return CTSI_ERR_INVALID before any launch. */
+int ctsi_lpips_blocks(void);
+int ctsi_lpips_prep(const float* x, void* dst, int n, int c, int h, int w, int normalize, void* stream);
+int ctsi_lpips_prep_bwd(const void* g, float* grad, int n, int c, int h, int w, int normalize, void* stream);
+int ctsi_lpips_dist_fwd(const void* y, const void* target, const float* w, int images, long long positions, int c,
+                        double* partials, void* stream);
+int ctsi_lpips_finalize(const double* partials, const long long* positions, int taps, int images, float* out,
+                        float* tap_means, void* stream);
+int ctsi_lpips_grad_relu_bwd(const void* g_in, const void* y, const void* target, const float* w, void* g_out, int images,
+                             long long positions, int c, const float* grad_out, void* stream);
+
 /* hipGraph helpers (one captured graph per denoising step) -------------------------------- */
 typedef struct ctsi_graph ctsi_graph;
 int ctsi_graph_begin_capture(void* stream);

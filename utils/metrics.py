@@ -8,3 +8,4 @@ calculate_ssim = _m.calculate_ssim
 calculate_video_metrics = _m.calculate_video_metrics
 measurement_residual = _m.measurement_residual
 ensemble_calibration = _m.ensemble_calibration
+calculate_lpips = _m.calculate_lpips

@@ -3,18 +3,7 @@
 // and the one elementwise pass per layer boundary of the backward (loss term + ReLU mask).  All HBM-bound: 16-byte accesses on
 // bf16 channels-last images [image][h][w][c], c a multiple of 8.  Every entry takes plain pointers and sizes, allocates
 // nothing, keeps no state between calls and is capture-safe; no float atomics anywhere, so results are bit-stable.
-#include "ctsi_internal.h"
-
-// the two bf16 halves of a dword as fp32
-__device__ __forceinline__ float bf_lo(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
-
-static unsigned grid_for(long long items, int cap = 8192) {
-    long long blocks = (items + 255) / 256;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (unsigned)blocks;
-}
+#include "feat_common.h"
 
 // ---- input transform ------------------------------------------------------------------------------------------------------
 // image i = b * num + s <- slice slices[s] of sample b (fp32 NCDHW, C = 1); channel c = ((x + 1) / 2 - mean_c) / std_c for
@@ -194,14 +183,6 @@ extern "C" int ctsi_feat_loss_blocks() { return FEAT_BLOCKS; }
 __device__ __forceinline__ float dist_pair(uint32_t p, uint32_t t, bool sq) {
     const float a = bf_lo(p) - bf_lo(t), b = bf_hi(p) - bf_hi(t);
     return sq ? __builtin_fmaf(b, b, a * a) : __builtin_fabsf(a) + __builtin_fabsf(b);
-}
-// fixed-order sum of one value per thread of a 256-thread block; the result is valid in thread 0
-__device__ __forceinline__ double block_sum_256(double v, double* s_part) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
 }
 
 __global__ void __launch_bounds__(256)

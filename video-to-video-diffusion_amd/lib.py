@@ -175,6 +175,12 @@ SIGNATURES = {
     "ctsi_feat_loss_fwd": (_i, [_vp, _vp, _ll, _i, _vp, _vp], True),
     "ctsi_feat_loss_finalize": (_i, [_vp, _vp, _i, _vp, _vp], True),
     "ctsi_feat_grad_relu_bwd": (_i, [_vp, _vp, _vp, _vp, _ll, _f, _i, _i, _vp, _vp], True),
+    "ctsi_lpips_blocks": (_i, [], False),
+    "ctsi_lpips_prep": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_lpips_prep_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_lpips_dist_fwd": (_i, [_vp, _vp, _vp, _i, _ll, _i, _vp, _vp], True),
+    "ctsi_lpips_finalize": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp], True),
+    "ctsi_lpips_grad_relu_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _vp, _vp], True),
     "ctsi_device_error_status": (_i, [C.POINTER(C.c_uint), C.POINTER(C.c_uint), _i], True),
     "ctsi_conv_f32_supported": (_i, [C.POINTER(ConvDesc)], False),
     "ctsi_conv_f32_weight_bytes": (_sz, [C.POINTER(ConvDesc)], False),

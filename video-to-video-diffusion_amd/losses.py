@@ -27,6 +27,15 @@ of `(v + 1) / 2`; five levels of the full SSIM map under the zero-padded 11 x 11
 level value is the mean over all planes and pixels, a 2 x 2 average pool (floor) between levels,
 `loss = 1 - prod_i mean_i ** w_i`.  A negative level mean gives NaN for the loss and every gradient element, as
 torch's `pow` does in the reference.  The gradient is computed for `pred` only.
+
+`LPIPS` is the perceptual distance of the `lpips` package (0.1.x, net='vgg', eval mode) that the reference's VAE trainer
+uses (training/train_vae.py:42-169), on the same engine program with a VGG-16 module table and the kernels of csrc/lpips.hip
+(DESIGN.md section 30).  Semantics of `LPIPS(weights=...)(in0, in1)`, both (N, 3, H, W) in [-1, 1]: the scaling layer
+`(x - shift_c) / scale_c`; torchvision's VGG-16 `features` 0..29; at the ReLU outputs 3, 8, 15, 22, 29 both feature maps are
+divided, per position, by their 2-norm over the channels plus 1e-10; the tap's value is the mean over positions of
+`sum_c w_c (u_c - v_c)^2` with the tap's learned 1x1 head `w`; the result is the sum of the five tap values PER IMAGE, shape
+(N, 1, 1, 1).  The same deviations as for `VGGPerceptualLoss` apply (H, W multiples of 16; ROCm tensors; gradient for `in0`
+only; bf16 activations), and again no weights ship or are fetched.
 """
 from __future__ import annotations
 
@@ -40,7 +49,7 @@ from torch.autograd.function import once_differentiable
 
 from .engine import Ctx, _ptr
 from .lib import CtsiError
-from .vgg_loss_engine import VGG19_MODULES, VGGLossProgram
+from .vgg_loss_engine import LPIPS_TAPS, VGG16_MODULES, VGG19_MODULES, VGGLossProgram
 
 MIN_SIZE = 16          # four 2 x 2 pools must leave at least one pixel
 MAX_WINDOW = 15        # csrc/msssim.hip: odd windows 1 .. 15
@@ -265,6 +274,190 @@ class VGGPerceptualLoss(nn.Module):
         p = pred.to(torch.float32).contiguous()             # outside the Function: autograd carries dtype and layout
         t = target.detach().to(torch.float32).contiguous()
         return _VGGLossFn.apply(p, t, self, torch.is_grad_enabled() and p.requires_grad)
+
+
+def _lpips_conv_param(sd: Dict[str, torch.Tensor], idx: int, kind: str, shape: Tuple[int, ...]) -> torch.Tensor:
+    """Conv `idx` of torchvision's VGG-16 `features` under `features.{idx}.`, `{idx}.` or lpips' `net.slice{k}.{idx}.`."""
+    names = [f"features.{idx}.{kind}", f"{idx}.{kind}"] + [f"net.slice{k}.{idx}.{kind}" for k in range(1, 6)]
+    name = next((n for n in names if n in sd), None)
+    if name is None:
+        raise ValueError(f"VGG-16 weights: key '{names[0]}' (or '{names[1]}', or 'net.slice<k>.{idx}.{kind}') is missing")
+    t = sd[name]
+    if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape):
+        got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"VGG-16 weights: key '{name}' has shape {got}, expected {tuple(shape)}")
+    return t
+
+
+def _lpips_head(src, k: int, channels: int) -> Optional[torch.Tensor]:
+    """Head k: element k of a sequence, or `lin{k}.model.1.weight` / `lins.{k}.model.1.weight` of a state dict; None if absent."""
+    if isinstance(src, dict):
+        t = next((src[n] for n in (f"lin{k}.model.1.weight", f"lins.{k}.model.1.weight") if n in src), None)
+    else:
+        t = src[k] if k < len(src) else None
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or t.numel() != channels:
+        got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"LPIPS head {k} has shape {got}, expected (1, {channels}, 1, 1)")
+    return t.detach().to(torch.float32).reshape(1, channels, 1, 1).clone()
+
+
+class _LPIPSFn(torch.autograd.Function):
+    """out[i] = the LPIPS distance of image i, (N, 1, 1, 1); backward gives in0's gradient from the per-image upstream."""
+
+    @staticmethod
+    def forward(fctx, in0, in1, owner, normalize, want_grad):
+        ctx = Ctx.get(in0.device)
+        n, c, h, w = in0.shape
+        with ctx.scope():
+            prog = owner._take_program(ctx, n, h, w)
+            out = prog.run_forward_images(in0, in1, normalize)
+        owner.last_layer_means = out[n:]
+        if want_grad:
+            fctx.prog, fctx.owner, fctx.generation, fctx.args = prog, owner, prog.generation, (c, bool(normalize))
+        else:
+            owner._give_program(prog)          # every use is ordered on the engine stream
+        return out[:n].reshape(n, 1, 1, 1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(fctx, grad_out):
+        prog = getattr(fctx, "prog", None)
+        if prog is None:
+            raise CtsiError("LPIPS: backward ran twice on one forward (the saved activations are released after the first "
+                            "backward); run the forward again")
+        c, normalize = fctx.args
+        with prog.ctx.scope():
+            g = grad_out.detach().to(torch.float32).reshape(-1).contiguous()
+            grad = prog.run_backward_images(g, c, normalize, fctx.generation)
+        fctx.owner._give_program(prog)
+        fctx.prog = None
+        return grad, None, None, None, None
+
+
+class LPIPS(nn.Module):
+    """The `lpips` package's distance (0.1.x, net='vgg', spatial=False, eval mode), forward and backward on the HIP engine.
+
+    `weights`: a state dict (or a path to one, `torch.load(..., weights_only=True)`) of torchvision's VGG-16
+    (`features.{i}.weight / bias`), of its `features` (`{i}. ...`) or of an `lpips.LPIPS` (`net.slice{k}.{i}. ...`).  The five
+    heads come from `lin_weights` -- five tensors of C = 64, 128, 256, 512, 512 weights, or a state dict with
+    `lin{k}.model.1.weight` / `lins.{k}.model.1.weight` -- or from `weights` when it carries those keys; `lpips=False` uses
+    all-ones heads (the package's baseline mode).  Negative head weights are accepted: the package does not clamp at inference.
+    `weights=None` raises `NotImplementedError`: the engine neither imports `lpips` / torchvision nor downloads, and no weights
+    ship with the project.
+
+    `forward(in0, in1, normalize=False)`: (N, 1 | 3, H, W) in [-1, 1] ([0, 1] with `normalize`) -> (N, 1, 1, 1), the
+    package's contract (a one-channel image is its grey value in all three channels); (B, 1, D, H, W) volumes -> the scalar
+    mean over the slices `slices` selects: 'middle' (D // 2, the VAE trainer's rule), 'all', or a float rate with
+    `VGGPerceptualLoss.slice_indices`' expression; the gradient is exactly zero on the other slices.  The gradient is computed
+    for `in0` only.  `last_layer_means` holds the five tap means over the batch of the latest forward as a device tensor."""
+
+    CHANNELS = (64, 128, 256, 512, 512)
+
+    def __init__(self, net: str = 'vgg', *, weights: Optional[Union[Dict[str, torch.Tensor], str, "os.PathLike"]] = None,
+                 lin_weights=None, lpips: bool = True, slices: Union[str, float] = 'middle', spatial: bool = False):
+        if net != 'vgg':
+            raise ValueError(f"LPIPS: only net='vgg' runs on the HIP engine (the strided 11x11 and fire-module stacks of 'alex' "
+                             f"and 'squeeze' are out of scope), got {net!r}")
+        if spatial:
+            raise ValueError("LPIPS: spatial=True (a distance map per image) is not implemented; the distance is one value per image")
+        if weights is None:
+            raise NotImplementedError(
+                "LPIPS needs pre-trained VGG-16 weights and linear heads, which the lpips package fetches through torchvision "
+                "from the network; the HIP engine does neither.  Pass them: LPIPS(weights=<state dict or path of an "
+                "lpips.LPIPS(net='vgg'), or of torchvision's vgg16 / vgg16().features plus lin_weights=...>) (DESIGN.md section "
+                "30), or use MS_SSIM_Loss.")
+        if not (slices in ('middle', 'all') or (isinstance(slices, (int, float)) and not isinstance(slices, bool) and slices >= 0)):
+            raise ValueError(f"slices must be 'middle', 'all' or a non-negative sampling rate, got {slices!r}")
+        super().__init__()
+        sd = _vgg_state_dict(weights)
+        self.slices = slices
+        self.lpips = bool(lpips)
+        self.net = nn.ModuleList()
+        self._convs: Dict[int, nn.Conv2d] = {}
+        for i, m in enumerate(VGG16_MODULES):
+            if m[0] == "conv":
+                conv = nn.Conv2d(m[1], m[2], kernel_size=3, padding=1)
+                with torch.no_grad():
+                    conv.weight.copy_(_lpips_conv_param(sd, i, "weight", (m[2], m[1], 3, 3)))
+                    conv.bias.copy_(_lpips_conv_param(sd, i, "bias", (m[2],)))
+                self._convs[i] = conv
+                self.net.append(conv)
+        heads = []
+        for k, c in enumerate(self.CHANNELS):
+            if not self.lpips:
+                t = torch.ones(1, c, 1, 1)
+            else:
+                src = _vgg_state_dict(lin_weights) if isinstance(lin_weights, (str, os.PathLike)) else lin_weights
+                t = _lpips_head(src, k, c) if src is not None else _lpips_head(sd, k, c)
+                if t is None:
+                    raise ValueError(f"LPIPS head {k} is missing: pass lin_weights (five tensors, or a state dict with "
+                                     f"'lin{k}.model.1.weight'), weights that carry those keys, or lpips=False")
+            heads.append(nn.Parameter(t, requires_grad=False))
+        self.lins = nn.ParameterList(heads)
+        for p in self.parameters():
+            p.requires_grad = False
+        self.eval()
+        self.register_buffer('shift', torch.tensor([-.030, -.088, -.188]).view(1, 3, 1, 1))
+        self.register_buffer('scale', torch.tensor([.458, .448, .450]).view(1, 3, 1, 1))
+        self.last_layer_means = None
+
+    def slice_indices(self, depth: int) -> torch.Tensor:
+        """The selected slices of a volume of `depth` slices (host, int64)."""
+        if self.slices == 'middle':
+            return torch.tensor([depth // 2], dtype=torch.long)
+        if self.slices == 'all':
+            return torch.arange(depth, dtype=torch.long)
+        num = max(1, int(depth * self.slices))
+        if num < depth:
+            return torch.linspace(0, depth - 1, num, dtype=torch.long)
+        return torch.arange(depth, dtype=torch.long)
+
+    # free programs per (device index, images, h, w), as VGGPerceptualLoss keeps them
+    def _take_program(self, ctx: Ctx, n_img: int, h: int, w: int) -> VGGLossProgram:
+        key = (ctx.device.index, n_img, h, w)
+        cache = self.__dict__.setdefault("_ctsi_programs", {})
+        free = cache.setdefault(key, [])
+        if free:
+            return free.pop()
+        prog = VGGLossProgram(ctx, self._convs, list(LPIPS_TAPS), False, n_img, h, w, modules=VGG16_MODULES, distance="lpips",
+                              heads=list(self.lins))
+        prog.key, prog.home = key, cache
+        return prog
+
+    _give_program = VGGPerceptualLoss._give_program
+
+    def forward(self, in0: torch.Tensor, in1: torch.Tensor, normalize: bool = False) -> torch.Tensor:
+        if not isinstance(in0, torch.Tensor) or not isinstance(in1, torch.Tensor) or in0.dim() not in (4, 5):
+            raise ValueError("LPIPS expects two (N, 1 | 3, H, W) images or two (B, 1, D, H, W) volumes")
+        if in0.shape != in1.shape:
+            raise ValueError(f"shape mismatch: in0 {tuple(in0.shape)} vs in1 {tuple(in1.shape)}")
+        if in0.shape[1] not in ((1, 3) if in0.dim() == 4 else (1,)):
+            raise ValueError(f"LPIPS expects 1 or 3 channels (volumes: 1), got C={in0.shape[1]}")
+        if in0.numel() == 0:
+            raise ValueError("LPIPS got an empty tensor")
+        if in0.shape[-2] % 16 or in0.shape[-1] % 16:
+            raise ValueError(f"H and W must be multiples of 16 (the stack halves them four times), got H={in0.shape[-2]}, "
+                             f"W={in0.shape[-1]}")
+        if not in0.is_cuda or not in1.is_cuda:
+            raise CtsiError("LPIPS runs on the HIP engine: pass ROCm tensors (there is no CPU path in the product; "
+                            "tests/lpips_restatement.py is test infrastructure)")
+        grad = torch.is_grad_enabled()
+        if grad and in1.requires_grad:
+            raise CtsiError("LPIPS computes the gradient for `in0` only; `in1` requires grad -- detach it")
+        in1 = in1.detach()
+        volume = in0.dim() == 5
+        if volume:
+            # the selected slices as images, sample-major; autograd's scatter leaves exact zeros on the other slices
+            b, _, d, h, w = in0.shape
+            idx = self.slice_indices(d).to(in0.device)
+            in0 = in0.index_select(2, idx).permute(0, 2, 1, 3, 4).reshape(-1, 1, h, w)
+            in1 = in1.index_select(2, idx).permute(0, 2, 1, 3, 4).reshape(-1, 1, h, w)
+        p = in0.to(torch.float32).contiguous()              # outside the Function: autograd carries dtype and layout
+        t = in1.to(torch.float32).contiguous()
+        out = _LPIPSFn.apply(p, t, self, bool(normalize), grad and p.requires_grad)
+        return out.mean() if volume else out
 
 
 class MS_SSIM_Loss(nn.Module):

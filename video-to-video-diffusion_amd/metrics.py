@@ -134,3 +134,30 @@ def ensemble_calibration(mean, std, target) -> Dict[str, object]:
     rows = [summary(per[j], float(n * c * plane)) for j in range(d)]
     out['per_slice'] = {k: [r[i] for r in rows] for i, k in enumerate(keys)}
     return out
+
+
+LPIPS_GROUP = 8        # images per engine call of calculate_lpips: one program, whatever the depth
+
+
+def calculate_lpips(video1, video2, lpips, max_val=1.0, group: int = LPIPS_GROUP) -> Dict[str, object]:
+    """LPIPS (losses.LPIPS, the caller's weights) of every slice of two (B, 1, D, H, W) or (D, H, W) volumes in [0, max_val],
+    forward only.  The slices go through the engine in groups of `group` images -- the last group is filled up with repeats of
+    the last slice, whose values are dropped -- so one program serves every depth and memory does not grow with D.
+    {'lpips': mean over all slices, 'per_slice': [B * D floats, sample-major]}."""
+    a, b = _as_device_f32(video1), _as_device_f32(video2)
+    if a.dim() == 3:
+        a, b = a[None, None], b[None, None]
+    if a.shape != b.shape or a.dim() != 5 or a.shape[1] != 1 or a.numel() == 0:
+        raise ValueError(f"expected two (B,1,D,H,W) or (D,H,W) volumes, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if not (isinstance(group, int) and group > 0) or not max_val > 0:
+        raise ValueError(f"group must be a positive integer and max_val positive, got {group!r}, {max_val!r}")
+    h, w = a.shape[-2:]
+    a, b = (a / max_val).transpose(1, 2).reshape(-1, 1, h, w), (b / max_val).transpose(1, 2).reshape(-1, 1, h, w)
+    total = a.shape[0]
+    vals = []
+    with torch.no_grad():
+        for s in range(0, total, group):
+            idx = torch.arange(s, s + group, device=a.device).clamp_(max=total - 1)
+            vals.append(lpips(a[idx], b[idx], normalize=True).reshape(-1)[:total - s])
+    per = torch.cat(vals).double().cpu().tolist()
+    return {'lpips': float(np.mean(per)), 'per_slice': per}

@@ -36,9 +36,14 @@ from .lib import ConvDesc, CtsiError
 VGG19_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512, 512, 512, 512, "M"]
 
 
-def vgg19_feature_modules() -> List[tuple]:
+# torchvision's vgg16().features without its last pool: 30 modules, 13 convs; lpips' five slices end on the ReLUs 3, 8, 15, 22, 29
+VGG16_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512]
+LPIPS_TAPS = (3, 8, 15, 22, 29)
+
+
+def feature_modules(cfg) -> List[tuple]:
     mods, cin = [], 3
-    for v in VGG19_CFG:
+    for v in cfg:
         if v == "M":
             mods.append(("pool",))
         else:
@@ -47,14 +52,24 @@ def vgg19_feature_modules() -> List[tuple]:
     return mods
 
 
+def vgg19_feature_modules() -> List[tuple]:
+    return feature_modules(VGG19_CFG)
+
+
 VGG19_MODULES = vgg19_feature_modules()
+VGG16_MODULES = feature_modules(VGG16_CFG)
 K, P = (1, 3, 3), (0, 1, 1)
 
 
 class VGGLossProgram(Program):
-    """convs: {module index: nn.Conv2d} up to max(feature_layers); n_img: sampled slices per call (B * num)."""
+    """convs: {module index: nn.Conv2d} up to max(feature_layers); n_img: sampled slices per call (B * num).  `modules`: the
+    stack's module table (VGG-19 for the feature loss, VGG-16 for LPIPS).  `distance`: "feat" -- the L1 / L2 feature distance
+    averaged over the layers into one scalar -- or "lpips" -- the unit-normalised, head-weighted squared distance of
+    csrc/lpips.hip, one value PER IMAGE (`heads`: one (C,) weight tensor per layer; every layer a ReLU output).  The conv /
+    ReLU / pool / data-gradient launches are the same for both."""
 
-    def __init__(self, ctx: Ctx, convs, feature_layers: Sequence[int], use_l1: bool, n_img: int, h: int, w: int):
+    def __init__(self, ctx: Ctx, convs, feature_layers: Sequence[int], use_l1: bool, n_img: int, h: int, w: int, *,
+                 modules: Sequence[tuple] = VGG19_MODULES, distance: str = "feat", heads=None):
         super().__init__(ctx)
         lib, sptr, prog = self.lib, ctx.sptr, self
         self.n_img, self.h, self.w = n_img, h, w
@@ -62,16 +77,29 @@ class VGGLossProgram(Program):
         last = self.layers[-1]
         nl = len(self.layers)
         n2 = 2 * n_img
-        self.blocks = lib.feat_loss_blocks()
-        self.partials = self.persistent((nl * self.blocks,), torch.float64)
-        self.out = self.persistent((1 + nl,), torch.float32)
-        self.gl = self.persistent((1,), torch.float32)
+        if distance not in ("feat", "lpips"):
+            raise CtsiError(f"internal: unknown feature distance {distance!r}")
+        self.lpips = distance == "lpips"
+        if self.lpips:
+            if heads is None or len(heads) != nl or any(modules[i][0] != "relu" for i in self.layers):
+                raise CtsiError("internal: the LPIPS distance needs one head per tap and taps at ReLU outputs")
+            self.blocks = lib.lpips_blocks()
+            self.partials = self.persistent((nl * n_img * self.blocks,), torch.float64)
+            self.out = self.persistent((n_img + nl,), torch.float32)          # per-image values, then the tap means
+            self.gl = self.persistent((n_img,), torch.float32)                # the upstream gradient, per image
+            self.track(*heads)
+            head_bufs = [self.dev_f32(lambda t=t: t.reshape(-1)) for t in heads]
+        else:
+            self.blocks = lib.feat_loss_blocks()
+            self.partials = self.persistent((nl * self.blocks,), torch.float64)
+            self.out = self.persistent((1 + nl,), torch.float32)
+            self.gl = self.persistent((1,), torch.float32)
         self.xin = Act(self.persistent((n2 * h * w * 8,), torch.bfloat16), 1, 8, n2, h, w)
         self.generation = 0
 
         # ---- forward --------------------------------------------------------------------------------------------------------
         nodes, x = [], self.xin
-        for i, m in enumerate(VGG19_MODULES[:last + 1]):
+        for i, m in enumerate(modules[:last + 1]):
             if m[0] == "conv":
                 conv = convs[i]
                 self.track(conv.weight, conv.bias)
@@ -102,8 +130,21 @@ class VGGLossProgram(Program):
             a = node["out"]
             half = n_img * a.h * a.w * a.c
             for l in node["feats"]:
+                pp, tp = a.ip, C.c_void_p(a.ip.value + 2 * half)
+                if self.lpips:
+                    pos = a.h * a.w
+                    counts[l] = pos                    # LPIPS means over positions, per image
+                    if a.c != head_bufs[l].numel():
+                        raise CtsiError(f"LPIPS head {l} has {head_bufs[l].numel()} weights, its tap has {a.c} channels")
+                    hp, dst = _ptr(head_bufs[l]), C.c_void_p(self.partials.data_ptr() + 8 * l * n_img * self.blocks)
+
+                    def run_dist(pp=pp, tp=tp, hp=hp, dst=dst, pos=pos, c=a.c):
+                        lib.lpips_dist_fwd(pp, tp, hp, n_img, pos, c, dst, sptr)
+
+                    self._emit(run_dist, f"vgg.{node['i']}.lpips", 0.0, "lpips_dist", nbytes=4.0 * half)
+                    continue
                 counts[l] = half
-                pp, tp, dst = a.ip, C.c_void_p(a.ip.value + 2 * half), C.c_void_p(self.partials.data_ptr() + 8 * l * self.blocks)
+                dst = C.c_void_p(self.partials.data_ptr() + 8 * l * self.blocks)
 
                 def run_loss(pp=pp, tp=tp, dst=dst, half=half):
                     lib.feat_loss_fwd(pp, tp, half, sq, dst, sptr)
@@ -113,10 +154,18 @@ class VGGLossProgram(Program):
         self.counts.copy_(torch.tensor(counts, dtype=torch.int64))
         pa, cn, ob = _ptr(self.partials), _ptr(self.counts), _ptr(self.out)
 
-        def run_fin():
-            lib.feat_loss_finalize(pa, cn, nl, ob, sptr)
+        if self.lpips:
+            tm = C.c_void_p(self.out.data_ptr() + 4 * n_img)
 
-        self._emit(run_fin, "vgg.loss.finalize", 0.0, "feat_loss_finalize")
+            def run_fin():
+                lib.lpips_finalize(pa, cn, nl, n_img, ob, tm, sptr)
+
+            self._emit(run_fin, "vgg.lpips.finalize", 0.0, "lpips_finalize")
+        else:
+            def run_fin():
+                lib.feat_loss_finalize(pa, cn, nl, ob, sptr)
+
+            self._emit(run_fin, "vgg.loss.finalize", 0.0, "feat_loss_finalize")
         self.n_fwd = len(self.ops)
 
         # ---- backward (pred half) ------------------------------------------------------------------------------------------
@@ -126,7 +175,18 @@ class VGGLossProgram(Program):
         for node in reversed(nodes):
             a = node["out"]
             half = n_img * a.h * a.w * a.c
-            if node["feats"] or node["relu"]:
+            if self.lpips and node["feats"]:
+                l, = node["feats"]
+                gout = g if g is not None else self.act(1, a.c, n_img, a.h, a.w)
+                gi, yp, tp, go = (g.ip if g is not None else C.c_void_p(0)), a.ip, C.c_void_p(a.ip.value + 2 * half), gout.ip
+                hp = _ptr(head_bufs[l])
+
+                def run_lgrad(gi=gi, yp=yp, tp=tp, hp=hp, go=go, pos=a.h * a.w, c=a.c):
+                    lib.lpips_grad_relu_bwd(gi, yp, tp, hp, go, n_img, pos, c, glp, sptr)
+
+                self._emit(run_lgrad, f"vgg.{node['i']}.grad", 0.0, "lpips_grad_relu_bwd", nbytes=8.0 * half)
+                g = gout
+            elif node["feats"] or node["relu"]:
                 if g is None and not node["feats"]:
                     raise CtsiError("internal: no gradient reaches the deepest VGG layer")
                 kind = kind_loss if node["feats"] else 0
@@ -212,6 +272,40 @@ class VGGLossProgram(Program):
         out = self.out.clone()
         self.check_errors()
         return out
+
+    def run_forward_images(self, in0: torch.Tensor, in1: torch.Tensor, normalize: bool) -> torch.Tensor:
+        """LPIPS: in0, in1 fp32 contiguous (N, 1 | 3, H, W) device tensors; returns the fp32 device tensor [N per-image values,
+        tap means]."""
+        n, c = in0.shape[:2]
+        if n != self.n_img or not self.lpips:
+            raise CtsiError("internal: the LPIPS program was built for another number of images")
+        self.ensure_fresh()
+        self.generation += 1
+        lib, sptr = self.lib, self.ctx.sptr
+        half_bytes = self.n_img * self.h * self.w * 8 * 2
+        lib.lpips_prep(_ptr(in0), self.xin.ip, n, c, self.h, self.w, int(normalize), sptr)
+        lib.lpips_prep(_ptr(in1), C.c_void_p(self.xin.ip.value + half_bytes), n, c, self.h, self.w, int(normalize), sptr)
+        in0.record_stream(self.ctx.stream)
+        in1.record_stream(self.ctx.stream)
+        for op in self.ops[:self.n_fwd]:
+            op()
+        out = self.out.clone()
+        self.check_errors()
+        return out
+
+    def run_backward_images(self, grad_out: torch.Tensor, c: int, normalize: bool, generation: int) -> torch.Tensor:
+        """grad_out: (N,) fp32 device; returns the gradient of in0, fp32 (N, c, H, W)."""
+        if generation != self.generation:
+            raise CtsiError("backward of an LPIPS forward whose saved activations were overwritten (internal: a program was "
+                            "handed out twice)")
+        lib, sptr = self.lib, self.ctx.sptr
+        self.gl.copy_(grad_out.reshape(self.n_img))
+        for op in self.ops[self.n_fwd:]:
+            op()
+        grad = torch.empty((self.n_img, c, self.h, self.w), dtype=torch.float32, device=self.ctx.device)
+        lib.lpips_prep_bwd(self.g_in.ip, _ptr(grad), self.n_img, c, self.h, self.w, int(normalize), sptr)
+        self.check_errors()
+        return grad
 
     def run_backward(self, grad_loss: torch.Tensor, slices: torch.Tensor, norm: torch.Tensor, b: int, d: int, num: int,
                      generation: int) -> torch.Tensor:
