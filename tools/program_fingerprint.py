@@ -1,11 +1,12 @@
 """What the engine's program builders emit, as text two commits can be compared on.  For each of a fixed set of small
 programs (formula weights from tests/helpers.py; every path a conv can take: single-GPU, guided, fp32 and bf16x3 on all
-three column tiles, depth-sharded with and without the overlap split, the VAE legs, both training programs) one line per
-op -- name, flops, kernel label, bytes, algorithmic bytes, the audit record's kind and a digest of its key set -- then the
-program's totals, the packed-weight cache keys it added and a SHA-256 of every output after an eager run (the U-Nets: again
-after capture() + two launch()es; the training programs: of every weight image after repack() and after an in-place update
-+ fast_repack()).  The long uniform lists (op lines other than the launches of an overlapped conv, cache keys, weight
-images) are folded into one digest line each; --full prints them line by line, to find what a digest that differs hides.
+three column tiles, depth-sharded with and without the overlap split, the VAE legs, both training programs, the
+differentiable decode, the VGG-19 and LPIPS losses) one line per op -- name, flops, kernel label, bytes, algorithmic bytes,
+the audit record's kind and a digest of its key set -- then the program's totals, the packed-weight cache keys it added and a
+SHA-256 of every output after an eager run (the U-Nets: again after capture() + two launch()es; the training programs: of
+every weight image after repack() and after an in-place update + fast_repack(), and of every parameter gradient of a
+backward).  The long uniform lists (op lines other than the launches of an overlapped conv, cache keys, weight images,
+gradients) are folded into one digest line each; --full prints them line by line, to find what a digest that differs hides.
 
     python tools/program_fingerprint.py [--full] > out.txt           # on a ROCm device
     python tools/program_fingerprint.py --compare a1.txt a2.txt b.txt
@@ -201,7 +202,8 @@ def main():
     section("vae.dec.world2", build_dec2, run_dec2)
 
     # ---- training programs: private weight images, the generic and the fast re-pack -----------------------------------------
-    def train_run(pr, params, fwd):
+    def train_run(pr, params, fwd, bwd):
+        """`bwd()` -> the parameter gradients of the latest forward, in `params` order."""
         yield from fwd()
         pr.repack()
         for i, ent in enumerate(pr._pack_meta):
@@ -214,6 +216,8 @@ def main():
         for i, ent in enumerate(pr._pack_meta):
             yield f"fast_repack.image{i}", ent["holder"][0]
         yield from fwd()
+        for i, g in enumerate(bwd()):
+            yield f"grad.image{i}", g
 
     un = unet(TINY_UNET)
     shape = (1, 8, 4, 8, 8)
@@ -227,11 +231,50 @@ def main():
         return [pr]
 
     section("train.unet", build_ut, lambda ps: train_run(
-        ps[0], list(un.parameters()), lambda: [("loss", ps[0].run_forward(z0, cond, t, noise, norm))]))
+        ps[0], list(un.parameters()), lambda: [("loss", ps[0].run_forward(z0, cond, t, noise, norm))],
+        lambda: ps[0].run_backward(torch.ones(1, device=DEV))))
     vae.train()
     xv = formula_input((1, 1, 3, 16, 12), 18).clamp(-1, 1).to(DEV)
+    g_recon, g_lat = formula_input((1, 1, 3, 16, 12), 23).to(DEV), formula_input((1, 8, 3, 4, 3), 24).to(DEV)
     section("train.vae", lambda: [V.VAETrainProgram(ctx, vae, 1, 3, 16, 12)], lambda ps: train_run(
-        ps[0], list(vae.parameters()), lambda: list(zip(("recon", "z"), ps[0].run_forward(xv)))))
+        ps[0], list(vae.parameters()), lambda: list(zip(("recon", "z"), ps[0].run_forward(xv))),
+        lambda: ps[0].run_backward(g_recon, g_lat)))
+
+    # ---- the differentiable decode: the decoder half of train.vae, data gradients only ----------------------------------
+    def run_decgrad(ps):
+        yield "recon", ps[0].run_forward(lat.to(DEV))
+        yield "g_z", ps[0].run_backward(g_recon)
+
+    section("train.decgrad", lambda: [V.VAEDecodeGradProgram(ctx, vae, 1, 3, 4, 3)], run_decgrad)
+
+    # ---- the feature losses, through their modules (the program comes out of the module's pool after the call) ----------
+    LS = importlib.import_module("video-to-video-diffusion_amd.losses")
+    from tests.lpips_restatement import he_state_dict as he_vgg16  # noqa: E402
+    from tests.vgg_restatement import he_state_dict as he_vgg19  # noqa: E402
+
+    def loss_section(tag, module, shape, n_img, outputs):
+        """outputs(module, out) -> [(name, tensor)] besides the input gradient."""
+        module.to(DEV)
+        a = formula_input(shape, 30).clamp(-1, 1).to(DEV).requires_grad_(True)
+        b = formula_input(shape, 31).clamp(-1, 1).to(DEV)
+        res = []
+
+        def build():
+            out = module(a, b)
+            out.sum().backward()
+            res.extend(outputs(module, out.detach()) + [("grad", a.grad)])
+            return [module._take_program(ctx, n_img, *shape[-2:])]
+
+        def run(ps):
+            module._give_program(ps[0])
+            return res
+
+        section(tag, build, run)
+
+    loss_section("loss.vgg19", LS.VGGPerceptualLoss(feature_layers=[2, 7], slice_sample_rate=1.0, weights=he_vgg19(40, upto=7)),
+                 (1, 1, 2, 16, 16), 2, lambda m, out: [("loss", out), ("layer_means", m.last_layer_means)])
+    loss_section("loss.lpips", LS.LPIPS(weights=he_vgg16(41), lpips=False), (2, 3, 16, 16), 2,
+                 lambda m, out: [("values", out), ("layer_means", m.last_layer_means)])
 
 
 def compare(a1, a2, b):

@@ -1134,6 +1134,43 @@ class Program:
             pass
 
 
+class PhasedProgram(Program):
+    """A program built as a forward followed by a backward and replayed one half at a time (the training programs, the
+    differentiable decode, the VGG / LPIPS loss).  `ops[:n_fwd]` is the forward.  It overwrites the activations the backward
+    reads, so every forward bumps `generation` and a backward names the generation it belongs to: one that belongs to an
+    EARLIER forward fails loudly instead of differentiating through the wrong activations
+    (l1 = model(a); l2 = model(b); (l1 + l2).backward())."""
+    stale_msg = ""     # the CtsiError text of such a backward; may name {then} and {now}
+
+    def __init__(self, ctx: Ctx):
+        super().__init__(ctx)
+        self.n_fwd = 0
+        self.generation = 0
+
+    def end_forward(self):
+        """Build time: every op emitted so far is the forward, whatever follows the backward."""
+        self.n_fwd = len(self.ops)
+
+    def forward_ops(self, load: Optional[Callable[[], None]] = None):
+        """Refresh the weight images, start a new generation, `load()` the inputs and run the forward."""
+        self.ensure_fresh()
+        self.generation += 1
+        if load is not None:
+            load()
+        for op in self.ops[:self.n_fwd]:
+            op()
+
+    def backward_ops(self, generation: Optional[int], load: Optional[Callable[[], None]] = None):
+        """Run the backward of the forward that started `generation` (None: unchecked), after `load()` took the incoming
+        gradients; nothing is touched when that forward's activations are gone."""
+        if generation is not None and generation != self.generation:
+            raise CtsiError(self.stale_msg.format(then=generation, now=self.generation))
+        if load is not None:
+            load()
+        for op in self.ops[self.n_fwd:]:
+            op()
+
+
 # ==========================================================================================================
 # U-Net
 # ==========================================================================================================

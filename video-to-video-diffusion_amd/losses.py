@@ -121,17 +121,77 @@ def _vgg_state_dict(weights) -> Dict[str, torch.Tensor]:
     return weights
 
 
-def _vgg_param(sd: Dict[str, torch.Tensor], idx: int, kind: str, shape: Tuple[int, ...]) -> torch.Tensor:
-    """`features.{idx}.{kind}` or `{idx}.{kind}` (torchvision's names for the whole model / its `features`), shape-checked."""
-    names = (f"features.{idx}.{kind}", f"{idx}.{kind}")
+def _conv_param(sd: Dict[str, torch.Tensor], idx: int, kind: str, shape: Tuple[int, ...], label: str,
+                extra_names: Sequence[str] = ()) -> torch.Tensor:
+    """`features.{idx}.{kind}` or `{idx}.{kind}` (torchvision's names for the whole model / its `features`), or one of
+    `extra_names` with 1 .. 5 for its '<k>' (lpips' `net.slice<k>.{idx}.{kind}`), shape-checked."""
+    names = [f"features.{idx}.{kind}", f"{idx}.{kind}"] + [e.replace("<k>", str(k)) for e in extra_names for k in range(1, 6)]
     name = next((n for n in names if n in sd), None)
     if name is None:
-        raise ValueError(f"VGG-19 weights: key '{names[0]}' (or '{names[1]}') is missing")
+        extra = "".join(f", or '{e}'" for e in extra_names)
+        raise ValueError(f"{label} weights: key '{names[0]}' (or '{names[1]}'{extra}) is missing")
     t = sd[name]
     if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape):
         got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
-        raise ValueError(f"VGG-19 weights: key '{name}' has shape {got}, expected {tuple(shape)}")
+        raise ValueError(f"{label} weights: key '{name}' has shape {got}, expected {tuple(shape)}")
     return t
+
+
+def _frozen_convs(sd: Dict[str, torch.Tensor], modules: Sequence[tuple], label: str,
+                  extra_names: Sequence[str] = ()) -> Dict[int, nn.Conv2d]:
+    """{module index: nn.Conv2d} of the convs of a module table (vgg_loss_engine.feature_modules), filled from `sd`;
+    `extra_names` may name {idx} and {kind}."""
+    convs = {}
+    for i, m in enumerate(modules):
+        if m[0] == "conv":
+            conv = convs[i] = nn.Conv2d(m[1], m[2], kernel_size=3, padding=1)
+            with torch.no_grad():
+                for kind, shape in (("weight", (m[2], m[1], 3, 3)), ("bias", (m[2],))):
+                    extra = [e.format(idx=i, kind=kind) for e in extra_names]
+                    getattr(conv, kind).copy_(_conv_param(sd, i, kind, shape, label, extra))
+    return convs
+
+
+def _rate_slices(depth: int, rate: float) -> torch.Tensor:
+    """`max(1, int(depth * rate))` evenly spaced slices of `depth` (host, int64): the reference's own expression."""
+    num = max(1, int(depth * rate))
+    if num < depth:
+        return torch.linspace(0, depth - 1, num, dtype=torch.long)
+    return torch.arange(depth, dtype=torch.long)
+
+
+class _ProgramPool:
+    """Free programs of a loss module per (device index, images, h, w), kept where engine.invalidate_engine_cache finds them.
+    A forward in grad mode owns its program (it holds the activations) until its backward has run, so two losses of one shape
+    in one graph never share one; a program that comes back after the cache was dropped is not kept."""
+
+    def _take_program(self, ctx: Ctx, n_img: int, h: int, w: int) -> VGGLossProgram:
+        key = (ctx.device.index, n_img, h, w)
+        cache = self.__dict__.setdefault("_ctsi_programs", {})
+        free = cache.setdefault(key, [])
+        if free:
+            return free.pop()
+        prog = self._build_program(ctx, n_img, h, w)
+        prog.key, prog.home = key, cache
+        return prog
+
+    def _give_program(self, prog: VGGLossProgram):
+        if self.__dict__.get("_ctsi_programs") is prog.home:
+            prog.home.setdefault(prog.key, []).append(prog)
+
+
+def _owned_program(fctx, name: str) -> VGGLossProgram:
+    """The program a forward in grad mode kept for its backward."""
+    prog = getattr(fctx, "prog", None)
+    if prog is None:
+        raise CtsiError(f"{name}: backward ran twice on one forward (the saved activations are released after the first "
+                        "backward); run the forward again")
+    return prog
+
+
+def _hand_back(fctx, prog: VGGLossProgram):
+    fctx.owner._give_program(prog)
+    fctx.prog = None
 
 
 class _VGGLossFn(torch.autograd.Function):
@@ -148,7 +208,7 @@ class _VGGLossFn(torch.autograd.Function):
             slices = idx.to(device=pred.device, dtype=torch.int32)
             norm = torch.cat([owner.mean.reshape(-1), owner.std.reshape(-1)]).to(device=pred.device, dtype=torch.float32)
             prog = owner._take_program(ctx, b * num, h, w)
-            out = prog.run_forward(pred, target, slices, norm, b, d, num)
+            out = prog.run_forward(pred, target, (slices, norm, b, d, num))
         owner.last_layer_means = out[1:]
         if want_grad:
             fctx.save_for_backward(slices, norm)
@@ -160,21 +220,15 @@ class _VGGLossFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(fctx, grad_loss):
-        prog = getattr(fctx, "prog", None)
-        if prog is None:
-            raise CtsiError("VGGPerceptualLoss: backward ran twice on one forward (the saved activations are released after "
-                            "the first backward); run the forward again")
-        slices, norm = fctx.saved_tensors
-        b, d, num = fctx.dims
+        prog = _owned_program(fctx, "VGGPerceptualLoss")
         with prog.ctx.scope():
             g = grad_loss.detach().to(torch.float32).contiguous()
-            grad_pred = prog.run_backward(g, slices, norm, b, d, num, fctx.generation)
-        fctx.owner._give_program(prog)
-        fctx.prog = None
+            grad_pred = prog.run_backward(g, fctx.saved_tensors + fctx.dims, fctx.generation)
+        _hand_back(fctx, prog)
         return grad_pred, None, None, None
 
 
-class VGGPerceptualLoss(nn.Module):
+class VGGPerceptualLoss(_ProgramPool, nn.Module):
     """The reference's VGG-19 perceptual loss on sampled 2-D slices, forward and backward on the HIP engine.
 
     Args as the reference's (feature_layers: strictly increasing indices into VGG-19 `features`, 0-36; use_l1; slice_sample_rate)
@@ -206,19 +260,14 @@ class VGGPerceptualLoss(nn.Module):
         self.use_l1 = use_l1
         self.slice_sample_rate = slice_sample_rate
         self.vgg_blocks = nn.ModuleList()
-        self._convs: Dict[int, nn.Conv2d] = {}
+        self._convs = _frozen_convs(sd, VGG19_MODULES[:layers[-1] + 1], "VGG-19")
         prev = 0
         for idx in layers:
             block = []
             for i in range(prev, idx + 1):
                 m = VGG19_MODULES[i]
                 if m[0] == "conv":
-                    conv = nn.Conv2d(m[1], m[2], kernel_size=3, padding=1)
-                    with torch.no_grad():
-                        conv.weight.copy_(_vgg_param(sd, i, "weight", (m[2], m[1], 3, 3)))
-                        conv.bias.copy_(_vgg_param(sd, i, "bias", (m[2],)))
-                    self._convs[i] = conv
-                    block.append(conv)
+                    block.append(self._convs[i])
                 elif m[0] == "relu":
                     block.append(nn.ReLU(inplace=True))
                 else:
@@ -234,27 +283,10 @@ class VGGPerceptualLoss(nn.Module):
 
     def slice_indices(self, depth: int) -> torch.Tensor:
         """The sampled slices of a volume of `depth` slices (host, int64): the reference's own expression."""
-        num = max(1, int(depth * self.slice_sample_rate))
-        if num < depth:
-            return torch.linspace(0, depth - 1, num, dtype=torch.long)
-        return torch.arange(depth, dtype=torch.long)
+        return _rate_slices(depth, self.slice_sample_rate)
 
-    # free programs per (device index, images, h, w), kept where engine.invalidate_engine_cache finds them.  A forward in grad
-    # mode owns its program (it holds the activations) until its backward has run, so two losses of one shape in one graph
-    # never share one; a program that comes back after the cache was dropped is not kept.
-    def _take_program(self, ctx: Ctx, n_img: int, h: int, w: int) -> VGGLossProgram:
-        key = (ctx.device.index, n_img, h, w)
-        cache = self.__dict__.setdefault("_ctsi_programs", {})
-        free = cache.setdefault(key, [])
-        if free:
-            return free.pop()
-        prog = VGGLossProgram(ctx, self._convs, self.feature_layers, bool(self.use_l1), n_img, h, w)
-        prog.key, prog.home = key, cache
-        return prog
-
-    def _give_program(self, prog: VGGLossProgram):
-        if self.__dict__.get("_ctsi_programs") is prog.home:
-            prog.home.setdefault(prog.key, []).append(prog)
+    def _build_program(self, ctx: Ctx, n_img: int, h: int, w: int) -> VGGLossProgram:
+        return VGGLossProgram(ctx, self._convs, self.feature_layers, bool(self.use_l1), n_img, h, w)
 
     def forward(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         if not isinstance(pred, torch.Tensor) or not isinstance(target, torch.Tensor) or pred.dim() != 5:
@@ -274,19 +306,6 @@ class VGGPerceptualLoss(nn.Module):
         p = pred.to(torch.float32).contiguous()             # outside the Function: autograd carries dtype and layout
         t = target.detach().to(torch.float32).contiguous()
         return _VGGLossFn.apply(p, t, self, torch.is_grad_enabled() and p.requires_grad)
-
-
-def _lpips_conv_param(sd: Dict[str, torch.Tensor], idx: int, kind: str, shape: Tuple[int, ...]) -> torch.Tensor:
-    """Conv `idx` of torchvision's VGG-16 `features` under `features.{idx}.`, `{idx}.` or lpips' `net.slice{k}.{idx}.`."""
-    names = [f"features.{idx}.{kind}", f"{idx}.{kind}"] + [f"net.slice{k}.{idx}.{kind}" for k in range(1, 6)]
-    name = next((n for n in names if n in sd), None)
-    if name is None:
-        raise ValueError(f"VGG-16 weights: key '{names[0]}' (or '{names[1]}', or 'net.slice<k>.{idx}.{kind}') is missing")
-    t = sd[name]
-    if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape):
-        got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
-        raise ValueError(f"VGG-16 weights: key '{name}' has shape {got}, expected {tuple(shape)}")
-    return t
 
 
 def _lpips_head(src, k: int, channels: int) -> Optional[torch.Tensor]:
@@ -312,7 +331,7 @@ class _LPIPSFn(torch.autograd.Function):
         n, c, h, w = in0.shape
         with ctx.scope():
             prog = owner._take_program(ctx, n, h, w)
-            out = prog.run_forward_images(in0, in1, normalize)
+            out = prog.run_forward(in0, in1, (c, bool(normalize)))
         owner.last_layer_means = out[n:]
         if want_grad:
             fctx.prog, fctx.owner, fctx.generation, fctx.args = prog, owner, prog.generation, (c, bool(normalize))
@@ -323,20 +342,15 @@ class _LPIPSFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(fctx, grad_out):
-        prog = getattr(fctx, "prog", None)
-        if prog is None:
-            raise CtsiError("LPIPS: backward ran twice on one forward (the saved activations are released after the first "
-                            "backward); run the forward again")
-        c, normalize = fctx.args
+        prog = _owned_program(fctx, "LPIPS")
         with prog.ctx.scope():
             g = grad_out.detach().to(torch.float32).reshape(-1).contiguous()
-            grad = prog.run_backward_images(g, c, normalize, fctx.generation)
-        fctx.owner._give_program(prog)
-        fctx.prog = None
+            grad = prog.run_backward(g, fctx.args, fctx.generation)
+        _hand_back(fctx, prog)
         return grad, None, None, None, None
 
 
-class LPIPS(nn.Module):
+class LPIPS(_ProgramPool, nn.Module):
     """The `lpips` package's distance (0.1.x, net='vgg', spatial=False, eval mode), forward and backward on the HIP engine.
 
     `weights`: a state dict (or a path to one, `torch.load(..., weights_only=True)`) of torchvision's VGG-16
@@ -374,16 +388,8 @@ class LPIPS(nn.Module):
         sd = _vgg_state_dict(weights)
         self.slices = slices
         self.lpips = bool(lpips)
-        self.net = nn.ModuleList()
-        self._convs: Dict[int, nn.Conv2d] = {}
-        for i, m in enumerate(VGG16_MODULES):
-            if m[0] == "conv":
-                conv = nn.Conv2d(m[1], m[2], kernel_size=3, padding=1)
-                with torch.no_grad():
-                    conv.weight.copy_(_lpips_conv_param(sd, i, "weight", (m[2], m[1], 3, 3)))
-                    conv.bias.copy_(_lpips_conv_param(sd, i, "bias", (m[2],)))
-                self._convs[i] = conv
-                self.net.append(conv)
+        self._convs = _frozen_convs(sd, VGG16_MODULES, "VGG-16", ("net.slice<k>.{idx}.{kind}",))
+        self.net = nn.ModuleList(self._convs.values())
         heads = []
         for k, c in enumerate(self.CHANNELS):
             if not self.lpips:
@@ -409,24 +415,11 @@ class LPIPS(nn.Module):
             return torch.tensor([depth // 2], dtype=torch.long)
         if self.slices == 'all':
             return torch.arange(depth, dtype=torch.long)
-        num = max(1, int(depth * self.slices))
-        if num < depth:
-            return torch.linspace(0, depth - 1, num, dtype=torch.long)
-        return torch.arange(depth, dtype=torch.long)
+        return _rate_slices(depth, self.slices)
 
-    # free programs per (device index, images, h, w), as VGGPerceptualLoss keeps them
-    def _take_program(self, ctx: Ctx, n_img: int, h: int, w: int) -> VGGLossProgram:
-        key = (ctx.device.index, n_img, h, w)
-        cache = self.__dict__.setdefault("_ctsi_programs", {})
-        free = cache.setdefault(key, [])
-        if free:
-            return free.pop()
-        prog = VGGLossProgram(ctx, self._convs, list(LPIPS_TAPS), False, n_img, h, w, modules=VGG16_MODULES, distance="lpips",
+    def _build_program(self, ctx: Ctx, n_img: int, h: int, w: int) -> VGGLossProgram:
+        return VGGLossProgram(ctx, self._convs, list(LPIPS_TAPS), False, n_img, h, w, modules=VGG16_MODULES, distance="lpips",
                               heads=list(self.lins))
-        prog.key, prog.home = key, cache
-        return prog
-
-    _give_program = VGGPerceptualLoss._give_program
 
     def forward(self, in0: torch.Tensor, in1: torch.Tensor, normalize: bool = False) -> torch.Tensor:
         if not isinstance(in0, torch.Tensor) or not isinstance(in1, torch.Tensor) or in0.dim() not in (4, 5):

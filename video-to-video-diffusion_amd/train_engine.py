@@ -31,19 +31,62 @@ import torch.nn as nn
 
 from .attention import check_attention_mode, emit_softmax_attention_train
 from .spatial_attention import check_spatial_attention_supported, emit_spatial_attention_train
-from .engine import Act, Ctx, Program, _ptr
+from .engine import Act, Ctx, PhasedProgram, _ptr
 from .lib import CtsiError, WgradDesc
 from .norm_mod import DropoutState, emit_gn_bwd_mod
 from .learned_sigma import emit_hybrid_loss, loss_schedule_rows
 from .prediction import check_prediction_type
 
 
-class TrainProgram(Program):
+class TrainProgram(PhasedProgram):
     """Shared machinery of the training programs (U-Net here, VAE in vae_train_engine.py): the gradient arena, the conv and
     GroupNorm forward wrappers that record their backward on a tape, and the backward launches themselves."""
     tbias = None       # time-bias rows of the U-Net (programs without a time embedding leave these unset)
     total_out = 0
     data_only = False  # True: a backward of data gradients only (vae_train_engine.VAEDecodeGradProgram): no parameter buffers
+
+    def __init__(self, ctx: Ctx, module: nn.Module, arena_floats: int, workspaces=("wgrad", "gn", "chsum")):
+        """`module`: whose parameters the program differentiates (and watches: needs_rebuild, Program.track_module).  Every
+        parameter-gradient buffer is a piece of ONE fp32 arena of `arena_floats`, so that the hand-over to autograd is one copy
+        instead of one per parameter (333 launches, 1.6 ms of a config-3 micro-step); size it with slack for the row padding of
+        the conv layouts.  `workspaces`: names of the byte workspaces the backward launches share (`_need` -> `_ws`)."""
+        super().__init__(ctx)
+        self.weight_cache = self.data_only    # trained weights change every optimizer step: private images, repacked in place
+        self.tape: List[Callable[[], None]] = []
+        self.grads: Dict[int, torch.Tensor] = {}     # id(param) -> fp32 gradient buffer (maybe padded)
+        self._need = {key: 16 for key in workspaces}
+        self._ws: Dict[str, Optional[torch.Tensor]] = {key: None for key in workspaces}
+        self.params = list(module.parameters())
+        self.track_module(module)
+        self._garena = self.persistent((arena_floats,), torch.float32, zero=True)
+        self._garena_used = 0
+
+    def finish_build(self, before_layout: Optional[Callable[[], None]] = None):
+        """Close the build after the head of the backward was emitted: the tape in reverse, `before_layout()` for launches that
+        follow it, then the statistics buffers and the workspaces at the sizes the launches asked for."""
+        for fn in reversed(self.tape):
+            fn()
+        if before_layout is not None:
+            before_layout()
+        self.finalize_layout()
+        for key, need in self._need.items():
+            self._ws[key] = torch.empty(need, dtype=torch.uint8, device=self.ctx.device)
+
+    def needs_rebuild(self) -> bool:
+        """The autograd bridge hands gradients to the Parameter objects captured at build time: a replaced
+        parameter (load_state_dict(assign=True), module.weight = ...) needs a new program, not just a repack."""
+        cur = list(self._track_module.parameters())
+        return len(cur) != len(self.params) or any(a is not b for a, b in zip(cur, self.params))
+
+    def param_grads(self) -> List[torch.Tensor]:
+        """The gradient buffers in `params` order, each cut back from its padded layout to the parameter's own shape."""
+        out = []
+        for p in self.params:
+            g = self.grads.get(id(p))
+            if g is None:
+                raise CtsiError("internal: a parameter received no gradient buffer")
+            out.append(g if g.shape == p.shape else g[tuple(slice(0, s) for s in p.shape)])
+        return out
 
     def _ws_ptr(self, key):
         return C.c_void_p(self._ws[key].data_ptr())
@@ -298,6 +341,11 @@ class TrainProgram(Program):
 
 
 class UNetTrainProgram(TrainProgram):
+    stale_msg = ("backward of a training forward whose saved activations were overwritten: another forward of the same "
+                 "shape ran on this program in between (tape generation {then}, now {now}).  Call "
+                 "backward() before the next forward of that shape, or evaluate the second batch under torch.no_grad() "
+                 "through model.generate / unet(x, t, c), which do not touch the training tape.")
+
     def __init__(self, ctx: Ctx, unet, n: int, d: int, h: int, w: int, prediction: str = "epsilon", dropout: bool = False):
         """`prediction` = 'v_prediction' (DESIGN section 18): the inputs come from ctsi_q_sample_v, which also writes the
         target v into `v_target`, and both loss launches read that buffer where the epsilon program reads the noise.
@@ -306,12 +354,11 @@ class UNetTrainProgram(TrainProgram):
         A `unet.learn_sigma` model: the head, its weight gradient and its data gradient are 2L channels wide
         (`eps` then holds both halves, `d_eps` both gradients), and the loss pair is ctsi_hybrid_loss_fwd / _bwd, which read
         z0, the noise and the per-timestep rows `lv_sched` (set_diffusion) instead of a target buffer."""
-        super().__init__(ctx)
+        super().__init__(ctx, unet, sum(p.numel() for p in unet.parameters()) + (16 << 20))
         self.learn_sigma = bool(getattr(unet, "learn_sigma", False))
         self.film = bool(getattr(unet, "use_scale_shift_norm", False))
         self.drop_state = DropoutState(self.persistent((1,), torch.int64, zero=True)) if dropout else None
         self.prediction = check_prediction_type(prediction)
-        self.weight_cache = False    # weights change every optimizer step: private images, repacked in place
         self.attention_mode = check_attention_mode(unet.attention_mode)
         if self.attention_mode == "exact":
             raise CtsiError("training supports attention_mode='fast' and 'softmax' (the exact mode multiplies in a row sum "
@@ -324,19 +371,8 @@ class UNetTrainProgram(TrainProgram):
         if unet.conv_out[2].out_channels != Lo:
             raise CtsiError(f"internal: the head has {unet.conv_out[2].out_channels} channels, expected {Lo}")
         self.Lp = (Lo + 7) // 8 * 8
-        dev = ctx.device
         vox = d * h * w
-        self.tape: List[Callable[[], None]] = []
         self._deferred_lin: List[tuple] = []     # small pointwise layers whose weight / bias gradients go into ONE launch at the end
-        self.grads: Dict[int, torch.Tensor] = {}     # id(param) -> fp32 gradient buffer (maybe padded)
-        self._need = dict(wgrad=16, gn=16, chsum=16)
-        self._ws: Dict[str, Optional[torch.Tensor]] = dict(wgrad=None, gn=None, chsum=None)
-        self.params = [p for p in unet.parameters()]
-        self.track_module(unet)
-        # every parameter-gradient buffer is a piece of ONE fp32 arena, so that the hand-over to autograd is one copy instead of
-        # one per parameter (333 launches, 1.6 ms of a config-3 micro-step); the slack takes the row padding of the conv layouts
-        self._garena = self.persistent((sum(p.numel() for p in self.params) + (16 << 20),), torch.float32, zero=True)
-        self._garena_used = 0
         for p in self.params:
             if not p.is_cuda:
                 raise CtsiError("training runs on the HIP engine: move the model to a ROCm device first")
@@ -461,8 +497,7 @@ class UNetTrainProgram(TrainProgram):
             self._emit(run_loss, "loss.fwd", audit=dict(
                 kind="loss.fwd", pred=self.eps, noise=self.target, mask=lambda: prog.mask if prog.use_mask else None,
                 norm=self.norm, out=self.loss_out))
-        self.n_fwd = len(self.ops)
-        self.generation = 0   # bumped by every run_forward (see there)
+        self.end_forward()
 
         # ---- backward: loss, then the tape in reverse, then the time embedding ---------------------------------
         # the predicted clean latent as a second output (train_step_pred): buffers made on first use, the
@@ -485,13 +520,12 @@ class UNetTrainProgram(TrainProgram):
             self._emit(run_loss_bwd, "loss.bwd", audit=dict(
                 kind="loss_bwd", pred=self.eps, noise=self.target, mask=lambda: prog.mask if prog.use_mask else None,
                 norm=self.norm, gscale=self.gscale, out=self.d_eps))
-        for fn in reversed(self.tape):
-            fn()
-        self._emit_deferred_lin()
-        self._time_embed_bwd()
-        self.finalize_layout()
-        for key, need in self._need.items():
-            self._ws[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+
+        def tail():
+            self._emit_deferred_lin()
+            self._time_embed_bwd()
+
+        self.finish_build(tail)
 
     def _emit_deferred_lin(self):
         """ONE launch for the weight and bias gradients of every deferred pointwise layer (the 22 attention projections):
@@ -668,12 +702,6 @@ class UNetTrainProgram(TrainProgram):
             self.grads[id(m.time_mlp[1].weight)] = self.g_w_all[off:off + co]
             self.grads[id(m.time_mlp[1].bias)] = self.g_b_all[off:off + co]
 
-    def needs_rebuild(self) -> bool:
-        """The autograd bridge hands gradients to the Parameter objects captured at build time: a replaced
-        parameter (load_state_dict(assign=True), module.weight = ...) needs a new program, not just a repack."""
-        cur = list(self.unet.parameters())
-        return len(cur) != len(self.params) or any(a is not b for a, b in zip(cur, self.params))
-
     # ---- execution ---------------------------------------------------------------------------------------------------------
     def set_diffusion(self, diffusion):
         self.sqrt_ac = diffusion.sqrt_alphas_cumprod.detach().to(self.ctx.device, torch.float32).contiguous()
@@ -697,23 +725,21 @@ class UNetTrainProgram(TrainProgram):
         self.norm_vb.copy_(norm_vb.to(torch.float32))
 
     def run_forward(self, z0, cond, t, noise, norm, mask=None) -> torch.Tensor:
-        """Runs the forward launches and overwrites the tape (saved activations, t, noise) of this program: the
-        generation counter lets a backward that belongs to an EARLIER forward of the same shape fail loudly instead of
-        differentiating through the wrong activations (l1 = model(a); l2 = model(b); (l1 + l2).backward())."""
-        self.ensure_fresh()
-        self.generation += 1
-        self.z0.copy_(z0)
-        self.cond.copy_(cond)
-        self.noise.copy_(noise)
-        self.t_rows.copy_(t.to(torch.int32))
-        self.norm.copy_(norm.to(torch.float32))
-        if self.drop_state is not None:
-            self.drop_state.upload()
-        self.use_mask = mask is not None
-        if mask is not None:
-            self.mask.copy_(mask.to(torch.float32))
-        for op in self.ops[:self.n_fwd]:
-            op()
+        """Runs the forward launches and overwrites the tape (saved activations, t, noise) of this program (a new generation:
+        engine.PhasedProgram)."""
+        def load():
+            self.z0.copy_(z0)
+            self.cond.copy_(cond)
+            self.noise.copy_(noise)
+            self.t_rows.copy_(t.to(torch.int32))
+            self.norm.copy_(norm.to(torch.float32))
+            if self.drop_state is not None:
+                self.drop_state.upload()
+            self.use_mask = mask is not None
+            if mask is not None:
+                self.mask.copy_(mask.to(torch.float32))
+
+        self.forward_ops(load)
         return self.loss_out[0].clone()
 
     def run_z0_pred(self, active: Optional[torch.Tensor]) -> torch.Tensor:
@@ -746,30 +772,19 @@ class UNetTrainProgram(TrainProgram):
                      grad_z0: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
         """`grad_z0` (train_step_pred): the gradient of run_z0_pred's result; the loss launch then is ctsi_loss_bwd_z0.
         `grad_out` None: the loss itself took no gradient (gscale 0)."""
-        if generation is not None and generation != self.generation:
-            raise CtsiError(
-                "backward of a training forward whose saved activations were overwritten: another forward of the same "
-                f"shape ran on this program in between (tape generation {generation}, now {self.generation}).  Call "
-                "backward() before the next forward of that shape, or evaluate the second batch under torch.no_grad() "
-                "through model.generate / unet(x, t, c), which do not touch the training tape.")
-        if grad_out is None:
-            self.gscale.zero_()
-        else:
-            self.gscale.copy_(grad_out.reshape(1).to(torch.float32))
-        self.use_gz0 = grad_z0 is not None
-        if grad_z0 is not None:
-            if self.g_z0 is None:
-                raise CtsiError("internal: a gradient of the predicted latent without a run_z0_pred")
-            self.g_z0.copy_(grad_z0.reshape(self.g_z0.shape))
-        for op in self.ops[self.n_fwd:]:
-            op()
-        out = []
-        for p in self.params:
-            g = self.grads.get(id(p))
-            if g is None:
-                raise CtsiError("internal: a U-Net parameter received no gradient buffer")
-            out.append(g[:p.shape[0]] if g.shape[0] != p.shape[0] else g)
-        return out
+        def load():
+            if grad_out is None:
+                self.gscale.zero_()
+            else:
+                self.gscale.copy_(grad_out.reshape(1).to(torch.float32))
+            self.use_gz0 = grad_z0 is not None
+            if grad_z0 is not None:
+                if self.g_z0 is None:
+                    raise CtsiError("internal: a gradient of the predicted latent without a run_z0_pred")
+                self.g_z0.copy_(grad_z0.reshape(self.g_z0.shape))
+
+        self.backward_ops(generation, load)
+        return self.param_grads()
 
 
 def _clone_grads(grads: List[torch.Tensor]) -> List[torch.Tensor]:

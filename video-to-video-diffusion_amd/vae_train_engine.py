@@ -24,7 +24,7 @@ to its INPUT and nothing else (`SliceInterpolationVAE.decode_with_grad`), for im
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional
+from typing import List, Optional
 
 import torch
 
@@ -54,29 +54,34 @@ def check_trainable_geometry(vae, x: torch.Tensor):
 
 
 class VAETrainProgram(TrainProgram):
+    stale_msg = ("backward of a VAE training forward whose saved activations were overwritten: another forward of the same "
+                 "shape ran on this program in between (tape generation {then}, now {now}).  Call "
+                 "backward() before the next training forward of that shape, or run the second batch under torch.no_grad().")
+
     def __init__(self, ctx: Ctx, vae, n: int, d: int, h: int, w: int):
-        super().__init__(ctx)
-        self.weight_cache = False    # weights change every optimizer step: private images, repacked in place
+        super().__init__(ctx, *self._trained(vae), workspaces=("wgrad", "gn", "chsum", "thin"))
         self.vae = vae
         self.n, self.d, self.h, self.w = n, d, h, w
-        enc, dec = vae.encoder, vae.decoder
         self.sf = float(vae.scaling_factor)
-        self.tape = []
-        self.grads: Dict[int, torch.Tensor] = {}
-        self._need = dict(wgrad=16, gn=16, chsum=16, thin=16)
-        self._ws: Dict[str, Optional[torch.Tensor]] = dict(wgrad=None, gn=None, chsum=None, thin=None)
-        self.params = list(vae.parameters())
-        self.track_module(vae)
-        self._garena = self.persistent((sum(p.numel() for p in self.params) + (4 << 20),), torch.float32, zero=True)
-        self._garena_used = 0
-        self.use_thin = os.environ.get("CTSI_VAE_THIN_WGRAD", "1") != "0"   # A/B: 0 = the MFMA wgrad on padded channels
-        lib, sptr, prog = self.lib, ctx.sptr, self
+        self.L = vae.latent_dim
+        # A/B: CTSI_VAE_THIN_WGRAD=0 = the MFMA wgrad on padded channels
+        self.use_thin = not self.data_only and os.environ.get("CTSI_VAE_THIN_WGRAD", "1") != "0"
+        self.zero_gn_op()
+        self._emit_front()
+        self._emit_decoder()
+        self.finish_build()
 
-        # ---- encoder (engine.VAEEncodeProgram) ----------------------------------------------------------------------------
+    def _trained(self, vae):
+        """(the module whose parameters take gradients, the floats of its gradient arena)"""
+        return vae, sum(p.numel() for p in vae.parameters()) + (4 << 20)
+
+    def _emit_front(self):
+        """What precedes the decoder: the encoder (engine.VAEEncodeProgram), quant_conv and the seam into `zin`."""
+        lib, sptr, prog = self.lib, self.ctx.sptr, self
+        vae, enc, n, d, h, w, L, sf = self.vae, self.vae.encoder, self.n, self.d, self.h, self.w, self.L, self.sf
         cin = vae.in_channels
         self.cin, self.cin_pad = cin, _pad8(cin)
         self.xin = Act(self.persistent((n * d * h * w * self.cin_pad,), torch.bfloat16, zero=True), n, self.cin_pad, d, h, w)
-        self.zero_gn_op()
         x = self.conv_gn_act("enc.conv_in", enc.conv_in, self.xin, cin_w=cin, stem=True)
         for stage in (enc.down1, enc.down2):
             for m in stage:
@@ -84,19 +89,18 @@ class VAETrainProgram(TrainProgram):
         for m in enc.mid:
             x = self.block(m, x)
         y = self.v_conv("enc.conv_out", enc.conv_out, x)
-        L = vae.latent_dim
-        self.L = L
         hl, wl = y.h, y.w
         self.hl, self.wl = hl, wl
         vox_l = d * hl * wl
         self.z = self.persistent((n, L, d, hl, wl), torch.float32)
-        sf = self.sf
         qc = enc.quant_conv
         qb = lambda: qc.bias * sf
         qb.parts, qb.scale = [lambda: qc.bias], sf        # (fast_repack: a scaled parameter view)
         self.conv("enc.quant", lambda: qc.weight * sf, qb, y, None, k=(1, 1, 1), p=(0, 0, 0), cout=L, f32_out=self.z,
                   f32_strides=(L * vox_l, vox_l, hl * wl, wl, 1))
         self.zin = Act(self.persistent((n * vox_l * L,), torch.bfloat16, zero=True), n, L, d, hl, wl)
+        self.g_z = self.persistent(tuple(self.z.shape), torch.float32, zero=True)
+        self.use_gz = False
 
         def quant_bwd():      # output gradient: sf * dL/dz, left in zin.grad by the seam (see the module docstring)
             g = prog.zin.grad
@@ -126,10 +130,16 @@ class VAETrainProgram(TrainProgram):
 
         self.tape.append(seam_bwd)
 
-        # ---- decoder (engine.VAEDecodeProgram) -------------------------------------------------------------------------------
+    def _emit_decoder(self):
+        """The decoder (engine.VAEDecodeProgram) from `zin` to the fp32 `recon`, the end of the forward, and the head of the
+        backward: ctsi_vae_head_grad from `g_recon` into `d_head`, the output gradient of conv_out.  A `data_only` program
+        differentiates post_quant_conv with the folded weight the forward used (the seam's grad_z then is dL/dz itself)."""
+        lib, sptr, prog = self.lib, self.ctx.sptr, self
+        dec, n, d, sf = self.vae.decoder, self.n, self.d, self.sf
         pq = dec.post_quant_conv
-        u = self.v_conv("dec.post_quant", pq, self.zin, weight_fn=lambda: pq.weight * (1.0 / sf), k=(1, 1, 1), cin_w=L,
-                        w_scale=1.0 / sf)
+        pq_w = lambda: pq.weight * (1.0 / sf)
+        u = self.v_conv("dec.post_quant", pq, self.zin, weight_fn=pq_w, k=(1, 1, 1), cin_w=self.L, w_scale=1.0 / sf,
+                        dgrad_weight_fn=pq_w if self.data_only else None)
         x = self.conv_gn_act("dec.conv_in", dec.conv_in, u)
         for m in dec.mid:
             x = self.block(m, x)
@@ -139,33 +149,21 @@ class VAETrainProgram(TrainProgram):
         x = self.block(dec.up3_upsample, x)
         for m in dec.up3_res:
             x = self.block(m, x)
-        co = dec.conv_out.out_channels
-        self.co = co
-        self.ho, self.wo = x.h, x.w
-        vox = d * x.h * x.w
-        self.recon = self.persistent((n, co, d, x.h, x.w), torch.float32)
-        self.d_head = Act(self.persistent((n * vox * _pad8(co),), torch.bfloat16, zero=True), n, _pad8(co), d, x.h, x.w)
-        self.v_conv("dec.conv_out", dec.conv_out, x, f32_out=self.recon, f32_strides=(co * vox, vox, x.h * x.w, x.w, 1),
-                    act=1, gy=self.d_head, thin_head=(co == 1))
-        self.n_fwd = len(self.ops)
-        self.generation = 0
-
-        # ---- backward --------------------------------------------------------------------------------------------------------
+        co = self.co = dec.conv_out.out_channels
+        ho, wo = self.ho, self.wo = x.h, x.w
+        vox = d * ho * wo
+        self.recon = self.persistent((n, co, d, ho, wo), torch.float32)
+        hp = self.d_head = Act(self.persistent((n * vox * _pad8(co),), torch.bfloat16, zero=True), n, _pad8(co), d, ho, wo)
+        self.v_conv("dec.conv_out", dec.conv_out, x, f32_out=self.recon, f32_strides=(co * vox, vox, ho * wo, wo, 1), act=1,
+                    gy=hp, thin_head=(co == 1))
+        self.end_forward()
         self.g_recon = self.persistent(tuple(self.recon.shape), torch.float32, zero=True)
-        self.g_z = self.persistent(tuple(self.z.shape), torch.float32, zero=True)
-        self.use_gz = False
-        ho, wo, hp = x.h, x.w, self.d_head
 
         def run_head():
             lib.vae_head_grad(_ptr(prog.g_recon), _ptr(prog.recon), n, co, d, ho, wo, 1.0, 0, hp.ip, hp.c, sptr)
 
         self._emit(run_head, "head.grad", audit=dict(kind="head_grad", mode=0, g=self.g_recon, y=self.recon, scale=1.0, out=hp,
                                                      active=None))
-        for fn in reversed(self.tape):
-            fn()
-        self.finalize_layout()
-        for key, need in self._need.items():
-            self._ws[key] = torch.empty(need, dtype=torch.uint8, device=ctx.device)
 
     # ---- layers --------------------------------------------------------------------------------------------------------------
     def v_conv(self, name, m, x1: Act, *, weight_fn=None, bias_fn=None, cin_w=None, k=(3, 3, 3), s=(1, 1),
@@ -258,52 +256,35 @@ class VAETrainProgram(TrainProgram):
             return self.conv_gn_act("up", m, x, k=(3, 4, 4), s=(2, 2), transposed=True)
         raise CtsiError(f"unsupported VAE block {kind}")
 
-    def needs_rebuild(self) -> bool:
-        cur = list(self.vae.parameters())
-        return len(cur) != len(self.params) or any(a is not b for a, b in zip(cur, self.params))
-
     # ---- execution -----------------------------------------------------------------------------------------------------------
+    def _load(self, src: torch.Tensor, a: Act, c: int):
+        """fp32 NCDHW `src` of `c` channels into the bf16 input tensor `a`."""
+        xx = src.detach().to(device=self.ctx.device, dtype=torch.float32).contiguous()
+        self.lib.ncdhw_f32_to_ndhwc_bf16(_ptr(xx), a.ip, a.n, c, a.d, a.h, a.w, a.c, 0, self.ctx.sptr)
+        xx.record_stream(self.ctx.stream)
+
     def run_forward(self, x: torch.Tensor):
         """Forward launches; overwrites the saved activations (the generation counter makes a backward of an earlier forward
         of this shape fail loudly)."""
-        self.ensure_fresh()
-        self.generation += 1
-        lib, sptr = self.lib, self.ctx.sptr
-        xx = x.detach().to(device=self.ctx.device, dtype=torch.float32).contiguous()
-        lib.ncdhw_f32_to_ndhwc_bf16(_ptr(xx), self.xin.ip, self.n, self.cin, self.d, self.h, self.w, self.cin_pad, 0, sptr)
-        xx.record_stream(self.ctx.stream)
-        for op in self.ops[:self.n_fwd]:
-            op()
+        self.forward_ops(lambda: self._load(x, self.xin, self.cin))
         recon, z = self.recon.clone(), self.z.clone()
         self.check_errors()
         return recon, z
 
     def run_backward(self, grad_recon: Optional[torch.Tensor], grad_z: Optional[torch.Tensor],
                      generation: Optional[int] = None) -> List[torch.Tensor]:
-        if generation is not None and generation != self.generation:
-            raise CtsiError(
-                "backward of a VAE training forward whose saved activations were overwritten: another forward of the same "
-                f"shape ran on this program in between (tape generation {generation}, now {self.generation}).  Call "
-                "backward() before the next training forward of that shape, or run the second batch under torch.no_grad().")
-        if grad_recon is None:
-            self.g_recon.zero_()
-        else:
-            self.g_recon.copy_(grad_recon.reshape(self.g_recon.shape))
-        self.use_gz = grad_z is not None
-        if grad_z is not None:
-            self.g_z.copy_(grad_z.reshape(self.g_z.shape))
-        for op in self.ops[self.n_fwd:]:
-            op()
+        def load():
+            if grad_recon is None:
+                self.g_recon.zero_()
+            else:
+                self.g_recon.copy_(grad_recon.reshape(self.g_recon.shape))
+            self.use_gz = grad_z is not None
+            if grad_z is not None:
+                self.g_z.copy_(grad_z.reshape(self.g_z.shape))
+
+        self.backward_ops(generation, load)
         self.check_errors()
-        out = []
-        for p in self.params:
-            g = self.grads.get(id(p))
-            if g is None:
-                raise CtsiError("internal: a VAE parameter received no gradient buffer")
-            if tuple(g.shape) != tuple(p.shape):
-                g = g[tuple(slice(0, s) for s in p.shape)]
-            out.append(g)
-        return out
+        return self.param_grads()
 
 
 class _VAETrainStep(torch.autograd.Function):
@@ -358,31 +339,22 @@ class VAEDecodeGradProgram(VAETrainProgram):
     at.  The weights are frozen as far as this program is concerned, so it shares packed weight images with the inference
     programs (a changed parameter is still picked up: Program.ensure_fresh)."""
     data_only = True
+    stale_msg = ("backward of a differentiable decode whose saved activations were overwritten: another decode_with_grad of the "
+                 "same shape ran on this program in between (tape generation {then}, now {now}).  Call "
+                 "backward() before the next decode_with_grad of that shape, or decode the second latent under torch.no_grad().")
 
-    def __init__(self, ctx: Ctx, vae, n: int, d: int, h: int, w: int):
-        TrainProgram.__init__(self, ctx)
-        self.vae = vae
-        self.n, self.d, self.h, self.w = n, d, h, w          # (h, w: the LATENT plane)
-        dec = vae.decoder
-        self.sf = sf = float(vae.scaling_factor)
-        self.tape = []
-        self.grads: Dict[int, torch.Tensor] = {}
-        self._need = dict(wgrad=16, gn=16, chsum=16, thin=16)
-        self._ws: Dict[str, Optional[torch.Tensor]] = dict(wgrad=None, gn=None, chsum=None, thin=None)
-        self.params = list(dec.parameters())
-        self.track_module(dec)
-        norms = [m for m in dec.modules() if isinstance(m, torch.nn.GroupNorm)]
-        # (the arena holds nothing but the dgamma / dbeta rows ctsi_gn_bwd insists on writing)
-        self._garena = self.persistent((sum(2 * ((m.num_channels + 63) // 64 * 64) for m in norms),), torch.float32, zero=True)
-        self._garena_used = 0
-        self.use_thin = False
-        lib, sptr, prog = self.lib, ctx.sptr, self
-        L = self.L = vae.latent_dim
+    def _trained(self, vae):
+        # (nothing is trained: the arena holds nothing but the dgamma / dbeta rows ctsi_gn_bwd insists on writing)
+        norms = [m for m in vae.decoder.modules() if isinstance(m, torch.nn.GroupNorm)]
+        return vae.decoder, sum(2 * ((m.num_channels + 63) // 64 * 64) for m in norms)
+
+    def _emit_front(self):
+        """The latent input `zin` ((h, w): the LATENT plane) and the seam's backward: one layout pass back to fp32 NCDHW."""
+        lib, sptr, prog = self.lib, self.ctx.sptr, self
+        n, d, h, w, L = self.n, self.d, self.h, self.w, self.L
         self.hl, self.wl = h, w
-        vox_l = d * h * w
-        self.zin = Act(self.persistent((n * vox_l * L,), torch.bfloat16, zero=True), n, L, d, h, w)
+        self.zin = Act(self.persistent((n * d * h * w * L,), torch.bfloat16, zero=True), n, L, d, h, w)
         self.g_z = self.persistent((n, L, d, h, w), torch.float32)
-        self.zero_gn_op()
 
         def seam_bwd():       # runs after post_quant's data gradient wrote zin.grad = (W_p / sf)^T du = dL/dz, bf16 NDHWC
             zg = prog.zin.grad
@@ -395,70 +367,17 @@ class VAEDecodeGradProgram(VAETrainProgram):
             prog.zin.grad = None
 
         self.tape.append(seam_bwd)
-        pq = dec.post_quant_conv
-        pq_w = lambda: pq.weight * (1.0 / sf)
-        u = self.v_conv("dec.post_quant", pq, self.zin, weight_fn=pq_w, k=(1, 1, 1), cin_w=L, dgrad_weight_fn=pq_w)
-        x = self.conv_gn_act("dec.conv_in", dec.conv_in, u)
-        for m in dec.mid:
-            x = self.block(m, x)
-        x = self.block(dec.up2_upsample, x)
-        for m in dec.up2_res:
-            x = self.block(m, x)
-        x = self.block(dec.up3_upsample, x)
-        for m in dec.up3_res:
-            x = self.block(m, x)
-        co = self.co = dec.conv_out.out_channels
-        ho, wo = self.ho, self.wo = x.h, x.w
-        vox = d * ho * wo
-        self.recon = self.persistent((n, co, d, ho, wo), torch.float32)
-        self.d_head = Act(self.persistent((n * vox * _pad8(co),), torch.bfloat16, zero=True), n, _pad8(co), d, ho, wo)
-        self.v_conv("dec.conv_out", dec.conv_out, x, f32_out=self.recon, f32_strides=(co * vox, vox, ho * wo, wo, 1), act=1,
-                    gy=self.d_head)
-        self.n_fwd = len(self.ops)
-        self.generation = 0
-
-        # ---- backward: head, then the tape in reverse ----------------------------------------------------------------------
-        self.g_recon = self.persistent(tuple(self.recon.shape), torch.float32, zero=True)
-        hp = self.d_head
-
-        def run_head():
-            lib.vae_head_grad(_ptr(prog.g_recon), _ptr(prog.recon), n, co, d, ho, wo, 1.0, 0, hp.ip, hp.c, sptr)
-
-        self._emit(run_head, "head.grad", audit=dict(kind="head_grad", mode=0, g=self.g_recon, y=self.recon, scale=1.0, out=hp,
-                                                     active=None))
-        for fn in reversed(self.tape):
-            fn()
-        self.finalize_layout()
-        for key, need in self._need.items():
-            self._ws[key] = torch.empty(need, dtype=torch.uint8, device=ctx.device)
-
-    def needs_rebuild(self) -> bool:
-        cur = list(self.vae.decoder.parameters())
-        return len(cur) != len(self.params) or any(a is not b for a, b in zip(cur, self.params))
 
     def run_forward(self, z: torch.Tensor) -> torch.Tensor:
         """Forward launches; overwrites the saved activations (the generation counter makes a backward of an earlier forward
         of this shape fail loudly)."""
-        self.ensure_fresh()
-        self.generation += 1
-        zz = z.detach().to(device=self.ctx.device, dtype=torch.float32).contiguous()
-        self.lib.ncdhw_f32_to_ndhwc_bf16(_ptr(zz), self.zin.ip, self.n, self.L, self.d, self.h, self.w, self.L, 0, self.ctx.sptr)
-        zz.record_stream(self.ctx.stream)
-        for op in self.ops[:self.n_fwd]:
-            op()
+        self.forward_ops(lambda: self._load(z, self.zin, self.L))
         recon = self.recon.clone()
         self.check_errors()
         return recon
 
     def run_backward(self, grad_recon: torch.Tensor, generation: Optional[int] = None) -> torch.Tensor:
-        if generation is not None and generation != self.generation:
-            raise CtsiError(
-                "backward of a differentiable decode whose saved activations were overwritten: another decode_with_grad of the "
-                f"same shape ran on this program in between (tape generation {generation}, now {self.generation}).  Call "
-                "backward() before the next decode_with_grad of that shape, or decode the second latent under torch.no_grad().")
-        self.g_recon.copy_(grad_recon.reshape(self.g_recon.shape))
-        for op in self.ops[self.n_fwd:]:
-            op()
+        self.backward_ops(generation, lambda: self.g_recon.copy_(grad_recon.reshape(self.g_recon.shape)))
         self.check_errors()
         return self.g_z.clone()
 

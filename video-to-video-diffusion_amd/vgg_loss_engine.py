@@ -29,7 +29,7 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from .engine import Act, Ctx, Program, _ptr
+from .engine import Act, Ctx, PhasedProgram, _ptr
 from .lib import ConvDesc, CtsiError
 
 # torchvision's vgg19().features: module index -> ("conv", cin, cout) | ("relu",) | ("pool",); 37 modules, 16 convs
@@ -61,7 +61,7 @@ VGG16_MODULES = feature_modules(VGG16_CFG)
 K, P = (1, 3, 3), (0, 1, 1)
 
 
-class VGGLossProgram(Program):
+class VGGLossProgram(PhasedProgram):
     """convs: {module index: nn.Conv2d} up to max(feature_layers); n_img: sampled slices per call (B * num).  `modules`: the
     stack's module table (VGG-19 for the feature loss, VGG-16 for LPIPS).  `distance`: "feat" -- the L1 / L2 feature distance
     averaged over the layers into one scalar -- or "lpips" -- the unit-normalised, head-weighted squared distance of
@@ -80,6 +80,9 @@ class VGGLossProgram(Program):
         if distance not in ("feat", "lpips"):
             raise CtsiError(f"internal: unknown feature distance {distance!r}")
         self.lpips = distance == "lpips"
+        self.label = "LPIPS" if self.lpips else "VGG loss"
+        self.stale_msg = (f"backward of a{'n' if self.lpips else ''} {self.label} forward whose saved activations were "
+                          "overwritten (internal: a program was handed out twice)")
         if self.lpips:
             if heads is None or len(heads) != nl or any(modules[i][0] != "relu" for i in self.layers):
                 raise CtsiError("internal: the LPIPS distance needs one head per tap and taps at ReLU outputs")
@@ -95,7 +98,6 @@ class VGGLossProgram(Program):
             self.out = self.persistent((1 + nl,), torch.float32)
             self.gl = self.persistent((1,), torch.float32)
         self.xin = Act(self.persistent((n2 * h * w * 8,), torch.bfloat16), 1, 8, n2, h, w)
-        self.generation = 0
 
         # ---- forward --------------------------------------------------------------------------------------------------------
         nodes, x = [], self.xin
@@ -166,7 +168,7 @@ class VGGLossProgram(Program):
                 lib.feat_loss_finalize(pa, cn, nl, ob, sptr)
 
             self._emit(run_fin, "vgg.loss.finalize", 0.0, "feat_loss_finalize")
-        self.n_fwd = len(self.ops)
+        self.end_forward()
 
         # ---- backward (pred half) ------------------------------------------------------------------------------------------
         glp = _ptr(self.gl)
@@ -253,70 +255,43 @@ class VGGLossProgram(Program):
         self._emit(run, name, 0.0, "relu_bf16", nbytes=4.0 * cnt)
 
     # ---- execution -----------------------------------------------------------------------------------------------------------
-    def run_forward(self, pred: torch.Tensor, target: torch.Tensor, slices: torch.Tensor, norm: torch.Tensor, b: int, d: int,
-                    num: int) -> torch.Tensor:
-        """pred, target: fp32 contiguous (B, 1, D, H, W) device tensors; returns the fp32 device tensor [loss, layer means]."""
-        if b * num != self.n_img:
-            raise CtsiError("internal: the VGG loss program was built for another number of images")
-        self.ensure_fresh()
-        self.generation += 1
-        lib, sptr = self.lib, self.ctx.sptr
-        half_bytes = self.n_img * self.h * self.w * 8 * 2
-        lib.vgg_prep(_ptr(pred), _ptr(slices), _ptr(norm), self.xin.ip, b, d, num, self.h, self.w, sptr)
-        lib.vgg_prep(_ptr(target), _ptr(slices), _ptr(norm), C.c_void_p(self.xin.ip.value + half_bytes), b, d, num, self.h,
-                     self.w, sptr)
-        pred.record_stream(self.ctx.stream)
-        target.record_stream(self.ctx.stream)
-        for op in self.ops[:self.n_fwd]:
-            op()
+    # `args`, the per-distance part of a call, the same tuple for the forward and its backward:
+    #   feature loss  (slices, norm, b, d, num)   x0, x1: fp32 contiguous (B, 1, D, H, W) device tensors, pred and target
+    #   LPIPS         (c, normalize)              x0, x1: fp32 contiguous (N, c = 1 | 3, H, W) device tensors
+    def run_forward(self, x0: torch.Tensor, x1: torch.Tensor, args: tuple) -> torch.Tensor:
+        """Returns the fp32 device tensor [loss, layer means] (LPIPS: [N per-image values, tap means])."""
+        lib, sptr, h, w = self.lib, self.ctx.sptr, self.h, self.w
+        if (x0.shape[0] if self.lpips else args[2] * args[4]) != self.n_img:
+            raise CtsiError(f"internal: the {self.label} program was built for another number of images")
+
+        def load():
+            for src, off in ((x0, 0), (x1, self.n_img * h * w * 8 * 2)):
+                dst = C.c_void_p(self.xin.ip.value + off)
+                if self.lpips:
+                    c, normalize = args
+                    lib.lpips_prep(_ptr(src), dst, self.n_img, c, h, w, int(normalize), sptr)
+                else:
+                    slices, norm, b, d, num = args
+                    lib.vgg_prep(_ptr(src), _ptr(slices), _ptr(norm), dst, b, d, num, h, w, sptr)
+            x0.record_stream(self.ctx.stream)
+            x1.record_stream(self.ctx.stream)
+
+        self.forward_ops(load)
         out = self.out.clone()
         self.check_errors()
         return out
 
-    def run_forward_images(self, in0: torch.Tensor, in1: torch.Tensor, normalize: bool) -> torch.Tensor:
-        """LPIPS: in0, in1 fp32 contiguous (N, 1 | 3, H, W) device tensors; returns the fp32 device tensor [N per-image values,
-        tap means]."""
-        n, c = in0.shape[:2]
-        if n != self.n_img or not self.lpips:
-            raise CtsiError("internal: the LPIPS program was built for another number of images")
-        self.ensure_fresh()
-        self.generation += 1
-        lib, sptr = self.lib, self.ctx.sptr
-        half_bytes = self.n_img * self.h * self.w * 8 * 2
-        lib.lpips_prep(_ptr(in0), self.xin.ip, n, c, self.h, self.w, int(normalize), sptr)
-        lib.lpips_prep(_ptr(in1), C.c_void_p(self.xin.ip.value + half_bytes), n, c, self.h, self.w, int(normalize), sptr)
-        in0.record_stream(self.ctx.stream)
-        in1.record_stream(self.ctx.stream)
-        for op in self.ops[:self.n_fwd]:
-            op()
-        out = self.out.clone()
-        self.check_errors()
-        return out
-
-    def run_backward_images(self, grad_out: torch.Tensor, c: int, normalize: bool, generation: int) -> torch.Tensor:
-        """grad_out: (N,) fp32 device; returns the gradient of in0, fp32 (N, c, H, W)."""
-        if generation != self.generation:
-            raise CtsiError("backward of an LPIPS forward whose saved activations were overwritten (internal: a program was "
-                            "handed out twice)")
-        lib, sptr = self.lib, self.ctx.sptr
-        self.gl.copy_(grad_out.reshape(self.n_img))
-        for op in self.ops[self.n_fwd:]:
-            op()
-        grad = torch.empty((self.n_img, c, self.h, self.w), dtype=torch.float32, device=self.ctx.device)
-        lib.lpips_prep_bwd(self.g_in.ip, _ptr(grad), self.n_img, c, self.h, self.w, int(normalize), sptr)
+    def run_backward(self, grad_out: torch.Tensor, args: tuple, generation: int) -> torch.Tensor:
+        """grad_out: fp32 device, one element (LPIPS: (N,)); returns the gradient of x0, fp32, in x0's shape."""
+        lib, sptr, h, w = self.lib, self.ctx.sptr, self.h, self.w
+        self.backward_ops(generation, lambda: self.gl.copy_(grad_out.reshape(self.gl.shape)))
+        if self.lpips:
+            c, normalize = args
+            grad = torch.empty((self.n_img, c, h, w), dtype=torch.float32, device=self.ctx.device)
+            lib.lpips_prep_bwd(self.g_in.ip, _ptr(grad), self.n_img, c, h, w, int(normalize), sptr)
+        else:
+            slices, norm, b, d, num = args
+            grad = torch.empty((b, 1, d, h, w), dtype=torch.float32, device=self.ctx.device)
+            lib.vgg_prep_bwd(self.g_in.ip, _ptr(slices), _ptr(norm), _ptr(grad), b, d, num, h, w, sptr)
         self.check_errors()
         return grad
-
-    def run_backward(self, grad_loss: torch.Tensor, slices: torch.Tensor, norm: torch.Tensor, b: int, d: int, num: int,
-                     generation: int) -> torch.Tensor:
-        if generation != self.generation:
-            raise CtsiError("backward of a VGG loss forward whose saved activations were overwritten (internal: a program was "
-                            "handed out twice)")
-        lib, sptr = self.lib, self.ctx.sptr
-        self.gl.copy_(grad_loss.reshape(1))
-        for op in self.ops[self.n_fwd:]:
-            op()
-        grad_pred = torch.empty((b, 1, d, self.h, self.w), dtype=torch.float32, device=self.ctx.device)
-        lib.vgg_prep_bwd(self.g_in.ip, _ptr(slices), _ptr(norm), _ptr(grad_pred), b, d, num, self.h, self.w, sptr)
-        self.check_errors()
-        return grad_pred
