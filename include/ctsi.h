@@ -904,6 +904,34 @@ int ctsi_ensemble_finalize(const float* m2, float* std_out, int members, int unb
 int ctsi_ensemble_calibration(const float* mean, const float* std_in, const float* target, int planes, long long plane,
                               double* partials, double* stats, void* stream);
 
+/* Measurement guidance (csrc/measure_guide.hip): the device passes of one guided sampler evaluation around
+ * the decoder's data-gradient tape.  Latents are n samples of c channels on d x h x w voxels.
+ * ctsi_guide_z0: the predicted clean latent, z0_out (fp32 NCDHW) from z_t and eps (both fp32 NDHWC, c floats per voxel):
+ *   mode 0  z0 = clip(nan_to_num((z_t - sigma nan_to_num(eps)) / alpha))     (the eps-form updates; alpha != 0)
+ *   mode 1  z0 = clip(nan_to_num(fma(alpha, z_t, -(sigma nan_to_num(eps)))))  (the x0 form on the raw v, and rows that hold
+ *           1 / alpha and sigma / alpha);  clip(v) = clamp(v, -clip, clip), clip == 0: no clamp.
+ * ctsi_depth_residual_adj: x a thin fp32 NCDHW volume (n, c, d_out, hw), y the thick one (n, c, d_in, hw), W [d_in][d_out] and
+ *   band [d_in][2] as for ctsi_depth_measure.  One pass: g_x = -W^T (y - W x) (fp32, x's shape; it may not alias x) and
+ *   sumsq[b] (fp64, n values) = sum over sample b of r^2, r = y - W x re-evaluated in fp64 on the fp32 values.  A block stages
+ *   a tile of whole depth columns in LDS, so x is read once and g_x written once.  partials: one fp64 per slot,
+ *   ctsi_depth_project_blocks(n c, hw) slots, every slot written by one block; a second launch folds each sample's slots in
+ *   index order.  No atomics: the same bits on every run.  Limits d_in <= 64, d_out <= 512.
+ * ctsi_guide_apply: per sample b, s_b = 1 / sqrt(sumsq[b]) (normalize == 1; a sample whose sumsq is 0 or not finite is left
+ *   untouched, bit for bit) or 1 (normalize == 0, sumsq may be NULL); in fp32, c_z = coef_z s_b and c_h = coef_hist s_b (the
+ *   products formed in fp64 and rounded once).  z (fp32 NDHWC, in place) <- nan_to_num(fma(c_z, g_z, z)) with g_z fp32 NCDHW;
+ *   hist (fp32 NDHWC, may be NULL) <- nan_to_num(fma(c_h, g_z, hist)); zin (bf16, may be NULL: voxel stride c_total, channel
+ *   offset c_off -- the operands of ctsi_x0_step) <- bf16(z) for every sample; its other channels are not touched.  The
+ *   factors are read from device memory: no host synchronisation.
+ * Null pointers (other than the optional ones), non-positive sizes, a bad mode / normalize flag / channel slice, clip < 0,
+ * alpha == 0 in mode 0 and depths over the limits return CTSI_ERR_INVALID before any launch.  Capture-safe: no allocation,
+ * no synchronisation. */
+int ctsi_guide_z0(const float* z_t, const float* eps, float alpha, float sigma, int mode, float clip, float* z0_out, int n,
+                  int c, int d, int h, int w, void* stream);
+int ctsi_depth_residual_adj(const float* x, const float* y, const float* W, const int* band, float* g_x, double* partials,
+                            double* sumsq, int n, int c, int d_in, int d_out, int hw, void* stream);
+int ctsi_guide_apply(float* z, float* hist, const float* g_z, const double* sumsq, float coef_z, float coef_hist,
+                     int normalize, void* zin, int c_total, int c_off, int n, int c, int d, int h, int w, void* stream);
+
 /* depth-sharding collectives (RCCL over xGMI, one process per GPU) --------------------------- *
  * a volume's depth is cut into `world` slabs; before a depth-3 conv a slab needs one boundary
  * slice of each depth neighbour (models/unet3d.py:56,96,204-207,218-221; models/vae.py:27,65-69,86-90), GroupNorm needs

@@ -1266,6 +1266,7 @@ class UNetProgram(Program):
         self.t_rows_f = self.persistent((max_rows,), torch.float32, zero=True)   # fractional timesteps (EDM sampler)
         self.coef = self.persistent((max_rows, 8), torch.float32, zero=True)
         self.noise = None  # fp32 NCDHW, allocated on demand
+        self.guide_z = None  # fp32 NDHWC like z: the state a guided evaluation saves before the replay (guide_scratch)
         self.track_module(unet)
 
         # ---- time embedding: stack every ResBlock's Linear(time_dim -> cout) -------------------------
@@ -1445,6 +1446,14 @@ class UNetProgram(Program):
         self.lib.ndhwc_f32_to_ncdhw_f32(_ptr(self.z), _ptr(out), self.n, self.L, self.d, self.h, self.w,
                                         self.ctx.sptr)
         return out
+
+    def guide_scratch(self) -> torch.Tensor:
+        """The program's scratch for measurement guidance: a buffer of z's shape that receives the state
+        before the replay of a guided evaluation.  Allocated on first use -- an unguided program never holds it -- and kept
+        with the program; no captured launch reads or writes it."""
+        if self.guide_z is None:
+            self.guide_z = torch.empty_like(self.z)
+        return self.guide_z
 
     def _sampler_zin(self):
         """The U-Net input slice the sampler update writes the new z into: (pointer, channels per voxel, bytes per

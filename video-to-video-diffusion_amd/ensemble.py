@@ -125,6 +125,11 @@ def generate_ensemble(model, v_in, sampler, num_inference_steps=20, num_members=
     from .engine_f32 import check_precision
     from .sampler import SAMPLERS, check_guidance
     check_members(num_members, member_batch)
+    mg = getattr(model, "measurement_guidance", None)
+    if mg is not None and mg.scale > 0.0:
+        raise CtsiError("generate_ensemble does not support measurement_guidance: the members are rows of one sampler batch and "
+                        "the guidance holds one thick volume per row; call generate() per member, or set "
+                        "measurement_guidance = None")
     if member_noise_fn is not None and not callable(member_noise_fn):
         raise ValueError(f"member_noise_fn must be None or a callable (k, i, shape) -> noise, got "
                          f"{type(member_noise_fn).__name__}")

@@ -14,6 +14,8 @@ from .diffusion import GaussianDiffusion
 from .engine import Ctx, check_attention_mode, nan_to_num_, trilinear_depth
 from .engine_f32 import check_precision
 from .lib import CtsiError
+from .measurement_guidance import (check_measurement_guidance, measurement_guidance_from_config,
+                                   refuse_unguidable_model)
 from .sampler import SAMPLERS, check_guidance
 from .unet3d import UNet3D
 from .vae import VideoVAE
@@ -80,6 +82,10 @@ class VideoToVideoDiffusion(nn.Module):
         # `data_consistency` is a plain attribute too: never a submodule, never in the state dict
         if name == "data_consistency":
             self.__dict__["data_consistency"] = check_data_consistency(value)
+            return
+        # and so is `measurement_guidance`
+        if name == "measurement_guidance":
+            self.__dict__["measurement_guidance"] = check_measurement_guidance(value)
             return
         super().__setattr__(name, value)
 
@@ -169,6 +175,11 @@ class VideoToVideoDiffusion(nn.Module):
         # From the config only when its additive `data_consistency:` section says `enabled: true`.
         self.data_consistency = data_consistency_from_config(config)
         self._consistency_warned = False
+        # measurement guidance of generate(), a plain attribute: None (default) or a
+        # measurement_guidance.MeasurementGuidance.  From the config only when its additive `measurement_guidance:` section
+        # says `enabled: true`.
+        self.measurement_guidance = measurement_guidance_from_config(config)
+        self._guidance_warned = False
 
     def set_inference_precision(self, precision):
         """'bf16' (default), 'fp32' or 'bf16x3' (fp32 tensors, split-bf16 MFMA convolutions: engine_x3.py): sets `unet.inference_precision` and `vae.inference_precision`, i.e. the arithmetic
@@ -271,7 +282,12 @@ class VideoToVideoDiffusion(nn.Module):
         call only; the attributes are restored afterwards.
         With `self.data_consistency` set (a consistency.DataConsistency; default None: the launches and bits of a model without it) and a
         `target_depth` that changes the depth, the decoded, sanitised volume is projected onto the sanitised `v_in` as the last
-        device step; when the depth does not change the attribute has no effect and one warning says so."""
+        device step; when the depth does not change the attribute has no effect and one warning says so.
+        With `self.measurement_guidance` set (a measurement_guidance.MeasurementGuidance of scale > 0; default None: the launches
+        and bits of a model without it) and a `target_depth` that changes the depth, the guidance's evaluations are steered
+        toward the sanitised `v_in` through the frozen decoder: samplers 'ddim', 'ddpm' and 'dpmpp_2m', bf16,
+        unsharded, fixed_small (CtsiError otherwise, before any device work); an unchanged depth warns once and has no effect.
+        Together with `data_consistency` the projection stays the last device step."""
         check_guidance(guidance_scale, guidance_rescale)
         if precision is not None:
             check_precision(precision)
@@ -290,6 +306,18 @@ class VideoToVideoDiffusion(nn.Module):
             if target_depth is not None and int(target_depth) < int(v_in.shape[2]):
                 raise ValueError(f"data_consistency: target_depth={int(target_depth)} is below the {int(v_in.shape[2])} input "
                                  f"slices; a slice profile maps thin slices onto fewer thick ones")
+        mg = self.measurement_guidance
+        if mg is not None and mg.scale == 0.0:
+            mg = None
+        if mg is not None:      # what the guidance refuses is refused before any work
+            for m in (self.vae, self.unet):
+                refuse_unguidable_model(self, sampler, check_precision(getattr(m, "inference_precision", "bf16")))
+            if target_depth is not None and int(target_depth) < int(v_in.shape[2]):
+                raise ValueError(f"measurement_guidance: target_depth={int(target_depth)} is below the {int(v_in.shape[2])} "
+                                 f"input slices; a slice profile maps thin slices onto fewer thick ones")
+            if target_depth is None or int(target_depth) == int(v_in.shape[2]):
+                self._warn_guidance_without_depth_change(v_in)
+                mg = None
         if not v_in.is_cuda:
             raise CtsiError("generate runs on the HIP engine: move the input to a ROCm device")
         device = v_in.device
@@ -300,7 +328,8 @@ class VideoToVideoDiffusion(nn.Module):
             torch.randn(latent_shape, device=device)  # model.py:303 draws (and discards) one latent
         z_0 = SAMPLERS[sampler](self.diffusion, self.unet, latent_shape, z_cond, num_inference_steps, device,
                                 noise_fn=noise_fn, guidance_scale=guidance_scale,
-                                guidance_rescale=guidance_rescale)
+                                guidance_rescale=guidance_rescale,
+                                **({} if mg is None else dict(measurement=mg.bind(v_in, self.vae))))
         v_out = self._decode_sanitised(ctx, z_0)
         if dc is not None:
             if v_out.shape[2] != v_in.shape[2]:
@@ -337,6 +366,12 @@ class VideoToVideoDiffusion(nn.Module):
             self._consistency_warned = True
             logger.warning("data_consistency is set but generate() keeps the depth (%d slices): there is nothing to "
                            "project, the attribute has no effect", int(v_in.shape[2]))
+
+    def _warn_guidance_without_depth_change(self, v_in):
+        if not self._guidance_warned:
+            self._guidance_warned = True
+            logger.warning("measurement_guidance is set but generate() keeps the depth (%d slices): there is no slice profile "
+                           "to guide toward, the attribute has no effect", int(v_in.shape[2]))
 
     @torch.no_grad()
     def generate_ensemble(self, v_in, sampler, num_inference_steps=20, num_members=8, guidance_scale=1.0, target_depth=None,

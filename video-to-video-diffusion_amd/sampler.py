@@ -14,9 +14,11 @@ generic-callable loops read.  Adding a sampler = one _step_plan branch + one eng
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import logging
 import math
+import threading
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -84,6 +86,29 @@ def check_guidance(guidance_scale, guidance_rescale) -> Tuple[float, float]:
     if not 0.0 <= phi <= 1.0:     # (a NaN fails both comparisons)
         raise ValueError(f"guidance_rescale must lie in [0, 1], got {guidance_rescale!r}")
     return s, phi
+
+
+_MEASUREMENT = threading.local()
+
+
+@contextlib.contextmanager
+def measurement_scope(measurement):
+    """Hand a bound measurement (MeasurementGuidance.bind(y, vae), or None) to the next run_sampler call of this thread.
+    run_sampler's parameter list is part of the pinned public surface and stays as it is; the call takes the value once on
+    entry, so a nested or a later run is not guided by it; leaving the scope puts back what an enclosing scope had set.
+    sample(measurement=None) opens no scope and so leaves an enclosing one alone."""
+    outer = getattr(_MEASUREMENT, "value", None)
+    _MEASUREMENT.value = measurement
+    try:
+        yield
+    finally:
+        _MEASUREMENT.value = outer
+
+
+def _take_measurement():
+    value = getattr(_MEASUREMENT, "value", None)
+    _MEASUREMENT.value = None
+    return value
 
 
 def _draw_noise(noise_fn, i, shape, dev) -> torch.Tensor:
@@ -580,10 +605,12 @@ def run_sampler_sharded(diffusion, unet, shape, conditioning, ctx, z0, *, kind, 
 
 
 def _run_step_program(prog: UNetProgram, plan: StepPlan, ctx, shape, conditioning, z0, nb: int, *, noise_fn, progress,
-                      guidance: Optional[Tuple[float, float]], trajectory, eps_trajectory):
+                      guidance: Optional[Tuple[float, float]], trajectory, eps_trajectory, guide=None):
     """The reverse loop on a step program (inside ctx.scope()): run_sampler's on the latent `shape`, run_sampler_fused's on the
     full latent's with the windows' conditioning.  `nb`: network rows of one evaluation (timestep rows per evaluation);
-    `shape`: the state's, which the noise draws and both trajectories have.  Returns the final state, fp32 NCDHW."""
+    `shape`: the state's, which the noise draws and both trajectories have.  Returns the final state, fp32 NCDHW.
+    `guide` (a measurement_guidance.GuideRun): its guided evaluations save the state before the replay of the
+    unchanged captured step and issue the correction eagerly behind it; the trajectory entries hold the corrected state."""
     prog.load_latents(z0, conditioning)
     prog.nonfinite.zero_()
     nf_tail = prog.nonfinite.data_ptr() + prog.max_rows * 24
@@ -607,7 +634,19 @@ def _run_step_program(prog: UNetProgram, plan: StepPlan, ctx, shape, conditionin
         else:
             prog.noise.normal_()
 
-    for closes in _replay(plan, _progress(plan, progress), load_noise, prog.launch):
+    launch = prog.launch
+    if guide is not None and guide.evals:
+        done = [0]
+
+        def launch():
+            e, done[0] = done[0], done[0] + 1
+            if e not in guide.slot:
+                return prog.launch()
+            guide.save_state(prog)
+            prog.launch()
+            guide.correct(prog, e)
+
+    for closes in _replay(plan, _progress(plan, progress), load_noise, launch):
         if trajectory is not None and closes:
             trajectory.append(prog.z_ncdhw())
         if eps_trajectory is not None:
@@ -644,9 +683,20 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
     update is ctsi_x0_step on the raw v, which divides by nothing, so a zero-terminal-SNR schedule can be sampled.  The
     guidance then combines -- and its rescale takes the statistics of -- the raw v rows (with phi = 0 algebraically the
     guided eps; with phi > 0 the statistics of the model output, as Lin et al. define the rescale: a difference from the
-    eps statistics of section 18), and `eps_trajectory` receives the (guided) raw v.  'heun' is not affected."""
+    eps statistics of section 18), and `eps_trajectory` receives the (guided) raw v.  'heun' is not affected.
+    Inside `with measurement_scope(MeasurementGuidance.bind(y, vae)):` (additive; the samplers'
+    sample(measurement=) does it) the run is steered toward the thick volume y on the guidance's evaluations: 'ddim', 'ddpm',
+    'dpmpp' on the engine's UNet3D in bf16, unsharded (CtsiError otherwise, before anything is drawn or built).  No scope, or
+    a guidance of scale 0, leaves every launch as it is."""
     s_cfg, phi_cfg = check_guidance(guidance_scale, guidance_rescale)
     guided = s_cfg != 1.0
+    measurement = _take_measurement()
+    if measurement is not None and measurement.guidance.scale == 0.0:
+        measurement = None
+    if measurement is not None:
+        from .measurement_guidance import refuse_unguidable_run
+        refuse_unguidable_run(model, measurement.vae, getattr(model, "inference_precision", "bf16"), kind,
+                              getattr(heun, "learned", False))
     plan = _step_plan(diffusion, kind, t_desc, eta, order, heun)
     if not _is_engine_unet(model) and not callable(model):
         raise CtsiError(f"the samplers need a model(z, t, c) callable; got {type(model).__name__}")
@@ -705,9 +755,13 @@ def run_sampler(diffusion, model, shape, conditioning, device, *, kind: str, t_d
             return prog
 
         prog: UNetProgram = cached_program(unet, key, build)
+        guide = None
+        if measurement is not None:
+            from .measurement_guidance import GuideRun
+            guide = GuideRun(measurement, diffusion, plan, order, ctx, shape)
         return _run_step_program(prog, plan, ctx, shape, conditioning, z0, nb, noise_fn=noise_fn, progress=progress,
                                  guidance=(s_cfg, phi_cfg) if guided else None, trajectory=trajectory,
-                                 eps_trajectory=eps_trajectory)
+                                 eps_trajectory=eps_trajectory, guide=guide)
 
 
 def check_fusable(diffusion, model, kind: str = "ddim", dp_group=None):
@@ -853,17 +907,19 @@ class DDPMSampler(_Sampler):
 
     @torch.no_grad()
     def sample(self, shape, conditioning, device, progress=True, noise_fn=None, num_steps=None,
-               trajectory=None, guidance_scale=1.0, guidance_rescale=0.0, num_inference_steps=None, clip_denoised=True):
+               trajectory=None, guidance_scale=1.0, guidance_rescale=0.0, num_inference_steps=None, clip_denoised=True,
+               measurement=None):
         """`num_inference_steps` N (additive; None or T: every step, as ever): the N-step strided ancestral sampler.  The
         timesteps are DDIMSampler's for N; the network is evaluated at the original timesteps and the update runs on the
         respaced chain beta'_i = 1 - abar_{S_i} / abar_{S_{i-1}} with its own posterior coefficients and variances
         (learned_sigma.respaced_ddpm_rows) -- the fixed-small beta~' or, under var_type='learned_range', the model's.
         `clip_denoised=False` (additive) drops the clamp of the predicted z_0 to [-1, 1].  `num_steps`: a prefix (test hook)."""
         kind, chain = self.chain(num_inference_steps, clip_denoised)
-        return run_sampler(self.diffusion, self.model, shape, conditioning, device, kind=kind, t_desc=chain[:num_steps],
-                           progress=progress, noise_fn=noise_fn, trajectory=trajectory,
-                           guidance_scale=guidance_scale, guidance_rescale=guidance_rescale,
-                           **(dict(heun=lv_rows(self.diffusion, chain, clip_denoised)) if kind == "ddpm_lv" else {}))
+        rows = dict(heun=lv_rows(self.diffusion, chain, clip_denoised)) if kind == "ddpm_lv" else {}
+        with measurement_scope(measurement) if measurement is not None else contextlib.nullcontext():
+            return run_sampler(self.diffusion, self.model, shape, conditioning, device, kind=kind, t_desc=chain[:num_steps],
+                               progress=progress, noise_fn=noise_fn, trajectory=trajectory,
+                               guidance_scale=guidance_scale, guidance_rescale=guidance_rescale, **rows)
 
     @torch.no_grad()
     def sample_with_stitching(self, v_thick_full, vae, patch_size=(8, 192, 192),
@@ -891,11 +947,12 @@ class DDIMSampler(_Sampler):
 
     @torch.no_grad()
     def sample(self, shape, conditioning, num_inference_steps, device, eta=0.0, progress=True, noise_fn=None,
-               trajectory=None, z_init=None, guidance_scale=1.0, guidance_rescale=0.0):
+               trajectory=None, z_init=None, guidance_scale=1.0, guidance_rescale=0.0, measurement=None):
         t_desc = [int(t) for t in self._get_timesteps(num_inference_steps)]
-        return run_sampler(self.diffusion, self.model, shape, conditioning, device, kind="ddim", t_desc=t_desc,
-                           progress=progress, eta=float(eta), noise_fn=noise_fn, trajectory=trajectory, z_init=z_init,
-                           guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
+        with measurement_scope(measurement) if measurement is not None else contextlib.nullcontext():
+            return run_sampler(self.diffusion, self.model, shape, conditioning, device, kind="ddim", t_desc=t_desc,
+                               progress=progress, eta=float(eta), noise_fn=noise_fn, trajectory=trajectory, z_init=z_init,
+                               guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
 
     @torch.no_grad()
     def sample_with_stitching(self, v_thick_full, vae, num_inference_steps=20, patch_size=(8, 192, 192),
@@ -941,11 +998,12 @@ class DPMSolverSampler(_Sampler):
 
     @torch.no_grad()
     def sample(self, shape, conditioning, num_inference_steps, device, progress=True, noise_fn=None, trajectory=None,
-               z_init=None, guidance_scale=1.0, guidance_rescale=0.0):
+               z_init=None, guidance_scale=1.0, guidance_rescale=0.0, measurement=None):
         t_desc = [int(t) for t in self._get_timesteps(num_inference_steps)]
-        return run_sampler(self.diffusion, self.model, shape, conditioning, device, kind="dpmpp", t_desc=t_desc,
-                           progress=progress, noise_fn=noise_fn, trajectory=trajectory, z_init=z_init,
-                           order=self.order, guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
+        with measurement_scope(measurement) if measurement is not None else contextlib.nullcontext():
+            return run_sampler(self.diffusion, self.model, shape, conditioning, device, kind="dpmpp", t_desc=t_desc,
+                               progress=progress, noise_fn=noise_fn, trajectory=trajectory, z_init=z_init,
+                               order=self.order, guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
 
     @torch.no_grad()
     def sample_with_stitching(self, v_thick_full, vae, num_inference_steps=20, patch_size=(8, 192, 192),
