@@ -739,8 +739,9 @@ int ctsi_hybrid_loss_bwd(const float* pred2, const float* z0, const float* noise
  *   in [0, d), all different.
  * ctsi_vgg_prep_bwd: grad_pred (fp32, the shape of x) = sum_c g_c / (2 std_c) on the sampled slices and exactly zero on the
  *   others (the entry clears the tensor itself when num < d); g: the 8-channel image gradient.
- * ctsi_maxpool2_fwd / _bwd: 2 x 2 / stride 2 max pooling of n images (h, w even).  The backward routes each gradient to the
- *   FIRST maximum of its window in (h, w) row-major order (torch's tie rule) and writes zeros to the other three positions.
+ * ctsi_maxpool2_fwd / _bwd: 2 x 2 / stride 2 max pooling of n images (h, w >= 2) to h / 2 x w / 2; an odd last row / column
+ *   takes part in no window (torch's floor).  The backward routes each gradient to the FIRST maximum of its window in (h, w)
+ *   row-major order (torch's tie rule) and writes zeros to the other three positions and to an odd last row / column.
  * ctsi_relu_bf16: x <- max(x, 0) in place.
  * ctsi_feat_loss_fwd: partials[0 .. ctsi_feat_loss_blocks()) <- fixed-order fp64 partial sums of |pred - target| (squared 0)
  *   or (pred - target)^2 over `count` elements.  ctsi_feat_loss_finalize: out[1 + l] = (sum of layer l's partials, stored at

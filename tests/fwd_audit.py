@@ -1,6 +1,7 @@
 """Eager audit of a program's forward pass, launch by launch (used by tests/test_gpu_fwd_audit.py and test_host_fwd_audit.py, and
 by the conv op tests through tests/gpu_utils.run_conv(audit=True) / audit_program: test_gpu_ops.py, test_gpu_vgg_ops.py,
-test_gpu_train_ops.py, shown on the CPU by test_host_conv_op_audit.py).
+test_gpu_train_ops.py, shown on the CPU by test_host_conv_op_audit.py; tests/loss_audit.py sends the forward ops of the
+perceptual-loss and decode-gradient programs through `snapshot` / `check` and keeps the references of their own kinds).
 
 Every forward op of engine.Program / UNetProgram / VAEEncodeProgram / VAEDecodeProgram, of the fp32 engine and of the forward
 halves of the training programs carries an audit record (`Program.op_audit`, parallel to `ops` / `op_meta`).  `audit_forward`

@@ -1,4 +1,5 @@
-"""Eager audit of a training program's backward pass, launch by launch (used by tests/test_gpu_train_backward_audit.py).
+"""Eager audit of a training program's backward pass, launch by launch (used by tests/test_gpu_train_backward_audit.py, and by
+tests/loss_audit.py for the data-gradient, GroupNorm and head launches of the perceptual-loss and decode-gradient programs).
 
 Every backward op of train_engine.UNetTrainProgram / vae_train_engine.VAETrainProgram carries an audit record
 (`Program.op_audit`, parallel to `ops` / `op_meta`).  `audit_backward` runs the backward ops one at a time; for each op with a

@@ -75,14 +75,17 @@ __device__ __forceinline__ uint4 max_u4(uint4 a, uint4 b) {
 }
 
 __global__ void __launch_bounds__(256)
-maxpool2_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int ho, int wo, int c8, long long total) {
-    const long long row = (long long)2 * wo * c8;           // one input row, in 16-byte units
+maxpool2_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int h, int w, int c8, long long total) {
+    const int ho = h / 2, wo = w / 2;
+    const long long row = (long long)w * c8;                 // one input row, in 16-byte units
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
         const int cg = (int)(e % c8);
         long long r = e / c8;
         const int ow = (int)(r % wo);
-        r /= wo;                                             // = image * ho + oh
-        const uint4* src = reinterpret_cast<const uint4*>(x) + (2 * r) * row + (long long)(2 * ow) * c8 + cg;
+        r /= wo;
+        const long long img = r / ho;
+        const int oh = (int)(r - img * ho);                  // an odd last row / column takes part in no window (torch's floor)
+        const uint4* src = reinterpret_cast<const uint4*>(x) + (img * h + 2 * oh) * row + (long long)(2 * ow) * c8 + cg;
         uint4 m = max_u4(src[0], src[c8]);                   // (h, w) row-major: the first maximum wins a tie
         m = max_u4(m, src[row]);
         m = max_u4(m, src[row + c8]);
@@ -91,11 +94,11 @@ maxpool2_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int ho
 }
 
 extern "C" int ctsi_maxpool2_fwd(const void* x, void* y, int n, int h, int w, int c, void* stream) {
-    CTSI_CHECK_ARG(x && y && n > 0 && h > 0 && w > 0 && c > 0 && h % 2 == 0 && w % 2 == 0 && c % 8 == 0,
-                   "ctsi_maxpool2_fwd: bad arguments (n=%d h=%d w=%d c=%d; h, w even, c a multiple of 8)", n, h, w, c);
+    CTSI_CHECK_ARG(x && y && n > 0 && h >= 2 && w >= 2 && c > 0 && c % 8 == 0,
+                   "ctsi_maxpool2_fwd: bad arguments (n=%d h=%d w=%d c=%d; h, w at least 2, c a multiple of 8)", n, h, w, c);
     const long long total = (long long)n * (h / 2) * (w / 2) * (c / 8);
     hipLaunchKernelGGL(maxpool2_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                       (bf16_t*)y, h / 2, w / 2, c / 8, total);
+                       (bf16_t*)y, h, w, c / 8, total);
     CTSI_LAUNCH_CHECK();
     return CTSI_OK;
 }
@@ -121,15 +124,19 @@ __device__ __forceinline__ void route_pair(uint32_t a, uint32_t b, uint32_t c, u
 }
 
 __global__ void __launch_bounds__(256)
-maxpool2_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ gy, bf16_t* __restrict__ gx, int ho, int wo,
+maxpool2_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ gy, bf16_t* __restrict__ gx, int h, int w,
                     int c8, long long total) {
-    const long long row = (long long)2 * wo * c8;
+    const int ho = h / 2, wo = w / 2;
+    const long long row = (long long)w * c8;
+    const uint4 zero = uint4{0u, 0u, 0u, 0u};
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
         const int cg = (int)(e % c8);
         long long r = e / c8;
         const int ow = (int)(r % wo);
         r /= wo;
-        const long long base = (2 * r) * row + (long long)(2 * ow) * c8 + cg;
+        const long long img = r / ho;
+        const int oh = (int)(r - img * ho);
+        const long long base = (img * h + 2 * oh) * row + (long long)(2 * ow) * c8 + cg;
         const uint4* src = reinterpret_cast<const uint4*>(x) + base;
         uint4* dst = reinterpret_cast<uint4*>(gx) + base;
         const uint4 a = src[0], b = src[c8], c = src[row], d = src[row + c8], g = reinterpret_cast<const uint4*>(gy)[e];
@@ -142,15 +149,26 @@ maxpool2_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ gy,
         dst[c8] = ob;
         dst[row] = oc;
         dst[row + c8] = od;
+        // an odd last column / row belongs to no window: its gradient is zero, written by the window beside it
+        const bool edge_w = (w & 1) && ow == wo - 1, edge_h = (h & 1) && oh == ho - 1;
+        if (edge_w) {
+            dst[2 * c8] = zero;
+            dst[row + 2 * c8] = zero;
+        }
+        if (edge_h) {
+            dst[2 * row] = zero;
+            dst[2 * row + c8] = zero;
+            if (edge_w) dst[2 * row + 2 * c8] = zero;
+        }
     }
 }
 
 extern "C" int ctsi_maxpool2_bwd(const void* x, const void* gy, void* gx, int n, int h, int w, int c, void* stream) {
-    CTSI_CHECK_ARG(x && gy && gx && n > 0 && h > 0 && w > 0 && c > 0 && h % 2 == 0 && w % 2 == 0 && c % 8 == 0,
-                   "ctsi_maxpool2_bwd: bad arguments (n=%d h=%d w=%d c=%d; h, w even, c a multiple of 8)", n, h, w, c);
+    CTSI_CHECK_ARG(x && gy && gx && n > 0 && h >= 2 && w >= 2 && c > 0 && c % 8 == 0,
+                   "ctsi_maxpool2_bwd: bad arguments (n=%d h=%d w=%d c=%d; h, w at least 2, c a multiple of 8)", n, h, w, c);
     const long long total = (long long)n * (h / 2) * (w / 2) * (c / 8);
     hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                       (const bf16_t*)gy, (bf16_t*)gx, h / 2, w / 2, c / 8, total);
+                       (const bf16_t*)gy, (bf16_t*)gx, h, w, c / 8, total);
     CTSI_LAUNCH_CHECK();
     return CTSI_OK;
 }

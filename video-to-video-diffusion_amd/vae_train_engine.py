@@ -362,7 +362,10 @@ class VAEDecodeGradProgram(VAETrainProgram):
             def run_gz():
                 lib.ndhwc_bf16_to_ncdhw_f32(zg.ip, _ptr(prog.g_z), n, L, d, h, w, sptr)
 
-            prog._emit(run_gz, "seam.grad_z")      # (a layout turn and a widening cast: exact, no audit record)
+            # a layout turn and a widening cast, checked bit for bit.  (A dict literal: this kind's reference is
+            # tests/loss_audit.py's, not one of the two tables that tests/test_host_fwd_audit.py pins to the keyword-form
+            # records of this file.)
+            prog._emit(run_gz, "seam.grad_z", audit={"kind": "seam.grad_z", "g": zg, "out": prog.g_z})
             prog.release(zg)
             prog.zin.grad = None
 

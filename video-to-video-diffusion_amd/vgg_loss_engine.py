@@ -21,6 +21,9 @@ and gradient are bit-identical run to run.
 In-place ReLU (torchvision's): a feature taken at a conv that another block follows is overwritten by that block's leading
 ReLU before the loss reads it, so it is compared POST-ReLU; only a conv that ends the stack is compared pre-ReLU.  Here the
 ReLU pass runs right behind every conv but the stack's last module, which gives exactly that.
+
+Every launch carries an audit record (engine.Program._emit): references to what it reads and writes and the scalars of its
+formula, from which tests/loss_audit.py recomputes each launch in float64.  The records change nothing about the launches.
 """
 from __future__ import annotations
 
@@ -111,7 +114,7 @@ class VGGLossProgram(PhasedProgram):
                                    p=P, cout=m[2], cin_w=3 if i == 0 else None, act=2 if fused else 0)
                 if relu and not fused:
                     self._emit_relu(f"vgg.{i + 1}.relu", out)
-                nodes.append(dict(kind="conv", i=i, x=x, out=out, relu=relu, conv=conv, feats=[]))
+                nodes.append(dict(node="conv", i=i, x=x, out=out, relu=relu, conv=conv, feats=[]))
                 x = out
             elif m[0] == "pool":
                 out = self.act(1, x.c, x.d, x.h // 2, x.w // 2)
@@ -121,18 +124,21 @@ class VGGLossProgram(PhasedProgram):
                 def run_pool(xp=xp, op=op, xd=xd, xh=xh, xw=xw, xc=xc):
                     lib.maxpool2_fwd(xp, op, xd, xh, xw, xc, sptr)
 
-                self._emit(run_pool, f"vgg.{i}.pool", 0.0, "maxpool2_fwd", nbytes=nbytes)
-                nodes.append(dict(kind="pool", i=i, x=x, out=out, relu=False, feats=[]))
+                self._emit(run_pool, f"vgg.{i}.pool", 0.0, "maxpool2_fwd", nbytes=nbytes,
+                           audit=dict(kind="maxpool2_fwd", x=x, out=out))
+                nodes.append(dict(node="pool", i=i, x=x, out=out, relu=False, feats=[]))
                 x = out
             if i in self.layers:       # (a ReLU index lands on its conv's node: the same post-ReLU tensor)
                 nodes[-1]["feats"].append(self.layers.index(i))
         counts = [0] * nl
         sq = 0 if use_l1 else 1
+        taps: List[Optional[Act]] = [None] * nl      # per compared layer: the Act it is taken from (audit records only)
         for node in nodes:
             a = node["out"]
             half = n_img * a.h * a.w * a.c
             for l in node["feats"]:
                 pp, tp = a.ip, C.c_void_p(a.ip.value + 2 * half)
+                taps[l] = a
                 if self.lpips:
                     pos = a.h * a.w
                     counts[l] = pos                    # LPIPS means over positions, per image
@@ -143,7 +149,10 @@ class VGGLossProgram(PhasedProgram):
                     def run_dist(pp=pp, tp=tp, hp=hp, dst=dst, pos=pos, c=a.c):
                         lib.lpips_dist_fwd(pp, tp, hp, n_img, pos, c, dst, sptr)
 
-                    self._emit(run_dist, f"vgg.{node['i']}.lpips", 0.0, "lpips_dist", nbytes=4.0 * half)
+                    nb = n_img * self.blocks
+                    self._emit(run_dist, f"vgg.{node['i']}.lpips", 0.0, "lpips_dist", nbytes=4.0 * half,
+                               audit=dict(kind="lpips_dist", x=a, n_img=n_img, l=l, half=half, pos=pos, head=head_bufs[l],
+                                          slab=self.partials[l * nb:(l + 1) * nb], partials=self.partials, blocks=self.blocks))
                     continue
                 counts[l] = half
                 dst = C.c_void_p(self.partials.data_ptr() + 8 * l * self.blocks)
@@ -151,7 +160,10 @@ class VGGLossProgram(PhasedProgram):
                 def run_loss(pp=pp, tp=tp, dst=dst, half=half):
                     lib.feat_loss_fwd(pp, tp, half, sq, dst, sptr)
 
-                self._emit(run_loss, f"vgg.{node['i']}.loss", 0.0, "feat_loss", nbytes=4.0 * half)
+                self._emit(run_loss, f"vgg.{node['i']}.loss", 0.0, "feat_loss", nbytes=4.0 * half,
+                           audit=dict(kind="feat_loss", x=a, n_img=n_img, l=l, half=half, sq=sq,
+                                      slab=self.partials[l * self.blocks:(l + 1) * self.blocks], partials=self.partials,
+                                      blocks=self.blocks))
         self.counts = self.persistent((nl,), torch.int64)
         self.counts.copy_(torch.tensor(counts, dtype=torch.int64))
         pa, cn, ob = _ptr(self.partials), _ptr(self.counts), _ptr(self.out)
@@ -162,12 +174,16 @@ class VGGLossProgram(PhasedProgram):
             def run_fin():
                 lib.lpips_finalize(pa, cn, nl, n_img, ob, tm, sptr)
 
-            self._emit(run_fin, "vgg.lpips.finalize", 0.0, "lpips_finalize")
+            self._emit(run_fin, "vgg.lpips.finalize", 0.0, "lpips_finalize",
+                       audit=dict(kind="lpips_finalize", partials=self.partials, counts=self.counts, taps=taps, n_img=n_img,
+                                  blocks=self.blocks, out=self.out))
         else:
             def run_fin():
                 lib.feat_loss_finalize(pa, cn, nl, ob, sptr)
 
-            self._emit(run_fin, "vgg.loss.finalize", 0.0, "feat_loss_finalize")
+            self._emit(run_fin, "vgg.loss.finalize", 0.0, "feat_loss_finalize",
+                       audit=dict(kind="feat_loss_finalize", partials=self.partials, counts=self.counts, taps=taps, n_img=n_img,
+                                  blocks=self.blocks, out=self.out))
         self.end_forward()
 
         # ---- backward (pred half) ------------------------------------------------------------------------------------------
@@ -186,7 +202,9 @@ class VGGLossProgram(PhasedProgram):
                 def run_lgrad(gi=gi, yp=yp, tp=tp, hp=hp, go=go, pos=a.h * a.w, c=a.c):
                     lib.lpips_grad_relu_bwd(gi, yp, tp, hp, go, n_img, pos, c, glp, sptr)
 
-                self._emit(run_lgrad, f"vgg.{node['i']}.grad", 0.0, "lpips_grad_relu_bwd", nbytes=8.0 * half)
+                self._emit(run_lgrad, f"vgg.{node['i']}.grad", 0.0, "lpips_grad_relu_bwd", nbytes=8.0 * half,
+                           audit=dict(kind="lpips_grad_relu", g_in=g, no_g_in=g is None, y=a, n_img=n_img, l=l, half=half,
+                                      pos=a.h * a.w, head=head_bufs[l], gl=self.gl, out=gout))
                 g = gout
             elif node["feats"] or node["relu"]:
                 if g is None and not node["feats"]:
@@ -200,10 +218,12 @@ class VGGLossProgram(PhasedProgram):
                 def run_grad(gi=gi, yp=yp, tp=tp, go=go, half=half, coef=coef, kind=kind, relu=relu):
                     lib.feat_grad_relu_bwd(gi, yp, tp, go, half, coef, kind, relu, glp, sptr)
 
-                self._emit(run_grad, f"vgg.{node['i']}.grad", 0.0, "feat_grad_relu_bwd", nbytes=(8.0 if kind else 6.0) * half)
+                self._emit(run_grad, f"vgg.{node['i']}.grad", 0.0, "feat_grad_relu_bwd", nbytes=(8.0 if kind else 6.0) * half,
+                           audit=dict(kind="feat_grad_relu", g_in=g, no_g_in=g is None, y=a, n_img=n_img, l=list(node["feats"]),
+                                      nl=nl, half=half, coef=coef, loss_kind=kind, relu=relu, sq=sq, gl=self.gl, out=gout))
                 g = gout
             xa = node["x"]
-            if node["kind"] == "pool":
+            if node["node"] == "pool":
                 gx = self.act(1, xa.c, n_img, xa.h, xa.w)
                 xp, gp, gxp, xh, xw, xc = xa.ip, g.ip, gx.ip, xa.h, xa.w, xa.c
 
@@ -211,7 +231,8 @@ class VGGLossProgram(PhasedProgram):
                     lib.maxpool2_bwd(xp, gp, gxp, n_img, xh, xw, xc, sptr)
 
                 self._emit(run_pool_bwd, f"vgg.{node['i']}.pool.bwd", 0.0, "maxpool2_bwd",
-                           nbytes=2.0 * n_img * xa.h * xa.w * xa.c * 2.25)
+                           nbytes=2.0 * n_img * xa.h * xa.w * xa.c * 2.25,
+                           audit=dict(kind="maxpool2_bwd", x=xa, g=g, n_img=n_img, out=gx))
             else:
                 conv = node["conv"]
                 cout, cin = conv.weight.shape[0], conv.weight.shape[1]
@@ -252,7 +273,7 @@ class VGGLossProgram(PhasedProgram):
         def run():
             lib.relu_bf16(ap, cnt, sptr)
 
-        self._emit(run, name, 0.0, "relu_bf16", nbytes=4.0 * cnt)
+        self._emit(run, name, 0.0, "relu_bf16", nbytes=4.0 * cnt, audit=dict(kind="relu", x=a, out=a))
 
     # ---- execution -----------------------------------------------------------------------------------------------------------
     # `args`, the per-distance part of a call, the same tuple for the forward and its backward:
