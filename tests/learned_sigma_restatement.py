@@ -120,6 +120,54 @@ def hybrid_terms(pred2, z0, noise, t, sched, v_pred):
     return mse, torch.where(t0, nll, kl)
 
 
+def hybrid_error_terms(pred2, z0, noise, t, sched, v_pred):
+    """(mse term, bound term) per-element error magnitudes of an fp32 evaluation of `hybrid_terms`, float64: the roundings
+    u = 2^-24 listed in tests/test_gpu_learned_sigma.py::test_hybrid_loss_forward_against_float64, each on the magnitude it acts
+    on, every inherited error carried through, doubled (fused and unfused multiply-adds round differently).  `sched`: the
+    columns of `schedule64`."""
+    u = 2.0 ** -24
+    n, Lc = z0.shape[0], z0.shape[1]
+    col = lambda k: sched[k][t].view(n, 1, 1, 1, 1)
+    a, s_, c1, c2, lb, lp = (col(k) for k in ("a", "s", "c1", "c2", "log_beta", "log_post"))
+    z0, nz, p, vch = z0.double(), noise.double(), pred2[:, :Lc].double(), pred2[:, Lc:].double()
+    zt = a * z0 + s_ * nz
+    if v_pred:
+        target, x0p = a * nz - s_ * z0, a * zt - s_ * p
+        e_t, e_x0 = 3 * u * ((a * nz).abs() + (s_ * z0).abs()), 4 * u * ((a * zt).abs() + (s_ * p).abs())
+    else:
+        target, x0p = nz, (zt - s_ * p) / a
+        e_t, e_x0 = torch.zeros_like(nz), 4 * u * (zt.abs() + (s_ * p).abs()) / a
+    dp = p - target
+    e_dp = e_t + u * dp.abs()
+    mag_mse = 2 * (2 * dp.abs() * e_dp + e_dp ** 2 + u * dp ** 2)
+    f = (vch + 1) / 2
+    lv = f * lb + (1 - f) * lp
+    e_lv = 4 * u * ((f * lb).abs() + ((1 - f) * lp).abs()) + u * lv.abs()
+    inv = torch.exp(-lv)
+    t0 = (t == 0).view(n, 1, 1, 1, 1)
+    q = torch.where(t0, z0 - c1 * x0p - c2 * zt, c1 * (z0 - x0p))
+    e_q = c1 * e_x0 + 4 * u * (z0.abs() + (c1 * x0p).abs() + (c2 * zt).abs())
+    e_quad = inv * (2 * q.abs() * e_q + e_q ** 2) + q ** 2 * inv * (e_lv + 5 * u)
+    ratio = torch.exp(lp - lv)
+    e_kl = e_lv + u * (lv - lp).abs() + ratio * (e_lv + u * (lp - lv).abs() + 3 * u) + u * (ratio - 1).abs()
+    e_nll = e_lv + u * (math.log(2 * math.pi) + lv.abs())
+    parts = torch.where(t0, math.log(2 * math.pi) + lv.abs(), (lv - lp).abs() + (ratio - 1).abs()) + q ** 2 * inv
+    mag_vb = 2 * (0.5 * (e_quad + torch.where(t0, e_nll, e_kl)) + 3 * u * 0.5 * parts)
+    return mag_mse, mag_vb
+
+
+def hybrid_sum_bounds(S, V, S_mag, V_mag, norm, norm_vb, mse=None, vb=None):
+    """The bounds of the five outputs of ctsi_hybrid_loss_fwd from the per-sample float64 sums S, V and the summed error
+    magnitudes S_mag, V_mag (each (B,)): dict(S_b, V_b, mse, vb, total).  u for each fp32 norm factor and the final fp32 store;
+    the scalars are formed from the device's double accumulators, not from the rounded per-sample sums.  `mse`, `vb`: the float64 values of the two terms where the caller has them (else formed here)."""
+    u = 2.0 ** -24
+    mse = (norm * S).sum() if mse is None else mse
+    vb = (norm_vb * V).sum() if vb is None else vb
+    return dict(S_b=S_mag + u * S.abs(), V_b=V_mag + u * V.abs(), mse=(norm * S_mag).sum() + 2 * u * mse.abs(),
+                vb=(norm_vb * V_mag).sum() + 2 * u * vb.abs(),
+                total=(norm * S_mag).sum() + (norm_vb * V_mag).sum() + 2 * u * (mse + vb).abs())
+
+
 def count_norm(mask, shape):
     """The batch / element normalisation of both loss terms, (B,) float64: 1 / (B L d h w) without a mask; with a (B, 1 or L, d)
     mask 1 / (total valid elements) when every sample has the same number of them, else 1 / (B valid_b) per sample.

@@ -295,42 +295,14 @@ def test_hybrid_loss_forward_against_float64(pkg, shape, v_pred, tag):
     g, t = c["g"], c["t"]
     ref = LR.hybrid_loss(c["pred2"].double(), c["z0"], c["noise"], t, g, c["weight"], c["mask"], v_pred)
     mse_e, vb_e = LR.hybrid_terms(c["pred2"].double(), c["z0"], c["noise"], t, LR.schedule64(g), v_pred)
-    sc = LR.schedule64(g)
-    col = lambda k: sc[k][t].view(n, 1, 1, 1, 1)
-    a, s_, c1, c2, lb, lp = (col(k) for k in ("a", "s", "c1", "c2", "log_beta", "log_post"))
-    z0, nz, p, vch = c["z0"].double(), c["noise"].double(), c["pred2"][:, :Lc].double(), c["pred2"][:, Lc:].double()
-    u = U24
-    zt = a * z0 + s_ * nz
-    if v_pred:
-        target, x0p = a * nz - s_ * z0, a * zt - s_ * p
-        e_t, e_x0 = 3 * u * ((a * nz).abs() + (s_ * z0).abs()), 4 * u * ((a * zt).abs() + (s_ * p).abs())
-    else:
-        target, x0p = nz, (zt - s_ * p) / a
-        e_t, e_x0 = torch.zeros_like(nz), 4 * u * (zt.abs() + (s_ * p).abs()) / a
-    dp = p - target
-    e_dp = e_t + u * dp.abs()
-    mag_mse = 2 * (2 * dp.abs() * e_dp + e_dp ** 2 + u * dp ** 2)
-    f = (vch + 1) / 2
-    lv = f * lb + (1 - f) * lp
-    e_lv = 4 * u * ((f * lb).abs() + ((1 - f) * lp).abs()) + u * lv.abs()
-    inv = torch.exp(-lv)
-    t0 = (t == 0).view(n, 1, 1, 1, 1)
-    q = torch.where(t0, z0 - c1 * x0p - c2 * zt, c1 * (z0 - x0p))
-    e_q = c1 * e_x0 + 4 * u * (z0.abs() + (c1 * x0p).abs() + (c2 * zt).abs())
-    e_quad = inv * (2 * q.abs() * e_q + e_q ** 2) + q ** 2 * inv * (e_lv + 5 * u)
-    ratio = torch.exp(lp - lv)
-    e_kl = e_lv + u * (lv - lp).abs() + ratio * (e_lv + u * (lp - lv).abs() + 3 * u) + u * (ratio - 1).abs()
-    e_nll = e_lv + u * (math.log(2 * math.pi) + lv.abs())
-    parts = torch.where(t0, math.log(2 * math.pi) + lv.abs(), (lv - lp).abs() + (ratio - 1).abs()) + q ** 2 * inv
-    mag_vb = 2 * (0.5 * (e_quad + torch.where(t0, e_nll, e_kl)) + 3 * u * 0.5 * parts)
+    mag_mse, mag_vb = LR.hybrid_error_terms(c["pred2"], c["z0"], c["noise"], t, LR.schedule64(g), v_pred)      # the list above
     me = c["me"]
     S_ref, V_ref = (me * mse_e).reshape(n, -1).sum(1), (me * vb_e).reshape(n, -1).sum(1)
     S_b, V_b = (me * mag_mse).reshape(n, -1).sum(1), (me * mag_vb).reshape(n, -1).sum(1)
     norm, nvb = c["norm"].double(), c["norm_vb"].double()
-    checks = [("S_b", out[3:3 + n], S_ref, S_b + U24 * S_ref.abs()), ("V_b", out[3 + n:], V_ref, V_b + U24 * V_ref.abs()),
-              ("mse", out[1], ref["mse"], (norm * S_b).sum() + 2 * U24 * ref["mse"].abs()),
-              ("vb", out[2], ref["vb"], (nvb * V_b).sum() + 2 * U24 * ref["vb"].abs()),
-              ("total", out[0], ref["total"], (norm * S_b).sum() + (nvb * V_b).sum() + 2 * U24 * ref["total"].abs())]
+    bd = LR.hybrid_sum_bounds(S_ref, V_ref, S_b, V_b, norm, nvb, ref["mse"], ref["vb"])
+    checks = [("S_b", out[3:3 + n], S_ref, bd["S_b"]), ("V_b", out[3 + n:], V_ref, bd["V_b"]), ("mse", out[1], ref["mse"], bd["mse"]),
+              ("vb", out[2], ref["vb"], bd["vb"]), ("total", out[0], ref["total"], bd["total"])]
     for name, got, want, bound in checks:
         err = (got - want).abs()
         print(f"hybrid fwd {shape} v_pred={v_pred} {tag} {name}: got {got.reshape(-1).tolist()} float64 {want.reshape(-1).tolist()} "
