@@ -100,7 +100,35 @@ def test_depth_residual_adj_against_the_passes_it_replaces():
     assert torch.equal(out, g)
 
 
-# ---- ctsi_guide_z0 ----------------------------------------------------------------------------------------------------
+# (n, d_in, d_out, hw, profile): 16-byte path with a ragged last tile, both kernels 64 wide; scalar path; deep volume, both 32
+# wide -- ctsi_depth_project holds (d_out + 2 d_in) rows, ctsi_depth_residual_adj (d_out + d_in) rows and 8 d_out bytes of row
+# table: (300 + 100) x 256 = 102400 and (300 + 50) x 256 + 2400 = 92000 bytes at 64 positions, both past the 80 KiB of two blocks
+SHARED_FRAME = [(2, 8, 48, 268, "box"), (1, 2, 6, 37, "box"), (1, 50, 300, 37, "gauss1.0")]
+
+
+@pytest.mark.parametrize("case", SHARED_FRAME, ids=lambda s: f"n{s[0]}-{s[1]}to{s[2]}-hw{s[3]}")
+def test_depth_residual_adj_sumsq_is_the_projection_statistic(case):
+    """One channel per sample: the per-sample sum r^2 of ctsi_depth_residual_adj has the bits of column 0 of the statistics table
+    of ctsi_depth_project + ctsi_depth_project_finalize on the same x, y.  Both evaluate the input residual in fp64 by the same
+    fma sequence over the column-tile frame (csrc/depth_tile.h), reduce it by the same tree into the same slots and fold the
+    slots in the same order (csrc/fixed_reduce.h); the tile widths agree at these depths."""
+    from tests.test_gpu_consistency_ops import launch_project
+    n, d_in, d_out, hw, name = case
+    h, w = HW[hw]
+    prof = CS.SliceProfile(d_in, d_out, **PROFILES[name])
+    seed = 300 + 11 * d_in + hw
+    x = torch.tanh(formula_input((n, 1, d_out, h, w), seed)).to(DEV)
+    other = torch.tanh(formula_input((n, 1, d_out, h, w), seed + 1)).double()
+    y = (torch.einsum("kj,ncjhw->nckhw", torch.from_numpy(prof.W), other)
+         + 0.02 * formula_noise(seed, (n, 1, d_in, h, w)).double()).clamp(-1, 1).float().contiguous().to(DEV)
+    _, sumsq, _ = launch_residual_adj(prof, x, y)
+    table = launch_project(prof, x.clone(), y, 1, 0)
+    print(f"\n[n{n} {d_in}->{d_out} hw {hw}] sum r^2 {sumsq.tolist()}  table column 0 {table[:, 0].tolist()}")
+    assert float(sumsq.min()) > 0
+    assert torch.equal(sumsq.view(torch.int64), table[:, 0].contiguous().view(torch.int64))
+
+
+# ---- ctsi_guide_z0----------------------------------------------------------------------------------------------------
 def launch_z0(z_nd, eps_nd, alpha, sigma, mode, clip, shape):
     ctx = E.Ctx.get(z_nd.device)
     n, c, d, h, w = shape

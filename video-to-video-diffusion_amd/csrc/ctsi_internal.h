@@ -119,6 +119,8 @@ __device__ __forceinline__ float nan_to_num_f(float v) {
 }
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+static inline bool aligned_to(const void* p, unsigned bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }   // bytes: a power of 2
+static inline bool aligned16(const void* p) { return aligned_to(p, 16); }
 
 // ---- conv3_halo.hip (3x3x3 halo-tile kernel), driven through the conv plan in conv_mfma.hip ------------
 struct Conv3HaloParams {

@@ -4,37 +4,18 @@
 //   W      [d_in][d_out] fp32, rows sum to 1          band_w [d_in][2]  first / last non-zero column of each row of W
 //   P      [d_out][d_in] fp32                         band_p [d_out][2] first / last non-zero column of each row of P
 // measure / measure_adj stream: one thread per output element (four with 16-byte accesses), the band of W bounds the sum.
-// project is the hot kernel: one block of four waves owns TILE consecutive positions of one plane and stages the whole column
-// tile in LDS -- xs[d_out][TILE], ys[d_in][TILE], rs[d_in][TILE] -- so x is read from HBM once and written once whatever
-// `iters` is.  A lane is a position (unit-stride LDS rows: no bank conflicts); the waves split the k rows in the residual phase
-// and the j rows in the update phase, so at TILE = 64 the W[k][j] / P[j][k] operand is wave-uniform (scalar loads).  TILE = 32
-// (deep volumes) puts two rows in a wave.  Sums run over the band supports only, ascending, one fma per term.
+// project is the hot kernel, written against the column-tile frame (depth_tile.h): the tile in LDS is xs[d_out][TILE],
+// ys[d_in][TILE], rs[d_in][TILE], so x is read from HBM once and written once whatever `iters` is.  The waves split the k rows
+// in the residual phase and the j rows in the update phase.  Sums run over the band supports only, ascending, one fma per term.
 // Statistics (partials != NULL): the residual of the input and of the output, re-evaluated in fp64 from the fp32 values the
-// kernel holds (products of two fp32 are exact in fp64; the sum runs ascending over the band), reduced per block in a fixed
-// order; ctsi_depth_project_finalize adds the block partials in index order.  No atomics: the same bits on every run.
-#include "ctsi_internal.h"
+// kernel holds (products of two fp32 are exact in fp64; the sum runs ascending over the band), reduced per block and folded per
+// plane by ctsi_depth_project_finalize in the fixed order of fixed_reduce.h.
+#include "depth_tile.h"
 
 namespace {
 
-constexpr int DC_MAX_D_IN = 64;
-constexpr int DC_MAX_D_OUT = 512;
-constexpr int DC_THREADS = 256;
-constexpr int DC_WAVES = DC_THREADS / 64;
-constexpr int DC_SLOT = 32;                  // positions per partial slot: the narrow tile, so the layout fits both tiles
-constexpr int DC_LDS_TWO_BLOCKS = 80 * 1024; // half of the CU's 160 KiB
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-inline int project_tile(int d_in, int d_out) {
-    // two blocks per CU at the 64-wide tile (256 B: the reduction scratch beside the tile), else the 32-wide one
-    return (size_t)(d_out + 2 * d_in) * 64 * sizeof(float) + 256 <= (size_t)DC_LDS_TWO_BLOCKS ? 64 : 32;
-}
-
-__device__ __forceinline__ void band_of(const int* __restrict__ band, int row, int limit, int& lo, int& hi) {
-    lo = band[2 * row], hi = band[2 * row + 1];
-    lo = lo < 0 ? 0 : lo;                    // a bad table must not index outside the tile
-    hi = hi >= limit ? limit - 1 : hi;
-}
+// the column tile, its copy of y and the residual rows
+inline size_t project_lds(int d_in, int d_out, int tile) { return (size_t)(d_out + 2 * d_in) * tile * sizeof(float); }
 
 // ---- measure: y[plane][k][p] = sum_j W[k][j] x[plane][j][p] --------------------------------------------------------
 // grid (ceil(hw / (256 V)), d_in, planes)
@@ -134,7 +115,7 @@ template <int TILE>
 __device__ __forceinline__ void residual_stats(const float* xs, const float* ys, const ProjectArgs& a, int row0, int pos,
                                                bool live, double& sum, double& mx) {
     if (!live) return;
-    constexpr int STRIDE = DC_WAVES * (64 / TILE);
+    constexpr int STRIDE = DT_WAVES * (64 / TILE);
     for (int k = row0; k < a.d_in; k += STRIDE) {
         int lo, hi;
         band_of(a.band_w, k, a.d_out, lo, hi);
@@ -148,100 +129,28 @@ __device__ __forceinline__ void residual_stats(const float* xs, const float* ys,
     }
 }
 
-// every value of v[5] reduced over the block in a fixed order: sums for 0, 1, 4, maxima for 2, 3 (thread 0 holds the result)
-__device__ __forceinline__ void block_reduce5(double* v, double* red /* [5][DC_WAVES] */) {
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-        double s = v[q];
-        for (int o = 32; o > 0; o >>= 1) {
-            const double t = __shfl_down(s, o, 64);
-            s = (q == 2 || q == 3) ? (t > s ? t : s) : s + t;
-        }
-        if ((threadIdx.x & 63) == 0) red[q * DC_WAVES + (threadIdx.x >> 6)] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < 5; ++q) {
-            double s = red[q * DC_WAVES];
-            for (int w = 1; w < DC_WAVES; ++w) {
-                const double t = red[q * DC_WAVES + w];
-                s = (q == 2 || q == 3) ? (t > s ? t : s) : s + t;
-            }
-            v[q] = s;
-        }
-    }
-}
+// the five statistics: sums for 0, 1, 4, maxima for 2, 3
+constexpr unsigned DC_STAT_MAX = 0b01100;
 
 template <int TILE, bool VEC>
-__global__ void __launch_bounds__(DC_THREADS)
+__global__ void __launch_bounds__(DT_THREADS)
 depth_project_kernel(const ProjectArgs a) {
     extern __shared__ __align__(16) float dc_lds[];
-    __shared__ double red[5 * DC_WAVES];
-    constexpr int RPW = 64 / TILE;               // rows per wave
-    constexpr int STRIDE = DC_WAVES * RPW;
+    __shared__ double red[5 * DT_WAVES];
+    const DepthTile<TILE, VEC> t(a.tiles_pp, a.hw);
+    constexpr int STRIDE = DepthTile<TILE, VEC>::STRIDE;
     float* xs = dc_lds;                          // [d_out][TILE]
     float* ys = xs + a.d_out * TILE;             // [d_in][TILE]
     float* rs = ys + a.d_in * TILE;              // [d_in][TILE]
-    const int tile = blockIdx.x % a.tiles_pp;
-    const long long plane = blockIdx.x / a.tiles_pp;
-    const int p0 = tile * TILE;
-    const int valid = a.hw - p0 < TILE ? a.hw - p0 : TILE;
-    float* xg = a.x + plane * a.d_out * (long long)a.hw + p0;
-    const float* yg = a.y + plane * a.d_in * (long long)a.hw + p0;
-
-    // stage the column tile; positions past the plane's end read as 0 and are never stored.  Four independent loads per
-    // thread are issued before the first LDS store: a block then has its whole tile in flight at the production depth
-    // ((48 + 8) rows x 64 positions = 3.5 16-byte loads per thread), not one load per thread and trip
-    if (VEC) {
-        constexpr int Q = TILE / 4;
-        const int total = (a.d_out + a.d_in) * Q;
-        for (int base = threadIdx.x; base < total; base += 4 * DC_THREADS) {
-            float4 t[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int i = base + u * DC_THREADS;
-                const int row = i / Q, p = (i - row * Q) * 4;
-                t[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (i < total && p < valid)
-                    t[u] = row < a.d_out ? *reinterpret_cast<const float4*>(xg + (long long)row * a.hw + p)
-                                         : *reinterpret_cast<const float4*>(yg + (long long)(row - a.d_out) * a.hw + p);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int i = base + u * DC_THREADS;
-                const int row = i / Q, p = (i - row * Q) * 4;
-                if (i < total) *reinterpret_cast<float4*>(xs + row * TILE + p) = t[u];    // ys follows xs: one row index
-            }
-        }
-    } else {
-        const int total = (a.d_out + a.d_in) * TILE;
-        for (int base = threadIdx.x; base < total; base += 4 * DC_THREADS) {
-            float t[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int i = base + u * DC_THREADS;
-                const int row = i / TILE, p = i - row * TILE;
-                t[u] = 0.0f;
-                if (i < total && p < valid)
-                    t[u] = row < a.d_out ? xg[(long long)row * a.hw + p] : yg[(long long)(row - a.d_out) * a.hw + p];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int i = base + u * DC_THREADS;
-                if (i < total) xs[i] = t[u];          // row * TILE + p == i
-            }
-        }
-    }
+    float* xg = a.x + t.plane * a.d_out * (long long)a.hw + t.p0;
+    const float* yg = a.y + t.plane * a.d_in * (long long)a.hw + t.p0;
+    t.stage_rows(xs, xg, yg, a.d_out, a.d_in, a.hw);
     __syncthreads();
 
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int pos = lane % TILE;
-    const int row0 = wave * RPW + lane / TILE;    // RPW == 1: wave-uniform, so W / P / band loads are scalar
+    const int pos = t.pos(), row0 = t.row0();
     const bool stats = a.partials != nullptr;
     double st[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    if (stats) residual_stats<TILE>(xs, ys, a, row0, pos, pos < valid, st[0], st[2]);
+    if (stats) residual_stats<TILE>(xs, ys, a, row0, pos, pos < t.valid, st[0], st[2]);
 
     for (int it = 0; it < a.iters; ++it) {
         // residual: rs[k] = ys[k] - sum_j W[k][j] xs[j]
@@ -265,7 +174,7 @@ depth_project_kernel(const ProjectArgs a) {
             float v = xs[j * TILE + pos] + acc;
             if (clamp) {
                 const float c = fminf(fmaxf(v, a.lo), a.hi);
-                if (c != v && pos < valid) st[4] += 1.0;
+                if (c != v && pos < t.valid) st[4] += 1.0;
                 v = c;
             }
             xs[j * TILE + pos] = v;
@@ -273,85 +182,27 @@ depth_project_kernel(const ProjectArgs a) {
         __syncthreads();
     }
 
-    if (stats) residual_stats<TILE>(xs, ys, a, row0, pos, pos < valid, st[1], st[3]);
-
-    if (VEC) {
-        constexpr int Q = TILE / 4;
-        for (int i = threadIdx.x; i < a.d_out * Q; i += DC_THREADS) {
-            const int row = i / Q, p = (i - row * Q) * 4;
-            if (p < valid)
-                *reinterpret_cast<float4*>(xg + (long long)row * a.hw + p) = *reinterpret_cast<const float4*>(xs + row * TILE + p);
-        }
-    } else {
-        for (int i = threadIdx.x; i < a.d_out * TILE; i += DC_THREADS) {
-            const int row = i / TILE, p = i - row * TILE;
-            if (p < valid) xg[(long long)row * a.hw + p] = xs[row * TILE + p];
-        }
-    }
-
+    if (stats) residual_stats<TILE>(xs, ys, a, row0, pos, pos < t.valid, st[1], st[3]);
+    t.store_rows(xg, xs, a.d_out, a.hw);
     if (stats) {
-        block_reduce5(st, red);
-        if (threadIdx.x == 0) {
-            // one slot per DC_SLOT positions: a 64-wide tile owns two, the second one (when the plane has it) holds zeros
-            const int slot = tile * (TILE / DC_SLOT);
-            double* out = a.partials + (plane * a.slots_pp + slot) * 5;
-            for (int q = 0; q < 5; ++q) out[q] = st[q];
-            if (TILE / DC_SLOT == 2 && slot + 1 < a.slots_pp)
-                for (int q = 0; q < 5; ++q) out[5 + q] = 0.0;
-        }
+        block_reduce<5, DC_STAT_MAX>(st, red);
+        if (threadIdx.x == 0) t.template write_slot<5>(a.partials, a.slots_pp, st);
     }
 }
 
-// one block per plane: thread t folds slots t, t + 256, ... in index order (neighbouring lanes read neighbouring slots), then
-// the 256 values go through the fixed shuffle tree of block_reduce5
-__global__ void __launch_bounds__(DC_THREADS)
-depth_project_finalize_kernel(const double* __restrict__ partials, double* __restrict__ stats, int slots_pp) {
-    __shared__ double red[5 * DC_WAVES];
-    const double* p = partials + (long long)blockIdx.x * slots_pp * 5;
-    double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    // four slots' loads are issued before the first use: one block walks a whole plane's slots (8192 at 512 x 512), and a
-    // trip per slot would pay the memory latency 32 times over
-    for (int base = threadIdx.x; base < slots_pp; base += 4 * DC_THREADS) {
-        double t[4][5];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int i = base + u * DC_THREADS;
-#pragma unroll
-            for (int q = 0; q < 5; ++q) t[u][q] = i < slots_pp ? p[(long long)i * 5 + q] : 0.0;     // 0: the identity of both folds
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int q = 0; q < 5; ++q) v[q] = (q == 2 || q == 3) ? (t[u][q] > v[q] ? t[u][q] : v[q]) : v[q] + t[u][q];
-    }
-    block_reduce5(v, red);
-    if (threadIdx.x == 0)
-        for (int q = 0; q < 5; ++q) stats[(long long)blockIdx.x * 5 + q] = v[q];
-}
-
-template <int TILE, bool VEC>
-void project_launch(const ProjectArgs& a, long long blocks, size_t lds, void* stream) {
-    auto k = depth_project_kernel<TILE, VEC>;
-    static CtsiPerDeviceOnce attr_once;
-    if (attr_once.first()) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, DC_LDS_TWO_BLOCKS);
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(DC_THREADS), lds, (hipStream_t)stream, a);
-}
-
-inline int slots_per_plane(int hw) { return (hw + DC_SLOT - 1) / DC_SLOT; }
+struct ProjectKernel {
+    template <int TILE, bool VEC>
+    static auto get() { return depth_project_kernel<TILE, VEC>; }
+};
 
 }  // namespace
-
-#define DC_CHECK_DEPTHS(fn, d_in, d_out)                                                                         \
-    CTSI_CHECK_ARG((d_in) <= DC_MAX_D_IN && (d_out) <= DC_MAX_D_OUT,                                            \
-                   fn ": depths d_in=%d d_out=%d exceed the limits d_in <= %d, d_out <= %d", (d_in), (d_out),  \
-                   DC_MAX_D_IN, DC_MAX_D_OUT)
 
 extern "C" int ctsi_depth_measure(const float* x, const float* W, const int* band, float* y_out, int planes, int d_in,
                                   int d_out, int hw, void* stream) {
     CTSI_CHECK_ARG(x && W && band && y_out, "ctsi_depth_measure: null argument");
     CTSI_CHECK_ARG(planes > 0 && planes <= 65535 && d_in > 0 && d_out > 0 && hw > 0,
                    "ctsi_depth_measure: bad sizes planes=%d d_in=%d d_out=%d hw=%d", planes, d_in, d_out, hw);
-    DC_CHECK_DEPTHS("ctsi_depth_measure", d_in, d_out);
+    DT_CHECK_DEPTHS("ctsi_depth_measure", d_in, d_out);
     if ((hw % 4) == 0 && aligned16(x) && aligned16(y_out))
         hipLaunchKernelGGL((depth_measure_kernel<4>), dim3((unsigned)ceil_div(hw, 1024), (unsigned)d_in, (unsigned)planes),
                            dim3(256), 0, (hipStream_t)stream, x, W, band, y_out, d_in, d_out, hw);
@@ -367,7 +218,7 @@ extern "C" int ctsi_depth_measure_adj(const float* g_y, const float* W, const in
     CTSI_CHECK_ARG(g_y && W && band && g_x, "ctsi_depth_measure_adj: null argument");
     CTSI_CHECK_ARG(planes > 0 && planes <= 65535 && d_in > 0 && d_out > 0 && hw > 0,
                    "ctsi_depth_measure_adj: bad sizes planes=%d d_in=%d d_out=%d hw=%d", planes, d_in, d_out, hw);
-    DC_CHECK_DEPTHS("ctsi_depth_measure_adj", d_in, d_out);
+    DT_CHECK_DEPTHS("ctsi_depth_measure_adj", d_in, d_out);
     if ((hw % 4) == 0 && aligned16(g_y) && aligned16(g_x))
         hipLaunchKernelGGL((depth_measure_adj_kernel<4>), dim3((unsigned)ceil_div(hw, 1024), (unsigned)d_out, (unsigned)planes),
                            dim3(256), 0, (hipStream_t)stream, g_y, W, band, g_x, scale, accumulate, d_in, d_out, hw);
@@ -390,27 +241,20 @@ extern "C" int ctsi_depth_project(float* x, const float* y, const float* W, cons
     CTSI_CHECK_ARG(x && y && W && P && band_w && band_p, "ctsi_depth_project: null argument");
     CTSI_CHECK_ARG(planes > 0 && d_in > 0 && d_out > 0 && hw > 0,
                    "ctsi_depth_project: bad sizes planes=%d d_in=%d d_out=%d hw=%d", planes, d_in, d_out, hw);
-    DC_CHECK_DEPTHS("ctsi_depth_project", d_in, d_out);
+    DT_CHECK_DEPTHS("ctsi_depth_project", d_in, d_out);
     CTSI_CHECK_ARG(iters >= 1, "ctsi_depth_project: iters=%d must be >= 1", iters);
     CTSI_CHECK_ARG(clamp_mode >= 0 && clamp_mode <= 2, "ctsi_depth_project: clamp_mode=%d must be 0, 1 or 2", clamp_mode);
     CTSI_CHECK_ARG(clamp_mode == 0 || clamp_lo <= clamp_hi, "ctsi_depth_project: clamp_lo=%g > clamp_hi=%g",
                    (double)clamp_lo, (double)clamp_hi);
-    const int tile = project_tile(d_in, d_out);
+    const int tile = tile_for(project_lds(d_in, d_out, 64));
     const int tiles_pp = ceil_div(hw, tile);
     const long long blocks = (long long)planes * tiles_pp;
     CTSI_CHECK_ARG(blocks < (1ll << 31) && ctsi_depth_project_blocks(planes, hw) > 0,
                    "ctsi_depth_project: planes=%d hw=%d give too many tiles", planes, hw);
-    const size_t lds = (size_t)(d_out + 2 * d_in) * tile * sizeof(float);
     const ProjectArgs a = {x, y, W, P, band_w, band_p, partials, iters, clamp_mode, clamp_lo, clamp_hi,
                            d_in, d_out, hw, tiles_pp, slots_per_plane(hw)};
     const bool vec = (hw % 4) == 0 && aligned16(x) && aligned16(y);
-    if (tile == 64) {
-        if (vec) project_launch<64, true>(a, blocks, lds, stream);
-        else project_launch<64, false>(a, blocks, lds, stream);
-    } else {
-        if (vec) project_launch<32, true>(a, blocks, lds, stream);
-        else project_launch<32, false>(a, blocks, lds, stream);
-    }
+    launch_tiled<ProjectKernel>(a, tile, vec, blocks, project_lds(d_in, d_out, tile), stream);
     CTSI_LAUNCH_CHECK();
     return CTSI_OK;
 }
@@ -420,9 +264,9 @@ extern "C" int ctsi_depth_project_finalize(const double* partials, double* stats
     CTSI_CHECK_ARG(partials && stats, "ctsi_depth_project_finalize: null argument");
     CTSI_CHECK_ARG(planes > 0 && hw > 0 && d_in > 0 && ctsi_depth_project_blocks(planes, hw) > 0,
                    "ctsi_depth_project_finalize: bad sizes planes=%d hw=%d d_in=%d", planes, hw, d_in);
-    CTSI_CHECK_ARG(d_in <= DC_MAX_D_IN, "ctsi_depth_project_finalize: d_in=%d exceeds the limit %d", d_in, DC_MAX_D_IN);
-    hipLaunchKernelGGL(depth_project_finalize_kernel, dim3((unsigned)planes), dim3(DC_THREADS), 0, (hipStream_t)stream,
-                       partials, stats, slots_per_plane(hw));
+    CTSI_CHECK_ARG(d_in <= DT_MAX_D_IN, "ctsi_depth_project_finalize: d_in=%d exceeds the limit %d", d_in, DT_MAX_D_IN);
+    hipLaunchKernelGGL((fold_slots_kernel<5, DC_STAT_MAX>), dim3((unsigned)planes), dim3(FR_THREADS), 0, (hipStream_t)stream,
+                       partials, stats, (long long)slots_per_plane(hw), 5);
     CTSI_LAUNCH_CHECK();
     return CTSI_OK;
 }

@@ -12,10 +12,10 @@
 //                of `plane` voxels the fp64 sum of std, sum of std^2 and max of std.
 //   calibration  per plane the fp64 sum of (mean - target)^2, the sum of std^2 and the counts of |mean - target| <= std and
 //                <= 2 std, all decided in fp64 on the fp32 values (differences and doublings of fp32 values are exact there).
-// The two tables are built like the projection's (depth_consistency.hip): one block owns ENS_CHUNK consecutive voxels of one
-// plane and writes one slot of partials in a fixed shuffle order; a second launch, one block per plane, folds the plane's
-// slots in index order.  No atomics, every slot written by exactly one block: the same bits on every run.
-#include "ctsi_internal.h"
+// The two tables go through fixed_reduce.h: one block owns ENS_CHUNK consecutive voxels of one plane and writes one slot of
+// partials (std >= 0, so 0 is the identity of the maximum too); a second launch, one block per plane, folds the plane's slots.
+// No atomics, every slot written by exactly one block: the same bits on every run.
+#include "fixed_reduce.h"
 #include <limits.h>
 
 namespace {
@@ -24,7 +24,6 @@ constexpr int ENS_THREADS = 256;
 constexpr int ENS_MAX_BLOCKS = 2048;         // accumulate: 256 CUs x 8 blocks, the rest by the grid-stride loop
 constexpr int ENS_CHUNK = 4096;              // tables: voxels of one plane per block (four 16-byte loads per thread)
 constexpr int ENS_SLOT = 4;                  // doubles per partial slot (finalize fills three)
-constexpr int ENS_WAVES = ENS_THREADS / 64;
 
 template <int V>
 struct alignas(4 * V) Pack {
@@ -109,33 +108,6 @@ void accumulate_launch(const float* x, int rows, long long count, int seen, floa
                            (hipStream_t)stream, x, rows, count, seen, mean, m2, head, nvec, tail);
 }
 
-// Q values per thread reduced over the block in a fixed order, bit q of MAXMASK set: a maximum, else a sum (thread 0 holds
-// the result)
-template <int Q, unsigned MAXMASK>
-__device__ __forceinline__ void block_reduce(double* v, double* red /* [Q][ENS_WAVES] */) {
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        double s = v[q];
-        for (int o = 32; o > 0; o >>= 1) {
-            const double t = __shfl_down(s, o, 64);
-            s = ((MAXMASK >> q) & 1u) ? (t > s ? t : s) : s + t;
-        }
-        if ((threadIdx.x & 63) == 0) red[q * ENS_WAVES + (threadIdx.x >> 6)] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            double s = red[q * ENS_WAVES];
-            for (int w = 1; w < ENS_WAVES; ++w) {
-                const double t = red[q * ENS_WAVES + w];
-                s = ((MAXMASK >> q) & 1u) ? (t > s ? t : s) : s + t;
-            }
-            v[q] = s;
-        }
-    }
-}
-
 __device__ __forceinline__ float std_of(float m2, float denom) {
 #pragma clang fp contract(off)
     if (denom <= 0.0f) return 0.0f;                // one member
@@ -155,7 +127,7 @@ template <bool VEC>
 __global__ void __launch_bounds__(ENS_THREADS)
 ensemble_finalize_kernel(const float* __restrict__ m2, float* __restrict__ sd, float denom, long long plane, int slots_pp,
                          double* __restrict__ partials) {
-    __shared__ double red[3 * ENS_WAVES];
+    __shared__ double red[3 * FR_WAVES];
     const int slot = blockIdx.x % slots_pp;
     const long long p0 = (long long)slot * ENS_CHUNK;
     const long long base = (long long)(blockIdx.x / slots_pp) * plane + p0;
@@ -205,7 +177,7 @@ template <bool VEC>
 __global__ void __launch_bounds__(ENS_THREADS)
 ensemble_calibration_kernel(const float* __restrict__ mean, const float* __restrict__ sd, const float* __restrict__ target,
                             long long plane, int slots_pp, double* __restrict__ partials) {
-    __shared__ double red[4 * ENS_WAVES];
+    __shared__ double red[4 * FR_WAVES];
     const int slot = blockIdx.x % slots_pp;
     const long long p0 = (long long)slot * ENS_CHUNK;
     const long long base = (long long)(blockIdx.x / slots_pp) * plane + p0;
@@ -239,29 +211,6 @@ ensemble_calibration_kernel(const float* __restrict__ mean, const float* __restr
         out[0] = v[0], out[1] = v[1], out[2] = v[2], out[3] = v[3];
     }
 }
-
-// one block per plane: thread t folds slots t, t + 256, ... in index order, then the fixed tree of block_reduce
-template <int Q, unsigned MAXMASK>
-__global__ void __launch_bounds__(ENS_THREADS)
-ensemble_fold_kernel(const double* __restrict__ partials, double* __restrict__ stats, int slots_pp) {
-    __shared__ double red[Q * ENS_WAVES];
-    const double* p = partials + (long long)blockIdx.x * slots_pp * ENS_SLOT;
-    double v[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) v[q] = 0.0;           // 0: the identity of both folds (std >= 0)
-    for (int i = threadIdx.x; i < slots_pp; i += ENS_THREADS)
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const double t = p[(long long)i * ENS_SLOT + q];
-            v[q] = ((MAXMASK >> q) & 1u) ? (t > v[q] ? t : v[q]) : v[q] + t;
-        }
-    block_reduce<Q, MAXMASK>(v, red);
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int q = 0; q < Q; ++q) stats[(long long)blockIdx.x * Q + q] = v[q];
-}
-
-inline bool aligned_to(const void* p, unsigned bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
 
 inline long long slots_per_plane(long long plane) { return (plane + ENS_CHUNK - 1) / ENS_CHUNK; }
 
@@ -323,8 +272,8 @@ extern "C" int ctsi_ensemble_finalize(const float* m2, float* std_out, int membe
         hipLaunchKernelGGL((ensemble_finalize_kernel<false>), dim3(blocks), dim3(ENS_THREADS), 0, (hipStream_t)stream, m2,
                            std_out, denom, plane, spp, partials);
     CTSI_LAUNCH_CHECK();
-    hipLaunchKernelGGL((ensemble_fold_kernel<3, 0x4u>), dim3((unsigned)planes), dim3(ENS_THREADS), 0, (hipStream_t)stream,
-                       partials, stats, spp);
+    hipLaunchKernelGGL((fold_slots_kernel<3, 0x4u>), dim3((unsigned)planes), dim3(FR_THREADS), 0, (hipStream_t)stream,
+                       partials, stats, (long long)spp, ENS_SLOT);
     CTSI_LAUNCH_CHECK();
     return CTSI_OK;
 }
@@ -345,8 +294,8 @@ extern "C" int ctsi_ensemble_calibration(const float* mean, const float* std_in,
         hipLaunchKernelGGL((ensemble_calibration_kernel<false>), dim3(blocks), dim3(ENS_THREADS), 0, (hipStream_t)stream, mean,
                            std_in, target, plane, spp, partials);
     CTSI_LAUNCH_CHECK();
-    hipLaunchKernelGGL((ensemble_fold_kernel<4, 0x0u>), dim3((unsigned)planes), dim3(ENS_THREADS), 0, (hipStream_t)stream,
-                       partials, stats, spp);
+    hipLaunchKernelGGL((fold_slots_kernel<4, 0x0u>), dim3((unsigned)planes), dim3(FR_THREADS), 0, (hipStream_t)stream,
+                       partials, stats, (long long)spp, ENS_SLOT);
     CTSI_LAUNCH_CHECK();
     return CTSI_OK;
 }

@@ -19,8 +19,6 @@ namespace {
 
 constexpr int Z0_MAX_BLOCKS = 8192;
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 struct Z0Row {
     float a, s;
     bool active;

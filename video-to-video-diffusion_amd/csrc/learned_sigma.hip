@@ -15,8 +15,6 @@ namespace {
 
 constexpr int LS_MAX_BLOCKS = 2048;        // 256 CUs x 8 blocks of 256 threads
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 inline unsigned grid_for(long long work) {
     long long blocks = (work + 255) / 256;
     return (unsigned)(blocks > LS_MAX_BLOCKS ? LS_MAX_BLOCKS : blocks);

@@ -4,58 +4,22 @@
 //   ctsi_depth_residual_adj  g_x = -W^T (y - W x) and per-sample sum r^2 in one pass over the decoded volume x
 //   ctsi_guide_apply         z += c_b g_z (and the data-prediction history, and the bf16 U-Net input slice), c_b from the
 //                            per-sample sum r^2 in device memory
-// ctsi_depth_residual_adj is the one with structure; it follows ctsi_depth_project (depth_consistency.hip): one block of four
-// waves owns TILE consecutive positions of one plane and stages whole depth columns in LDS -- xs[d_out][TILE], rs[d_in][TILE]
-// (y first, then the residual in its place) -- so x is read from HBM once and g_x written once; measure -> subtract ->
-// measure_adj would be three passes and a y-sized temporary.  A lane is a position (unit-stride LDS rows: no bank conflicts);
-// the waves split the k rows in the residual phase and the j rows in the adjoint phase (a register sum over the rows k whose
-// band holds j, their range found once per block), so at TILE = 64 the W[k][j] operand is wave-uniform (scalar loads).  TILE = 32 (deep volumes)
-// puts two rows in a wave.  Sums run over the band supports only, ascending, one fma per term.  sum r^2: the residual
-// re-evaluated in fp64 from the fp32 values in LDS (products of two fp32 are exact in fp64; ascending over the band), reduced
-// per block by a fixed shuffle tree into one slot per block; a second launch folds each sample's slots in a fixed order
-// (thread t takes slots t, t + 256, ... ascending, then the same tree).  No atomics, every slot has one writer: the same bits
-// on every run.
-#include "ctsi_internal.h"
+// ctsi_depth_residual_adj is the one with structure, written against the column-tile frame (depth_tile.h): the tile in LDS is
+// xs[d_out][TILE], rs[d_in][TILE] (y first, then the residual in its place), so x is read from HBM once and g_x written once;
+// measure -> subtract -> measure_adj would be three passes and a y-sized temporary.  The waves split the k rows in the residual
+// phase and the j rows in the adjoint phase (a register sum over the rows k whose band holds j, their range found once per
+// block).  Sums run over the band supports only, ascending, one fma per term.  sum r^2: the residual re-evaluated in fp64 from
+// the fp32 values in LDS (products of two fp32 are exact in fp64; ascending over the band), reduced per block into the slots of
+// ctsi_depth_project_blocks and folded per sample in the fixed order of fixed_reduce.h.
+#include "depth_tile.h"
 
 namespace {
 
-constexpr int MG_MAX_D_IN = 64;
-constexpr int MG_MAX_D_OUT = 512;
-constexpr int MG_THREADS = 256;
-constexpr int MG_WAVES = MG_THREADS / 64;
-constexpr int MG_SLOT = 32;                  // positions per partial slot: the layout of ctsi_depth_project_blocks
-constexpr int MG_LDS_TWO_BLOCKS = 80 * 1024; // half of the CU's 160 KiB
 constexpr int MG_MAX_BLOCKS = 2048;          // streaming passes: 256 CUs x 8 blocks of 256 threads
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // the column tile, the residual rows and the adjoint's [d_out][2] row table
 inline size_t residual_lds(int d_in, int d_out, int tile) {
     return (size_t)(d_out + d_in) * tile * sizeof(float) + (size_t)d_out * 2 * sizeof(int);
-}
-
-inline int residual_tile(int d_in, int d_out) {
-    return residual_lds(d_in, d_out, 64) + 256 <= (size_t)MG_LDS_TWO_BLOCKS ? 64 : 32;
-}
-
-inline int slots_per_plane(int hw) { return (hw + MG_SLOT - 1) / MG_SLOT; }
-
-__device__ __forceinline__ void band_of(const int* __restrict__ band, int row, int limit, int& lo, int& hi) {
-    lo = band[2 * row], hi = band[2 * row + 1];
-    lo = lo < 0 ? 0 : lo;                    // a bad table must not index outside the tile
-    hi = hi >= limit ? limit - 1 : hi;
-}
-
-// the block's sum in thread 0, by the fixed tree: 64 lanes by shuffles, then the four wave sums in wave order
-__device__ __forceinline__ double block_sum(double s, double* red /* [MG_WAVES] */) {
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        s = red[0];
-        for (int w = 1; w < MG_WAVES; ++w) s += red[w];
-    }
-    return s;
 }
 
 struct ResidualArgs {
@@ -70,25 +34,21 @@ struct ResidualArgs {
 };
 
 template <int TILE, bool VEC>
-__global__ void __launch_bounds__(MG_THREADS)
+__global__ void __launch_bounds__(DT_THREADS)
 depth_residual_adj_kernel(const ResidualArgs a) {
     extern __shared__ __align__(16) float mg_lds[];
-    __shared__ double red[MG_WAVES];
-    constexpr int RPW = 64 / TILE;               // rows per wave
-    constexpr int STRIDE = MG_WAVES * RPW;
+    __shared__ double red[DT_WAVES];
+    const DepthTile<TILE, VEC> t(a.tiles_pp, a.hw);
+    constexpr int STRIDE = DepthTile<TILE, VEC>::STRIDE;
     float* xs = mg_lds;                          // [d_out][TILE]: x, then g_x in its place
     float* rs = xs + a.d_out * TILE;             // [d_in][TILE]:  y, then r in its place
     int* kb = reinterpret_cast<int*>(rs + a.d_in * TILE);      // [d_out][2]: the first / last row k whose band holds column j
-    const int tile = blockIdx.x % a.tiles_pp;
-    const long long plane = blockIdx.x / a.tiles_pp;
-    const int p0 = tile * TILE;
-    const int valid = a.hw - p0 < TILE ? a.hw - p0 : TILE;
-    const float* xg = a.x + plane * a.d_out * (long long)a.hw + p0;
-    const float* yg = a.y + plane * a.d_in * (long long)a.hw + p0;
-    float* gg = a.gx + plane * a.d_out * (long long)a.hw + p0;
+    const float* xg = a.x + t.plane * a.d_out * (long long)a.hw + t.p0;
+    const float* yg = a.y + t.plane * a.d_in * (long long)a.hw + t.p0;
+    float* gg = a.gx + t.plane * a.d_out * (long long)a.hw + t.p0;
 
     // the adjoint's table, from the band table of W: column j is read by the rows kb[j][0] .. kb[j][1] ((0, -1): by none)
-    for (int j = threadIdx.x; j < a.d_out; j += MG_THREADS) {
+    for (int j = threadIdx.x; j < a.d_out; j += DT_THREADS) {
         int klo = 0, khi = -1;
         for (int k = a.d_in - 1; k >= 0; --k)
             if (j >= a.band[2 * k] && j <= a.band[2 * k + 1]) {
@@ -97,56 +57,11 @@ depth_residual_adj_kernel(const ResidualArgs a) {
             }
         kb[2 * j] = klo, kb[2 * j + 1] = khi;
     }
-
-    // stage the column tile; positions past the plane's end read as 0 and are never stored.  Four independent loads per
-    // thread are issued before the first LDS store, so a block has its whole tile in flight at the production depth
-    if (VEC) {
-        constexpr int Q = TILE / 4;
-        const int total = (a.d_out + a.d_in) * Q;
-        for (int base = threadIdx.x; base < total; base += 4 * MG_THREADS) {
-            float4 t[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int i = base + u * MG_THREADS;
-                const int row = i / Q, p = (i - row * Q) * 4;
-                t[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (i < total && p < valid)
-                    t[u] = row < a.d_out ? *reinterpret_cast<const float4*>(xg + (long long)row * a.hw + p)
-                                         : *reinterpret_cast<const float4*>(yg + (long long)(row - a.d_out) * a.hw + p);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int i = base + u * MG_THREADS;
-                const int row = i / Q, p = (i - row * Q) * 4;
-                if (i < total) *reinterpret_cast<float4*>(xs + row * TILE + p) = t[u];    // rs follows xs: one row index
-            }
-        }
-    } else {
-        const int total = (a.d_out + a.d_in) * TILE;
-        for (int base = threadIdx.x; base < total; base += 4 * MG_THREADS) {
-            float t[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int i = base + u * MG_THREADS;
-                const int row = i / TILE, p = i - row * TILE;
-                t[u] = 0.0f;
-                if (i < total && p < valid)
-                    t[u] = row < a.d_out ? xg[(long long)row * a.hw + p] : yg[(long long)(row - a.d_out) * a.hw + p];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int i = base + u * MG_THREADS;
-                if (i < total) xs[i] = t[u];          // row * TILE + p == i
-            }
-        }
-    }
+    t.stage_rows(xs, xg, yg, a.d_out, a.d_in, a.hw);
     __syncthreads();
 
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int pos = lane % TILE;
-    const int row0 = wave * RPW + lane / TILE;    // RPW == 1: wave-uniform, so W / band loads are scalar
-    const bool live = pos < valid;
+    const int pos = t.pos(), row0 = t.row0();
+    const bool live = pos < t.valid;
 
     // residual: rs[k] = y[k] - sum_j W[k][j] xs[j] in fp32 (what the adjoint reads), and the same sum in fp64 for sum r^2
     double sum = 0.0;
@@ -182,57 +97,15 @@ depth_residual_adj_kernel(const ResidualArgs a) {
     }
     __syncthreads();
 
-    if (VEC) {
-        constexpr int Q = TILE / 4;
-        for (int i = threadIdx.x; i < a.d_out * Q; i += MG_THREADS) {
-            const int row = i / Q, p = (i - row * Q) * 4;
-            if (p < valid)
-                *reinterpret_cast<float4*>(gg + (long long)row * a.hw + p) = *reinterpret_cast<const float4*>(xs + row * TILE + p);
-        }
-    } else {
-        for (int i = threadIdx.x; i < a.d_out * TILE; i += MG_THREADS) {
-            const int row = i / TILE, p = i - row * TILE;
-            if (p < valid) gg[(long long)row * a.hw + p] = xs[row * TILE + p];
-        }
-    }
-
-    sum = block_sum(sum, red);
-    if (threadIdx.x == 0) {
-        // one slot per MG_SLOT positions: a 64-wide tile owns two, the second one (when the plane has it) holds zero
-        const int slot = tile * (TILE / MG_SLOT);
-        double* out = a.partials + plane * a.slots_pp + slot;
-        out[0] = sum;
-        if (TILE / MG_SLOT == 2 && slot + 1 < a.slots_pp) out[1] = 0.0;
-    }
+    t.store_rows(gg, xs, a.d_out, a.hw);
+    block_reduce<1, 0u>(&sum, red);
+    if (threadIdx.x == 0) t.template write_slot<1>(a.partials, a.slots_pp, &sum);
 }
 
-// one block per sample: thread t folds slots t, t + 256, ... of the sample's planes ascending, then the fixed tree
-__global__ void __launch_bounds__(MG_THREADS)
-depth_residual_finalize_kernel(const double* __restrict__ partials, double* __restrict__ sumsq, long long slots_ps) {
-    __shared__ double red[MG_WAVES];
-    const double* p = partials + (long long)blockIdx.x * slots_ps;
-    double v = 0.0;
-    for (long long base = threadIdx.x; base < slots_ps; base += 4 * MG_THREADS) {
-        double t[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const long long i = base + u * MG_THREADS;
-            t[u] = i < slots_ps ? p[i] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v += t[u];
-    }
-    v = block_sum(v, red);
-    if (threadIdx.x == 0) sumsq[blockIdx.x] = v;
-}
-
-template <int TILE, bool VEC>
-void residual_launch(const ResidualArgs& a, long long blocks, size_t lds, void* stream) {
-    auto k = depth_residual_adj_kernel<TILE, VEC>;
-    static CtsiPerDeviceOnce attr_once;
-    if (attr_once.first()) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, MG_LDS_TWO_BLOCKS);
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(MG_THREADS), lds, (hipStream_t)stream, a);
-}
+struct ResidualKernel {
+    template <int TILE, bool VEC>
+    static auto get() { return depth_residual_adj_kernel<TILE, VEC>; }
+};
 
 // ---- z0 ------------------------------------------------------------------------------------------------------------------
 struct Z0Row {
@@ -395,28 +268,20 @@ extern "C" int ctsi_depth_residual_adj(const float* x, const float* y, const flo
     CTSI_CHECK_ARG(x && y && W && band && g_x && partials && sumsq, "ctsi_depth_residual_adj: null argument");
     CTSI_CHECK_ARG(n > 0 && c > 0 && d_in > 0 && d_out > 0 && hw > 0,
                    "ctsi_depth_residual_adj: bad sizes n=%d c=%d d_in=%d d_out=%d hw=%d", n, c, d_in, d_out, hw);
-    CTSI_CHECK_ARG(d_in <= MG_MAX_D_IN && d_out <= MG_MAX_D_OUT,
-                   "ctsi_depth_residual_adj: depths d_in=%d d_out=%d exceed the limits d_in <= %d, d_out <= %d", d_in, d_out,
-                   MG_MAX_D_IN, MG_MAX_D_OUT);
+    DT_CHECK_DEPTHS("ctsi_depth_residual_adj", d_in, d_out);
     const long long planes = (long long)n * c;
-    const int tile = residual_tile(d_in, d_out);
+    const int tile = tile_for(residual_lds(d_in, d_out, 64));
     const int tiles_pp = ceil_div(hw, tile);
     const long long blocks = planes * tiles_pp, slots = planes * slots_per_plane(hw);
     CTSI_CHECK_ARG(blocks < (1ll << 31) && slots < (1ll << 31), "ctsi_depth_residual_adj: n=%d c=%d hw=%d give too many tiles", n,
                    c, hw);
-    const size_t lds = residual_lds(d_in, d_out, tile);
     const ResidualArgs a = {x, y, W, band, g_x, partials, d_in, d_out, hw, tiles_pp, slots_per_plane(hw)};
     const bool vec = (hw % 4) == 0 && aligned16(x) && aligned16(y) && aligned16(g_x);
-    if (tile == 64) {
-        if (vec) residual_launch<64, true>(a, blocks, lds, stream);
-        else residual_launch<64, false>(a, blocks, lds, stream);
-    } else {
-        if (vec) residual_launch<32, true>(a, blocks, lds, stream);
-        else residual_launch<32, false>(a, blocks, lds, stream);
-    }
+    launch_tiled<ResidualKernel>(a, tile, vec, blocks, residual_lds(d_in, d_out, tile), stream);
     CTSI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(depth_residual_finalize_kernel, dim3((unsigned)n), dim3(MG_THREADS), 0, (hipStream_t)stream, partials,
-                       sumsq, (long long)c * slots_per_plane(hw));
+    // one block per sample folds the slots of the sample's c planes
+    hipLaunchKernelGGL((fold_slots_kernel<1, 0u>), dim3((unsigned)n), dim3(FR_THREADS), 0, (hipStream_t)stream, partials, sumsq,
+                       (long long)c * slots_per_plane(hw), 1);
     CTSI_LAUNCH_CHECK();
     return CTSI_OK;
 }

@@ -15,8 +15,6 @@ namespace {
 
 constexpr int PRED_MAX_BLOCKS = 2048;        // 256 CUs x 8 blocks of 256 threads
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 struct PredRow {
     float a, b0, b1;
 };

@@ -14,8 +14,6 @@ namespace {
 
 constexpr int WF_MAX_BLOCKS = 2048;        // 256 CUs x 8 blocks of 256 threads
 
-inline bool aligned_to(const void* p, int bytes) { return ((uintptr_t)p & (uintptr_t)(bytes - 1)) == 0; }
-
 // V: the widest of uint4 / uint2 / uint32_t / uint16_t that divides the channel bytes and both voxel pitches
 template <typename V>
 __global__ void __launch_bounds__(256)
