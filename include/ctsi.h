@@ -422,6 +422,18 @@ size_t ctsi_slice_metrics_workspace_doubles(int n, int c, int d, int h, int w);
 int ctsi_slice_metrics(const float* a, const float* b, int n, int c, int d, int h, int w, int window, float max_val,
                        double* workspace, double* out, void* stream);
 
+/* multi-planar and 3-D volume metrics (csrc/volume_metrics.hip): the SSIM of ctsi_slice_metrics under a separable window of
+ * radii (rd, rh, rw) <= 7 -- axial (0,R,R), coronal (R,0,R), sagittal (R,R,0), volumetric (Rd,R,R) -- over fp32 (n,c,d,h,w)
+ * volumes read in place, zero padding counted in the window.  gd/gh/gw: 2r+1 normalised fp32 weights each on the device, or
+ * all three NULL for the box window.  axis 0/1/2 = d/h/w names the tables' index: out[len(axis)][4] = (SUM of squared
+ * differences, SUM of SSIM, NaN count of a, NaN count of b) over every voxel with that index; the caller divides by the
+ * slice's voxel count.  workspace: ctsi_volume_metrics_workspace_doubles() doubles (enough for any axis; 0 for an invalid shape
+ * or radius).  Two launches, no atomics: the same bits on every run. */
+size_t ctsi_volume_metrics_workspace_doubles(int n, int c, int d, int h, int w, int rd, int rh, int rw);
+int ctsi_volume_metrics(const float* a, const float* b, int n, int c, int d, int h, int w, int rd, int rh, int rw,
+                        const float* gd, const float* gh, const float* gw, int axis, float max_val, double* workspace,
+                        double* out, void* stream);
+
 /* hipMemsetAsync on the engine stream (zeroing GroupNorm accumulators / padded channels);
  * capturable as a memset node.                                                              */
 int ctsi_memset_async(void* ptr, int value, size_t bytes, void* stream);

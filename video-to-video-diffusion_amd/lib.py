@@ -144,6 +144,8 @@ SIGNATURES = {
     "ctsi_blend_normalize": (_i, [_vp, _vp, _ll, _vp], True),
     "ctsi_slice_metrics_workspace_doubles": (_sz, [_i, _i, _i, _i, _i], False),
     "ctsi_slice_metrics": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp], True),
+    "ctsi_volume_metrics_workspace_doubles": (_sz, [_i] * 8, False),
+    "ctsi_volume_metrics": (_i, [_vp, _vp] + [_i] * 8 + [_vp, _vp, _vp, _i, _f, _vp, _vp, _vp], True),
     "ctsi_comm_unique_id": (_i, [_vp], True),
     "ctsi_comm_init": (_i, [C.POINTER(_vp), _vp, _i, _i], True),
     "ctsi_comm_destroy": (None, [_vp], False),

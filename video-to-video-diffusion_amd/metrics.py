@@ -8,6 +8,7 @@ Return types and edge cases follow the reference: python floats, PSNR clamped to
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Dict, List
 
@@ -83,6 +84,97 @@ def calculate_video_metrics(video1, video2, max_val=1.0) -> Dict[str, object]:
     return {'psnr': float(np.mean(psnr_values)) if psnr_values else 0.0,
             'ssim': float(np.mean(ssim_values)) if ssim_values else 0.0,
             'psnr_per_frame': psnr_values, 'ssim_per_frame': ssim_values}
+
+
+VOLUME_PLANES = {'axial': 0, 'coronal': 1, 'sagittal': 2}     # plane -> the axis its slices are indexed by (d, h, w)
+VOLUME_WINDOW_MAX = 15                                        # 2 * 7 + 1: the kernel's largest radius
+
+
+def gaussian_window(size: int, sigma: float) -> np.ndarray:
+    """exp(-(i - R)^2 / (2 sigma^2)), i = 0 .. size - 1, R = size // 2, normalised to sum 1 in float64."""
+    x = np.arange(size, dtype=np.float64) - size // 2
+    g = np.exp(-(x * x) / (2.0 * float(sigma) ** 2))
+    return g / g.sum()
+
+
+def calculate_volume_metrics(video1, video2, max_val=1.0, planes=('axial', 'coronal', 'sagittal'), window_size=11,
+                             window='box', sigma=1.5, volumetric=True, window_depth=None) -> Dict[str, object]:
+    """PSNR / SSIM of (B,C,D,H,W) or (C,D,H,W) volumes in the three reformats and under a 3-D window
+    (ctsi_volume_metrics: the volumes are read in place, no permuted copy).  'axial' slices are (h, w) planes indexed by d,
+    'coronal' (d, w) planes indexed by h, 'sagittal' (d, h) planes indexed by w; the window of a plane is window_size x
+    window_size inside it.  Each requested plane gives {'psnr', 'ssim', 'psnr_per_slice', 'ssim_per_slice'} (means over the
+    plane's slices and the per-slice lists, a slice taken over B and C as calculate_video_metrics does); `volumetric` adds
+    'ssim3d' and 'ssim3d_per_slice' (D floats): the same SSIM under a window_depth x window_size x window_size window
+    (window_depth defaults to window_size).  window: 'box' (the reference's avg_pool weights) or 'gaussian' (sigma); zero
+    padding counts in the window, and a window wider than an axis is legal.  Any NaN in either input gives zeros and empty
+    lists in every entry."""
+    planes = tuple(planes)
+    for name in planes:
+        if name not in VOLUME_PLANES:
+            raise ValueError(f"unknown plane {name!r}: expected some of {sorted(VOLUME_PLANES)}")
+    if window not in ('box', 'gaussian'):
+        raise ValueError(f"unknown window {window!r}: expected 'box' or 'gaussian'")
+    window_depth = window_size if window_depth is None else window_depth
+    for key, val in (('window_size', window_size), ('window_depth', window_depth)):
+        if not isinstance(val, int) or val < 1 or val % 2 == 0 or val > VOLUME_WINDOW_MAX:
+            raise ValueError(f"{key} must be an odd integer in [1, {VOLUME_WINDOW_MAX}], got {val!r}")
+    if window == 'gaussian' and not sigma > 0:
+        raise ValueError(f"sigma must be positive, got {sigma!r}")
+    if not isinstance(video1, torch.Tensor) or not isinstance(video2, torch.Tensor) or video1.shape != video2.shape \
+            or video1.dim() not in (4, 5) or video1.numel() == 0:
+        raise ValueError(f"expected two equal (B,C,D,H,W) or (C,D,H,W) tensors, got {tuple(getattr(video1, 'shape', ()))} "
+                         f"and {tuple(getattr(video2, 'shape', ()))}")
+    a, b = _as_device_f32(video1), _as_device_f32(video2)
+    if a.dim() == 4:
+        a, b = a.unsqueeze(0), b.unsqueeze(0)
+    n, c, d, h, w = a.shape
+    R, Rd = window_size // 2, window_depth // 2
+    # (key, radii, axis) of every launch; all tables land in one device tensor
+    jobs = [(name, tuple(0 if i == VOLUME_PLANES[name] else R for i in range(3)), VOLUME_PLANES[name]) for name in planes]
+    if volumetric:
+        jobs.append(('ssim3d', (Rd, R, R), 0))
+    lens = [(d, h, w)[axis] for _, _, axis in jobs]
+    if not jobs:
+        return {}
+    ctx = Ctx.get(a.device)
+    table = torch.empty((sum(lens), 4), dtype=torch.float64, device=a.device)
+    with ctx.scope():
+        gauss = None
+        if window == 'gaussian':          # one upload: the weights of both window lengths
+            gs, gdp = gaussian_window(window_size, sigma), gaussian_window(window_depth, sigma)
+            gauss = torch.from_numpy(np.concatenate([gs, gdp, np.ones(1)]).astype(np.float32)).to(a.device)
+            p_s = gauss.data_ptr()                                  # window_size weights | window_depth weights | 1.0 (radius 0)
+            p_d, p_1 = p_s + 4 * window_size, p_s + 4 * (window_size + window_depth)
+        ws_n = max(ctx.lib.volume_metrics_workspace_doubles(n, c, d, h, w, *radii) for _, radii, _ in jobs)
+        ws = torch.empty(max(ws_n, 1), dtype=torch.float64, device=a.device)
+        row = 0
+        for (key, radii, axis), ln in zip(jobs, lens):
+            if gauss is None:
+                g = (None, None, None)
+            else:
+                g = tuple(ctypes.c_void_p(p_1 if r == 0 else (p_d if (i == 0 and key == 'ssim3d') else p_s))
+                          for i, r in enumerate(radii))
+            ctx.lib.volume_metrics(_ptr(a), _ptr(b), n, c, d, h, w, radii[0], radii[1], radii[2], g[0], g[1], g[2], axis,
+                                   float(max_val), _ptr(ws), ctypes.c_void_p(table.data_ptr() + row * 32), ctx.sptr)
+            row += ln
+    for x in (a, b):
+        x.record_stream(ctx.stream)
+    st = table.cpu().numpy()
+    nan = bool(st[:, 2].sum() > 0 or st[:, 3].sum() > 0)
+    out: Dict[str, object] = {}
+    row = 0
+    for (key, radii, axis), ln in zip(jobs, lens):
+        rows, count = st[row:row + ln], float(a.numel() // ln)
+        row += ln
+        ssim_values: List[float] = [] if nan else [float(r[1] / count) for r in rows]
+        ssim_mean = float(np.mean(ssim_values)) if ssim_values else 0.0
+        if key == 'ssim3d':
+            out['ssim3d'], out['ssim3d_per_slice'] = ssim_mean, ssim_values
+            continue
+        psnr_values: List[float] = [] if nan else [_psnr_from_mse(r[0] / count, max_val) for r in rows]
+        out[key] = {'psnr': float(np.mean(psnr_values)) if psnr_values else 0.0, 'ssim': ssim_mean,
+                    'psnr_per_slice': psnr_values, 'ssim_per_slice': ssim_values}
+    return out
 
 
 def measurement_residual(volume, thick, profile) -> Dict[str, List[float]]:
