@@ -945,6 +945,27 @@ int ctsi_depth_residual_adj(const float* x, const float* y, const float* W, cons
 int ctsi_guide_apply(float* z, float* hist, const float* g_z, const double* sumsq, float coef_z, float coef_hist,
                      int normalize, void* zin, int c_total, int c_off, int n, int c, int d, int h, int w, void* stream);
 
+/* Training patches from volumes resident in HBM (csrc/patch_sample.hip): the crop, depth resample, flips
+ * and rot90 of the reference's patch dataset for a whole batch in one launch.
+ * table: n rows of CTSI_PATCH_COLS int64 on the device --
+ *   { thin pointer, thick pointer, d_thin, d_thick, h, w, z, y0, x0, k0, k1, flags }
+ *   -- the two volumes of the sample ((d, h, w) contiguous, `storage` elements: CTSI_PATCH_F32 or CTSI_PATCH_F16), their
+ *   sizes, the corner of the thin window, the thick slice range [k0, k1) and flags = flip W | flip H << 1 | k << 2.
+ * out_thin (n, 1, depth_thin, ph, pw) fp32: out[d, i, j] = src[z + d, y0 + i', x0 + j'] with (i', j') the preimage of (i, j)
+ *   under "flip W, then flip H, then rot90 k" (torch.flip / torch.rot90 on the last two axes); slices d >= d_thin - z are -1.
+ * out_thick (n, 1, depth_thick, ph, pw) fp32: the k1 - k0 thick slices of the same window resampled linearly along depth as
+ *   F.interpolate(mode='trilinear', align_corners=False) does in fp32, under the same in-plane map.  depth_thick == 0 with
+ *   out_thick == NULL writes no thick output (the thick pointer of the rows is then not read).
+ * A pure gather: no atomics, every output element written once, nothing read outside the windows.  Odd k needs ph == pw.
+ * The table lives on the device, so its rows are the caller's to validate (device_data.DevicePatchSampler does); null
+ * pointers, a bad storage type, non-positive sizes and n > 65535 return CTSI_ERR_INVALID before any launch.  Capture-safe:
+ * no allocation, no synchronisation. */
+#define CTSI_PATCH_COLS 12
+#define CTSI_PATCH_F32 0
+#define CTSI_PATCH_F16 1
+int ctsi_patch_sample(const long long* table, int n, int storage, int depth_thin, int depth_thick, int ph, int pw,
+                      float* out_thin, float* out_thick, void* stream);
+
 /* depth-sharding collectives (RCCL over xGMI, one process per GPU) --------------------------- *
  * a volume's depth is cut into `world` slabs; before a depth-3 conv a slab needs one boundary
  * slice of each depth neighbour (models/unet3d.py:56,96,204-207,218-221; models/vae.py:27,65-69,86-90), GroupNorm needs

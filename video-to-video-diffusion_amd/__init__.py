@@ -14,6 +14,7 @@ from .sampler import DDIMSampler, DDPMSampler, DPMSolverSampler, EDMSampler, Heu
 from .generate import generate_batch, interpolate_videos  # noqa: F401
 from .ema import EMAWeights  # noqa: F401
 from .optim import FusedAdam, FusedAdamW, clip_grad_norm_  # noqa: F401
+from .device_data import DevicePatchLoader, DevicePatchSampler, DeviceVolumeStore  # noqa: F401
 from . import parallel  # noqa: F401,E402
 
 

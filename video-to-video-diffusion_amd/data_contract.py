@@ -1,7 +1,8 @@
 """Tensor contract between the reference's data pipeline and the engine.
 
 The data pipeline itself (DICOM / HF download, preprocessing, augmentation: reference data/*.py) is CPU I/O and is NOT
-rebuilt.  What the engine must stay compatible with is the format those loaders hand to the model:
+rebuilt (what the patch dataset does per item at training time -- crop, depth resample, flips, rotation -- runs on the
+device from volumes kept in HBM: device_data.py).  What the engine must stay compatible with is the format those loaders hand to the model:
 
   * the per-patient cache file  `case_*.pt` = dict {'input' | 'thick': (1, D_thick, H, W), 'target' | 'thin':
     (1, D_thin, H, W), 'category', 'patient_id'}  (data/patch_slice_interpolation_dataset.py:257-258);

@@ -254,6 +254,7 @@ SIGNATURES = {
     "ctsi_guide_z0": (_i, [_vp, _vp, _f, _f, _i, _f, _vp, _i, _i, _i, _i, _i, _vp], True),
     "ctsi_depth_residual_adj": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], True),
     "ctsi_guide_apply": (_i, [_vp, _vp, _vp, _vp, _f, _f, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp], True),
+    "ctsi_patch_sample": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp], True),
     "ctsi_graph_begin_capture": (_i, [_vp], True),
     "ctsi_graph_end_capture": (_i, [_vp, C.POINTER(_vp)], True),
     "ctsi_graph_launch": (_i, [_vp, _vp], True),
